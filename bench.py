@@ -6,6 +6,12 @@ metric grid, 192x192x23 sigma (config C3: 50 km, dt = 150 s, hydrostatic, full
 advection + diffusion + split-explicit, physics stubbed), synthetic ICBC (syn-icbc v1).
 A step = one `tend` + one `bdyval` (Main/mod_regcm_interface.F90:189,208).
 Scaling: strong (the 192x192x23 domain is split into set_nproc tiles across N GPUs).
+
+A plain run sets up, settles the clock, warms up, times the K steps and prints the result line.
+`--dump-outputs DIR` also writes the prognostic state the timed steps left (`DIR/<field>.npy`).
+`--full` adds every secondary figure, each a run of its own after the timed steps: the drop-in
+tend + bdyval pair, per-kernel HIP-event times with the dominant-kernel roofline, and the CPU
+baseline.
 """
 from __future__ import annotations
 
@@ -20,11 +26,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from regcm_amd.config import CONFIGS, set_nproc  # noqa: E402
+from regcm_amd.config import (CONFIGS, NH_STATE_FIELDS, QX_STATE_FIELDS, STATE_FIELDS,  # noqa: E402
+                              TKE_STATE_FIELDS, field_levels, set_nproc)
 from regcm_amd import icbc  # noqa: E402
 from regcm_amd.traffic import kernel_bytes, step_bytes, step_bytes_nh  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, 8 TB/s
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this much (all ranks together)
+DUMP_SEED = 20261019    # of the sample drawn from a state larger than that
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
 
 
@@ -171,6 +180,54 @@ def settle(eng, seconds: float, bcast=None):
         chunk = min(2 * chunk, 64)
 
 
+def hold_boundary(data):
+    """The lateral boundary data held at its first record: every XxB_BT of the ICBC set to zero.
+    The synthetic ICBC spans one boundary interval (b0 and the tendency bt towards the record
+    dtbdys later), and the bench reads no further record (no bdyin), so past the interval
+    b0 + bt * xbctime extrapolates without bound (+1 K and +1 m/s every 6 h) until the step
+    fails: C3 stops with CFL VIOLATION at step 4756, which any run of more than some 4 000 steps
+    reached.  With bt = 0 the kernels do the same work on a boundary that stays where it is, and
+    --steps may be as large as the measurement needs."""
+    for name, a in data["state"].items():
+        if name.endswith("_BT"):
+            data["state"][name] = np.zeros_like(a)
+    return data
+
+
+def output_fields(rc):
+    """The prognostic state of rc's core and options: what a caller of rcmdyn_step reads back
+    (the SAV fields of tests/test_restart_gpu.py)."""
+    names = list(STATE_FIELDS)
+    if rc.idynamic == 2:
+        names = [n for n in names if n not in ("DSTOR", "HSTOR")] + NH_STATE_FIELDS
+    if rc.ibltyp == 2:
+        names += TKE_STATE_FIELDS
+    if rc.nqx > 2:
+        names += QX_STATE_FIELDS
+    return names
+
+
+def dump_outputs(eng, rc, outdir, world=1, rank=0):
+    """Write the engine's prognostic state as outdir/<field>.npy (float64; with more than one
+    rank outdir/<field>.rank<r>.npy, each the global box with this rank's tiles filled).  A state
+    of more than DUMP_BYTES is thinned: every field keeps the same share of its points, a sorted
+    sample of the flattened [k][i][j] array drawn without replacement by PCG64(DUMP_SEED), the
+    same points for fields of one shape and from run to run; the file is then 1-D."""
+    os.makedirs(outdir, exist_ok=True)
+    names = output_fields(rc)
+    size = {n: field_levels(n, rc.kz, rc.nsplit) * rc.iy * rc.jx for n in names}
+    share = min(1.0, DUMP_BYTES / (8.0 * world * sum(size.values())))
+    picks = {}
+    for name in names:
+        a = eng.get(name).ravel()
+        if share < 1.0:
+            if a.size not in picks:
+                rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+                picks[a.size] = np.sort(rng.choice(a.size, int(a.size * share), replace=False))
+            a = a[picks[a.size]]
+        np.save(os.path.join(outdir, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,7 +242,18 @@ def main():
                     help="eager steps timed per kernel with HIP events (dominant-kernel roofline)")
     ap.add_argument("--settle-ms", type=float, default=100.0,
                     help="untimed steps run for this long before the warm-up (GPU clock ramp); 0: none")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the prognostic state they left as DIR/<field>.npy "
+                         "(float64, at most 48 MiB: a fixed seeded sample of a larger state).  The state is "
+                         "put again after the settle phase, whose step count varies, so the files depend "
+                         "on the arguments alone")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the drop-in tend + bdyval pair, the per-kernel "
+                         "times (--prof-steps) with the dominant-kernel roofline, and the CPU baseline "
+                         "(--no-cpu-baseline, --cpu-budget, --cpu-threads); without it those options do nothing")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -194,7 +262,7 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     rc = CONFIGS[args.config]
     nh = rc.idynamic == 2
-    data = icbc.generate_nh(rc) if nh else icbc.generate(rc)
+    data = hold_boundary(icbc.generate_nh(rc) if nh else icbc.generate(rc))
     cj, ci = set_nproc(world, rc.jx, rc.iy)
 
     from regcm_amd.dycore import DynCore, comm_unique_id, runtime_info
@@ -219,7 +287,9 @@ def main():
                       comm_rank=rank, comm_size=world, device=local_rank, unique_id=uid)
     else:
         eng = DynCore(rc, data["split"], device=local_rank)
+    clock0 = eng.get_time()
     eng.put_state(data["state"])
+    sav0 = {name: eng.get(name) for name in output_fields(rc)} if args.dump_outputs else None
     eng.bdyval()
 
     def barrier():
@@ -234,6 +304,14 @@ def main():
             dist.broadcast(t, src=0)
             return int(t.item())
     settle_steps, settle_s = settle(eng, args.settle_ms * 1e-3, bcast)
+    if args.dump_outputs and settle_steps:
+        # the settle phase ran for a time, not a count: back to the initial state and clock (a
+        # restart, tests/test_restart_gpu.py), so the W + K steps below start from the same
+        # state in every run; the captured graphs stay
+        for name, a in sav0.items():        # a field the ICBC does not hold: as it was read back
+            eng.put(name, data["state"].get(name, a))
+        eng.set_time(*clock0)
+        eng.bdyval()
     eng.step(args.warmup)
     barrier()
     t0 = time.perf_counter()
@@ -249,28 +327,32 @@ def main():
         wall = float(tt.item())
     t_step = wall / args.steps
     sypd = rc.dt / (365.0 * t_step)
-    # the drop-in call sequence of INTEGRATION.md section 4 (RCM_run: rcmdyn_tend then
-    # rcmdyn_bdyval per step through the C-ABI, each replaying its own graph), same K steps,
-    # after two untimed pairs that capture its graphs (one per ping-pong parity)
-    for _ in range(2):
-        eng.tend()
-        eng.bdyval()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        eng.tend()
-        eng.bdyval()
-    barrier()
-    wall_d = time.perf_counter() - t0
-    if dist is not None:
-        import torch
-        tt = torch.tensor([wall_d], dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        wall_d = float(tt.item())
-    # per-kernel device time (HIP events around each launch on the engine's stream), on
-    # every rank (the eager steps exchange halos), after the timed region
-    kt = eng.kernel_times(args.prof_steps) if args.prof_steps > 0 else {}
-    barrier()
+    if args.dump_outputs:
+        dump_outputs(eng, rc, args.dump_outputs, world, rank)
+    kt, wall_d = {}, None
+    if args.full:
+        # the drop-in call sequence of INTEGRATION.md section 4 (RCM_run: rcmdyn_tend then
+        # rcmdyn_bdyval per step through the C-ABI, each replaying its own graph), same K steps,
+        # after two untimed pairs that capture its graphs (one per ping-pong parity)
+        for _ in range(2):
+            eng.tend()
+            eng.bdyval()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.tend()
+            eng.bdyval()
+        barrier()
+        wall_d = time.perf_counter() - t0
+        if dist is not None:
+            import torch
+            tt = torch.tensor([wall_d], dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            wall_d = float(tt.item())
+        # per-kernel device time (HIP events around each launch on the engine's stream), on
+        # every rank (the eager steps exchange halos), after the timed region
+        kt = eng.kernel_times(args.prof_steps) if args.prof_steps > 0 else {}
+        barrier()
     if nh:
         from regcm_amd.nhbase import acoustic_substeps
         istep = acoustic_substeps(rc, data["split"]["nh_dtsmax"], 2.0 * rc.dt, 2)
@@ -321,7 +403,7 @@ def main():
         "vs_baseline": None,
         "dtype": "f64",
         "data": ("synthetic (syn-icbc v1" + (" NH variant" if nh else "") +
-                 ", PCG64 seed 20261015): no DOMAIN/ICBC files offline"),
+                 ", PCG64 seed 20261015, boundary held at its first record): no DOMAIN/ICBC files offline"),
         "config": {"workload": (f"{args.config} {rc.jx}x{rc.iy}x{rc.kz} ds={rc.ds}km dt={rc.dt}s " +
                                 ("non-hydrostatic (MM5 core), upstream adv + 4th-order diff + sound "
                                  f"({istep} acoustic sub-steps, upper radiative BC, Rayleigh damping) "
@@ -329,14 +411,10 @@ def main():
                                  "hydrostatic, upstream adv + 4th-order diff + split-explicit "
                                  "(nsplit=2) + iboudy=5 relaxation, physics stubbed")),
                    "tiles": f"{cj}x{ci}", "step": "tend + bdyval"},
-        "roofline": roof,
         "step_roofline": {"achieved": step_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": step_achieved / HBM_PEAK_GBS, "algorithmic_bytes": bstep,
                           "note": "SURVEY 8(d) " + ("B_nh" if nh else "B_h") + " per step / wall time per step"},
-        "kernel_us": {k: round(v[1] * 1e3, 2) for k, v in sorted(kt.items(), key=lambda kv: -kv[1][0] * kv[1][1])},
         "device_ms_per_step": dev_ms,
-        "dropin_ms_per_step": wall_d / args.steps * 1e3,
-        "dropin_note": "rcmdyn_tend + rcmdyn_bdyval per step (INTEGRATION.md section 4), timed like value",
         "runtime": rt,
         "settle": {"steps": settle_steps, "s": round(settle_s, 3),
                    "note": "untimed steps before the W warm-up steps, until --settle-ms of wall time has "
@@ -346,7 +424,16 @@ def main():
     }
     if world > 1:
         line["runtime_per_rank"] = rts
-    if not args.no_cpu_baseline and world == 1:
+    if args.dump_outputs:
+        line["outputs"] = {"dir": args.dump_outputs, "fields": output_fields(rc), "dtype": "f64",
+                           "restart_after_settle": bool(settle_steps)}
+    if args.full:
+        line["roofline"] = roof
+        line["kernel_us"] = {k: round(v[1] * 1e3, 2)
+                             for k, v in sorted(kt.items(), key=lambda kv: -kv[1][0] * kv[1][1])}
+        line["dropin_ms_per_step"] = wall_d / args.steps * 1e3
+        line["dropin_note"] = "rcmdyn_tend + rcmdyn_bdyval per step (INTEGRATION.md section 4), timed like value"
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(rc, data, args.cpu_budget, args.cpu_threads)
     print(json.dumps(line))
     if dist is not None:
