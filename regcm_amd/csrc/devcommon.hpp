@@ -62,23 +62,13 @@ static __device__ int rcm_pt_count = 0;
 
 // XCD-aware block placement.  The workgroups of a launch go round-robin over the 8 XCDs, each
 // with its own L2: in blockIdx order the four neighbours of a tile run on other XCDs, so every
-// stencil halo is fetched again from beyond L2.  xcd_block() renumbers the blocks: launch-order
-// block b takes tile start(b % 8) + b / 8 of the row-major tile order (x fastest, z slowest), so
+// stencil halo is fetched again from beyond L2.  xcd_tile2d renumbers the blocks of one z slice:
+// launch-order block b takes tile start(b % 8) + b / 8 of the slice's row-major tile order, so
 // each XCD walks one contiguous band of tile rows and the rows above and below a tile are (but
-// at the band edges) its own XCD's.
+// at the band edges) its own XCD's; z (a level, say) keeps its launch order
 struct Blk3 {
   int x, y, z;
 };
-__device__ __forceinline__ Blk3 xcd_block() {
-  const int nx = (int)gridDim.x, ny = (int)gridDim.y;
-  const int n = nx * ny * (int)gridDim.z;
-  const int b = ((int)blockIdx.z * ny + (int)blockIdx.y) * nx + (int)blockIdx.x;
-  const int per = n >> 3, rem = n & 7, x = b & 7;
-  const int t = x * per + (x < rem ? x : rem) + (b >> 3);
-  return {t % nx, (t / nx) % ny, t / (nx * ny)};
-}
-// the same within one z slice: (x, y) renumbered so each XCD walks one contiguous band of the
-// slice's rows; z (a level, say) keeps its launch order
 __device__ __forceinline__ void xcd_tile2d(int& bx, int& by) {
   const int nx = (int)gridDim.x, n = nx * (int)gridDim.y;
   const int b = (int)blockIdx.y * nx + (int)blockIdx.x;
@@ -101,28 +91,12 @@ __device__ __forceinline__ int xcd_range(int B, int base, int n) {
   const int fx = base + ((x - b0 + 8) & 7);
   return t + (B - fx) / 8;
 }
-// THREAD_POINT over xcd_block()'s tile
-#define THREAD_POINT_XCD(j1, i1)                                        \
-  const Blk3 xb_ = xcd_block();                                         \
-  const int j = (j1) + xb_.x * (int)blockDim.x + (int)threadIdx.x;      \
-  const int i = (i1) + xb_.y * (int)blockDim.y + (int)threadIdx.y;      \
-  const int k = xb_.z + 1;                                              \
-  (void)k;
-
 // thread -> (j, i, k) over a box starting at (j1, i1); k = blockIdx.z + 1
 #define THREAD_POINT(j1, i1)                                   \
   const int j = (j1) + (int)(blockIdx.x * blockDim.x + threadIdx.x); \
   const int i = (i1) + (int)(blockIdx.y * blockDim.y + threadIdx.y); \
   const int k = (int)blockIdx.z + 1;                              \
   (void)k;
-
-// The frame's rows start on 128-B lines (pitch of 16 doubles), but the index ranges start a
-// few points in (jde1 = j0 + G): a 64-wide wavefront from jde1 touches five lines per field
-// instead of four, and the fifth is fetched again by the neighbouring block (another XCD).
-// ALIGN_J moves a box's first thread column down to the line boundary at or below j1 (those
-// lanes idle: every such kernel rejects j < j1 by its own range test); jalign (engine.hpp) is
-// the host's matching count of extra columns for the grid.
-#define ALIGN_J(j1) ((j1) - jalign(g, j1))
 
 // psc2psd at one dot point, Main/mpplib/mod_mppparam.F90:13811-13862.
 __device__ __forceinline__ bool psc2psd_at(const Geom& g, const double* pc, int j, int i, double& v) {

@@ -341,7 +341,7 @@ struct rcmdyn_engine {
   bool qfuse() const { return cfg.idynamic != 2 && !no_qfuse; }
   // nqx = 5, hydrostatic qfuse: the species' serial fix joins the qv / qc one after the split
   // corrections (k_negfix_serial_qx)
-  bool serial_with_corr() const { return NEGFIX_POST && qfuse() && hc.nsp > 0; }
+  bool serial_with_corr() const { return qfuse() && hc.nsp > 0; }
   // halo/compute overlap of the hydrostatic prologue exchange (Part, kernels.hpp) on a
   // decomposed domain; RCMDYN_NO_OVERLAP=1: the atm1/p* part first, then the atm2 part beside
   // k_columns only
@@ -601,12 +601,8 @@ struct rcmdyn_engine {
     for (double** p : {&f.a1pp, &f.a2pp, &f.pr1, &f.rho1, &f.cr, &f.xkcr, &f.ppten, &f.ct, &f.cu, &f.cv,
                        &f.cpp, &f.cdt, &f.se, &f.sf, &f.spi, &f.th})
       *p = dalloc(t, P3);
-    if (!NH_XPRFORM) f.xpr = dalloc(t, P3);
-    if (!NH_UDFORM) { f.ud = dalloc(t, P3); f.vd = dalloc(t, P3); }
-    if (NH_NEGLIST) {             // every interior point of both species at most once
-      f.neglist = talloc<unsigned>(t, 2 * P3);
-      f.negcnt = talloc<int>(t, 1);
-    }
+    f.neglist = talloc<unsigned>(t, 2 * P3);     // every interior point of both species at most once
+    f.negcnt = talloc<int>(t, 1);
     for (double** p : {&f.a1w, &f.a2w, &f.wten, &f.cw})
       *p = dalloc(t, P4);
     f.ppb0 = dalloc(t, P3); f.ppbt = dalloc(t, P3); f.wwb0 = dalloc(t, P4); f.wwbt = dalloc(t, P4);
@@ -729,11 +725,6 @@ struct rcmdyn_engine {
     cfg = *c;
     dry = plan != nullptr;
     if (cfg.abi_version != RCMDYN_ABI_VERSION) throw std::runtime_error("rcmdyn: ABI version mismatch");
-#if RCM_SC_TIMING_PART || defined(RCM_SP_TIMING_M2)
-    // a timing-only build computes wrong results on purpose: never by accident
-    if (!std::getenv("RCMDYN_TIMING_BUILD"))
-      throw std::runtime_error("rcmdyn: this library is a timing-only build (set RCMDYN_TIMING_BUILD=1 to run it)");
-#endif
     if (cfg.idynamic != 1 && cfg.idynamic != 2) throw std::runtime_error("rcmdyn: idynamic must be 1 or 2");
     if (cfg.idynamic == 2) {
       if (!(cfg.nh_dtsmax > 0.0) || !(cfg.nh_xmsf > 0.0))
@@ -1617,11 +1608,11 @@ struct rcmdyn_engine {
     exchange_generic(fn, on, on);
   }
 
-  // NH_DPRFORM: the acoustic update forms dprddx / dprddy from atm0%pr as the reference
+  // the acoustic update forms dprddx / dprddy from atm0%pr as the reference
   // defines them (Main/mod_params.F90:2676-2686); values a host put must be exactly those, or
   // the engine would silently compute with others
   void check_dprd() {
-    if (!NH_DPRFORM || cfg.idynamic != 2 || dry) { dprd_put = false; return; }
+    if (cfg.idynamic != 2 || dry) { dprd_put = false; return; }
     int* bad = nullptr;
     HIPCHK(hipMalloc(&bad, sizeof(int)));
     HIPCHK(hipMemsetAsync(bad, 0, sizeof(int), stream));
@@ -1817,16 +1808,11 @@ struct rcmdyn_engine {
     // on the second stream beside k_nh_tend_c (which reads them at its own point only), the
     // cqv/cqc exchange beside k_nh_tend_d (which does not read them)
     const bool ovl = halo && !no_overlap && phase == TEND_ALL && !slice && cfg.isladvec != 1;
-    // ci1a: the interior cross columns from the 128-B line at or below jci1 (NH_ALIGN)
-    struct Grids { dim3 fr, ce1, cek, ci1, cik, cik1, di1, dik, ci1a; };
+    struct Grids { dim3 fr, ce1, ci1; };
     auto grids = [&](const Geom& g) {
       const int nce_j = g.jce2 - g.jce1 + 1, nce_i = g.ice2 - g.ice1 + 1;
       const int nci_j = g.jci2 - g.jci1 + 1, nci_i = g.ici2 - g.ici1 + 1;
-      const int ndi_j = g.jdi2 - g.jdi1 + 1, ndi_i = g.idi2 - g.idi1 + 1;
-      return Grids{grid3(g.nj, g.ni, kp), grid3(nce_j, nce_i, 1), grid3(nce_j, nce_i, kz),
-                   grid3(nci_j, nci_i, 1), grid3(nci_j, nci_i, kz), grid3(nci_j, nci_i, kz - 1),
-                   grid3(ndi_j, ndi_i, 1), grid3(ndi_j, ndi_i, kz),
-                   grid3(nci_j + (NH_ALIGN ? jalign(g, g.jci1) : 0), nci_i, 1)};
+      return Grids{grid3(g.nj, g.ni, kp), grid3(nce_j, nce_i, 1), grid3(nci_j, nci_i, 1)};
     };
     if (phase & TEND_PRE) {
     // isladvec = 1: k_sladv forms ud*msfd two points out (the reference exchanges atmx%ud 2
@@ -1865,7 +1851,7 @@ struct rcmdyn_engine {
       const Geom& g = t.g;
       const NHFields f = nhfields(t);
       const Grids q = grids(g);
-      KLAUNCH(k_nh_coeff_raw, NH_XKCOL ? q.ce1 : q.cek, BLK, 0, stream, g, dc, f);
+      KLAUNCH(k_nh_coeff_raw, q.ce1, BLK, 0, stream, g, dc, f);
     });
     // ovl: the exchange is issued in TEND_POST, after k_nh_tend_c went to the second stream
     if (!ovl) xch({{FK::NCR, kz}, {FK::QDOT, kp}, {FK::NXKCR, kz}});
@@ -1922,17 +1908,13 @@ struct rcmdyn_engine {
                 qx_args(t));      // the column box, as the hydrostatic launch: its jci x ici fix
         KLAUNCH(k_qx_serial, dim3(hc.nsp * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc,
                 qx_args(t));
-        if (NEGFIX_POST)
-          KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
-                  qx_args(t));
+        KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
+                qx_args(t));
       }
-      if (NH_NEGLIST)
-        KLAUNCH(k_nh_negfix, dim3(1024), dim3(256), 0, stream, g, dc, f);
-      else
-        KLAUNCH(k_nh_negfix, q.cik, BLK, 0, stream, g, dc, f);
+      KLAUNCH(k_nh_negfix, dim3(1024), dim3(256), 0, stream, g, dc, f);
       KLAUNCH(k_nh_negfix_serial, dim3(2 * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc, f);
       // tend's time filters (tfuse = 0) with part A of the first acoustic sub-step (sound, :163-718)
-      if (NH_A1COL && nh_tfuse)     // part A alone: one column walk per cross column
+      if (nh_tfuse)     // part A alone: one column walk per cross column
         KLAUNCH(k_nh_a1_col, q.ce1, BLK, 0, stream, g, dc, f);
       else
         KLAUNCH(k_nh_tfilter_a1, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, kp), BLK, 0, stream, g, dc, f);
@@ -1953,7 +1935,7 @@ struct rcmdyn_engine {
                     fin, first, 2);
           return;
         }
-        KLAUNCH(k_nh_sound_uv, grid3(g.jde2 - g.jde1 + 1 + (NH_ALIGN && !NH_WRAP_PT ? jalign(g, g.jde1) : 0), g.ide2 - g.ide1 + 1, kz),
+        KLAUNCH(k_nh_sound_uv, grid3(g.jde2 - g.jde1 + 1, g.ide2 - g.ide1 + 1, kz),
                 BLK, 0, stream, g, dc, ds, nhfields(t), istep, fin, first, part);
       };
       if (halo && !no_overlap) {
@@ -1972,7 +1954,7 @@ struct rcmdyn_engine {
         const Geom& g = t.g;
         const NHFields f = nhfields(t);
         const Grids q = grids(g);
-        KLAUNCH(k_nh_sound_bc, NH_WRAP ? q.ci1 : q.ci1a, BLK, 0, stream, g, dc, ds, f, istep, it);
+        KLAUNCH(k_nh_sound_bc, q.ci1, BLK, 0, stream, g, dc, ds, f, istep, it);
       });
       if (cfg.ifupr == 1) {
         if (it == 1 && alarm) {
@@ -1993,10 +1975,10 @@ struct rcmdyn_engine {
         const NHFields f = nhfields(t);
         const Grids q = grids(g);
         if (halo)
-          KLAUNCH(k_nh_sound_cd, NH_ALIGN_CD && !NH_WRAP ? q.ci1a : q.ci1, BLK, 0, stream, g, t.gw, t.westore, dc, ds, f, istep, (int)(it == istep),
+          KLAUNCH(k_nh_sound_cd, q.ci1, BLK, 0, stream, g, t.gw, t.westore, dc, ds, f, istep, (int)(it == istep),
                   (int)(it < istep));
         else
-          KLAUNCH(k_nh_sound_cd, NH_ALIGN_CD && !NH_WRAP ? q.ci1a : q.ci1, BLK, 0, stream, g, g, f.estore, dc, ds, f, istep, (int)(it == istep),
+          KLAUNCH(k_nh_sound_cd, q.ci1, BLK, 0, stream, g, g, f.estore, dc, ds, f, istep, (int)(it == istep),
                   (int)(it < istep));
       });
     }
@@ -2012,19 +1994,19 @@ struct rcmdyn_engine {
   void tend_d_launch(Tile& t, const NHFields& f, int istep) {
     const Geom& g = t.g;
     const dim3 gd((g.jdi2 - g.jdi1 + 64) / 64, (g.idi2 - g.idi1 + TD_I) / TD_I, cfg.kz);
-    KLAUNCH(k_nh_tend_d, NH_ZFIRST ? dim3(gd.z, gd.x, gd.y) : gd, dim3(64, TD_I), 0, stream, g, dc, ds, f, istep);
+    KLAUNCH(k_nh_tend_d, dim3(gd.z, gd.x, gd.y), dim3(64, TD_I), 0, stream, g, dc, ds, f, istep);
   }
   void tend_c_launch(Tile& t, const NHFields& f, int istep) {
     const Geom& g = t.g;
     const dim3 gc((g.nj + TC_J - 1) / TC_J, (g.ni + TC_I - 1) / TC_I, cfg.kz + 1);
     if (hc.nsp) {
-      KLAUNCH(k_nh_tend_c<true>, NH_ZFIRST ? dim3(gc.z, gc.x, gc.y) : gc, dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+      KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
               (int)diag, istep);
       // the chains of qi, qr, qs after it on the same stream
       KLAUNCH(k_nh_qx_tend, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0, stream, g, dc, ds, f,
               qx_args(t));
     } else {
-      KLAUNCH(k_nh_tend_c<false>, NH_ZFIRST ? dim3(gc.z, gc.x, gc.y) : gc, dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
               (int)diag, istep);
     }
   }
@@ -2229,9 +2211,8 @@ struct rcmdyn_engine {
         if (serial_with_corr()) return;          // the serial chains then run in launch_corrections
         KLAUNCH(k_qx_serial, dim3(hc.nsp * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc,
                 qx_args(t));
-        if (NEGFIX_POST)
-          KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
-                  qx_args(t));
+        KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
+                qx_args(t));
       });
     }
     if (!fused) xch({{FK::CQV, kz}, {FK::CQC, kz}});     // else k_scalars computed the ring
@@ -2317,8 +2298,7 @@ struct rcmdyn_engine {
       const Geom& g = t.g;
       const int c = t.cur;
       const long npts = (long)((g.jdx2() - g.jde1 + 2) / 2) * (g.idx2() - g.ide1 + 1);   // point pairs per level
-      dim3 gr = SCOR_FLAT ? dim3((unsigned)((npts + 255) / 256), 1, kz)
-                          : grid3((g.jdx2() - g.jde1 + 2) / 2, g.idx2() - g.ide1 + 1, kz);
+      dim3 gr((unsigned)((npts + 255) / 256), 1, kz);
       const int adv = (int)(q + 1 == tiles.size());
       // qfuse: trailing z slices run the serial sweeps of the flagged moisture planes
       const QFix qf = qfix(t);

@@ -95,7 +95,8 @@ struct Geom {
 };
 // the negative-moisture fix's row bitmap: words per (species, level) plane; the LDS (doubles) of
 // its serial part (qxcommon.hpp): the row sweep's two interior rows and 13 per lane, or the
-// wavefront's 4-slot ring per row; the wavefront's block: a thread per interior row
+// wavefront's ring (4 doubles per row reserved; the hand-over between wavefronts uses 64 per
+// wavefront); the wavefront's block: a thread per interior row
 __host__ __device__ __forceinline__ int negfix_rowwords(const Geom& g) { return (g.ici2 - g.ici1 + 1 + 31) / 32; }
 __host__ __device__ __forceinline__ int negfix_threads(const Geom& g) {
   const int r = (g.ici2 - g.ici1 + 1 + 63) / 64 * 64;
@@ -103,14 +104,15 @@ __host__ __device__ __forceinline__ int negfix_threads(const Geom& g) {
 }
 // the row sweep's LDS (one wavefront: two rows + 13 per lane)
 __host__ __device__ __forceinline__ int negfix_sweep_lds(const Geom& g) { return 2 * (g.jci2 - g.jci1 + 1) + 64 * 13; }
-// the LDS of a launch whose block per plane can run either path: the wavefront's 4-slot ring per
-// row is added only when a negfix_threads block holds a thread per row (a tall tile
+// the LDS of a launch whose block per plane can run either path: the wavefront's ring (4 doubles per
+// row) is added only when a negfix_threads block holds a thread per row (a tall tile
 // then requests the sweep's LDS and keeps it, instead of failing the launch)
 __host__ __device__ __forceinline__ int negfix_lds(const Geom& g) {
   const int a = negfix_sweep_lds(g), R = g.ici2 - g.ici1 + 1, b = R <= negfix_threads(g) ? 4 * R : 0;
   return a > b ? a : b;
 }
-// columns between j1 and the frame's 128-B line boundary at or below it (ALIGN_J, devcommon.hpp)
+// columns between j1 and the frame's 128-B line boundary at or below it (the rows start on
+// 128-B lines, a pitch of 16 doubles; wrap_j, kernels_nh.hip)
 __host__ __device__ __forceinline__ int jalign(const Geom& g, int j1) { return (j1 - g.j0) & 15; }
 
 // Run constants (read-only on device, one copy per engine).

@@ -156,9 +156,6 @@ __device__ __forceinline__ bool part_skip(const Part& p, int j1, int j2, int i1,
 #ifndef COL_KU
 #define COL_KU 1
 #endif
-#ifndef COL_PF
-#define COL_PF 1
-#endif
 // QX: nqx = 5, tvfac with the total water load (an instance of its own, so the nqx = 2 kernel
 // keeps its code)
 template <bool QX>
@@ -204,10 +201,10 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
     }
     return;
   }
-  // COL_XCD: the column blocks of one tile in XCD-contiguous runs of rows, so a block's i + 1
+  // the column blocks of one tile in XCD-contiguous runs of rows, so a block's i + 1
   // row (the dot points of its divergence) is the next row's block's own and a hit in the same
   // L2; the noise partial keeps the block's logical slot, so the sums are unchanged
-  const int cb = (COL_XCD && f.pt.part == 0) ? xcd_range(bb, 0, ncol) : bb;
+  const int cb = (f.pt.part == 0) ? xcd_range(bb, 0, ncol) : bb;
   // k_scalars appends after this (part 2 follows part 1 and the k_scalars blocks of part 1)
   if (f.qfuse && cb == 0 && threadIdx.x == 0 && f.pt.part != 2) *f.negcnt = 0;
   const int tx = (int)threadIdx.x % COLW, ty = (int)threadIdx.x / COLW;     // column, level group
@@ -290,9 +287,8 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
   }
   // the operands of new_pressure (scan wavefront) and of the geopotential column are loaded
   // before the barrier, so their latency overlaps the wait for the other level groups instead
-  // of following the pten / qdot scan (COL_PF = 0: loaded where they are used)
+  // of following the pten / qdot scan
   const int gwave = COLW == 32 ? 2 : 1;
-#if COL_PF
   double psbv = 0.0, pav = 0.0, pbt0 = 0.0, dtv = 0.0, xbt = 0.0, fg1[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
   int rgc = 0, ibc = 0;
   if (ce && ty == 0) {
@@ -317,7 +313,6 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
     gps = LD(f.psa, o2);
     ght = LD(f.ht, o2);
   }
-#endif
   __syncthreads();
   PT_MARK();
   double na = 0.0, nb = 0.0;
@@ -339,7 +334,6 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
     }
     if (ce) {
       // new_pressure
-#if COL_PF
       const double dt = dtv;
       if (ci && rgc > 0 && c->iboudy == 4) {
         // sponge2d, Main/mod_bdycod.F90:3065-3122
@@ -349,32 +343,12 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
         nudge_coef(c, ibc, kz, xf, xg);
         pt = relax(pt, xf, xg, fg1[0], fg1[1], fg1[2], fg1[3], fg1[4]);
       }
-#else
-      const double dt = s->dt;
-      const double psbv = LD(f.psb, o2);
-      if (ci && f.rgcr[o2 >> 3] > 0 && c->iboudy == 4) {
-        // sponge2d, Main/mod_bdycod.F90:3065-3122
-        const int ib = f.ibcr[o2 >> 3];
-        pt = c->wgtx[ib] * pt + (d_one - c->wgtx[ib]) * LD(f.pbt, o2);
-      } else if (ci && f.rgcr[o2 >> 3] > 0) {
-        const double xt = s->xbctime + dt;
-        double xf, xg;
-        nudge_coef(c, f.ibcr[o2 >> 3], kz, xf, xg);
-#define FG1(dj, di) ((LD(f.pb0, O2(dj, di)) + xt * LD(f.pbt, O2(dj, di))) - LD(f.psb, O2(dj, di)))
-        pt = relax(pt, xf, xg, FG1(0, 0), FG1(-1, 0), FG1(1, 0), FG1(0, -1), FG1(0, 1));
-#undef FG1
-      }
-#endif
       ST(f.ptenn, o2, pt);
       const double pc = psbv + pt * dt;
       ST(f.psc, o2, pc);
       if (f.qfuse) {
         // the RA filter of p* (Main/mod_tendency.F90:420, filter_ra_2d) into the next buffers
-#if COL_PF
         const double pa = pav;
-#else
-        const double pa = LD(f.psa, o2);
-#endif
         if (ci) {
           const double d = c->gnu1 * (pc + psbv - d_two * pa);
           ST(f.bpsb, o2, pa + d);
@@ -386,11 +360,7 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
       }
       if (s->lcount > 0 && ci && own) {
         na = fabs(pt);
-#if COL_PF
         nb = fabs((pc + psbv - d_two * pav) / (dt * dt * d_rfour));
-#else
-        nb = fabs((pc + psbv - d_two * LD(f.psa, o2)) / (dt * dt * d_rfour));
-#endif
       }
     }
   }
@@ -398,13 +368,8 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
   // groups 2k and 2k+1 share wavefront k)
   if (ce && ty == gwave) {
     // geopotential column, bottom-up
-#if COL_PF
     const double ps = gps;
     double top = ght;
-#else
-    const double ps = LD(f.psa, o2);
-    double top = LD(f.ht, o2);
-#endif
     double tdk1 = sTD[(kz - 1) * COLW + tx];
     const double tv = tdk1 * rp * sTV[(kz - 1) * COLW + tx];
     if (c->ipgf == 1) top = top + rgas * T00PG / c->pgfaa1 * rcm_powpos((ps + ptop) / P00PG, c->pgfaa1);  // :2045
@@ -1172,18 +1137,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   const double xkcs = xkc * c->rdxsq * pb;
   if (f.xkcs) ST(f.xkcs, o3, xkcs);
   // ================= temperature
-#if RCM_SC_TIMING_PART == 2
-  if (0)
-#endif
   {
     double td = d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXT, 0, 0), H1T(sXT, -1, 0),
                                    H1T(sXT, 1, 0), H1T(sXT, 0, -1), H1T(sXT, 0, 1), 1);
     // vadv3d ind = 1 (Main/mod_advection.F90:771-783): pf/pb from psb (mkslice :263-271)
     {
       const double ptop = c->ptop, c287 = c->c287;
-#if RCM_SC_TIMING_PART >= 3
-#define powpos(x, y) ((x) + 0.0 * (y))
-#endif
 #define PF(K) ((c->sigma[K] * pb + ptop) * d_1000)
 #define PB(K) ((c->hsigma[K] * pb + ptop) * d_1000)
       if (k >= 2)
@@ -1194,9 +1153,6 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
                          c->twt2[k + 1] * t1 * powpos(PF(k + 1) / PB(k), c287))) * c->xds[k];
 #undef PB
 #undef PF
-#if RCM_SC_TIMING_PART >= 3
-#undef powpos
-#endif
     }
     // omega, Main/mod_tendency.F90:1200-1214
     double om;
@@ -1238,9 +1194,6 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     ST(f.b2t, o3, t1 + d);
     ST(f.b1t, o3, ct);
   }
-#if RCM_SC_TIMING_PART == 1 || RCM_SC_TIMING_PART == 3
-  return;
-#endif
   // ================= qv
   // hadvqv, or the semi-Lagrangian start of qxdyn from k_sladv (isladvec = 1, :1361-1363)
   double tq = c->isladvec ? LD(f.slqv, o3)
@@ -1503,22 +1456,11 @@ __global__ __launch_bounds__(512) void k_negfix_serial(Geom g, const Consts* __r
     negfix_collect(g, q.depf, q.depplane, plane, (int)threadIdx.x, (int)blockDim.x);
     __syncthreads();
   }
-  if (NEGFIX_POST) {
-    negfix_resolve(g, n ? q.cqc : q.cqv, n ? q.fqc : q.fqv, q.depplane, plane, k, lds, negfix_lds(g), NoPost{},
-                   [](int, int, double) {}, c->negfix_mode);
-    return;
-  }
-  const QvRaw acc{g, c, n ? q.o1qc : q.o1qv, n ? q.o2qc : q.o2qv, q.psc, q.opsa, q.opsb,
-                  n ? q.n1qc : q.n1qv, n ? q.n2qc : q.n2qv, n, k};
-  negfix_resolve(g, n ? q.cqc : q.cqv, n ? q.fqc : q.fqv, q.depplane, plane, k, lds, negfix_lds(g), acc,
-                 [=](int jj, int i, double v) {
-                   double x[5];
-                   acc.load(jj, i, x);
-                   acc.apply(jj, i, v, x);
-                 }, c->negfix_mode);
+  negfix_resolve(g, n ? q.cqc : q.cqv, n ? q.fqc : q.fqv, q.depplane, plane, k, lds, negfix_lds(g), NoPost{},
+                 [](int, int, double) {}, c->negfix_mode);
 }
 
-// NEGFIX_POST: the filters of the points k_negfix_serial fixed, a thread per interior point of
+// the filters of the points k_negfix_serial fixed, a thread per interior point of
 // a (qv | qc, level) plane (z = plane)
 __global__ void k_negfix_post(Geom g, const Consts* __restrict__ c, QFix q) {
   const int j = g.jci1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -1579,9 +1521,6 @@ __device__ __forceinline__ void negfix_list(Geom g, const Consts* c, QFix q, int
 #ifndef SP_KU
 #define SP_KU 1
 #endif
-#ifndef SP_PF
-#define SP_PF 1
-#endif
 __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
     Geom g, const Consts* __restrict__ c, const double* __restrict__ a1u, const double* __restrict__ a1v,
     const double* __restrict__ a2u, const double* __restrict__ a2v, const double* __restrict__ a1t,
@@ -1597,9 +1536,9 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
       negfix_serial_plane(g, c, qf, b - nproj, negfix_sweep_lds(g) <= 4 * c->kz * SPC ? lds : nullptr);
     return;
   }
-  // SP_XCD: each XCD takes a contiguous run of column rows, so the i + 1 row of the u, v
+  // each XCD takes a contiguous run of column rows, so the i + 1 row of the u, v
   // divergence, which the next row's block loads as its own, is a hit in the same L2
-  const int b = SP_XCD ? xcd_range((int)blockIdx.x, 0, nproj) : (int)blockIdx.x;
+  const int b = xcd_range((int)blockIdx.x, 0, nproj);
   PT_DECL
   const int tx = (int)threadIdx.x % SPC, ty = (int)threadIdx.x / SPC;
   // owned dot points, plus psdota on the right/top ghost ring (the split corrections of the
@@ -1664,10 +1603,9 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
     }
   }
   // the 2-D operands of this thread's first (mode, sum) item are loaded before the barrier, so
-  // their latency overlaps the wait instead of following it (SP_PF = 0: loaded where used)
+  // their latency overlaps the wait instead of following it
   const int ns = c->nsplit;
   const long q = valid ? g.ix(j, i) : 0;
-#if SP_PF
   double pf_st = 0.0, pf_a = 0.0, pf_b = 0.0;
   if (valid && ty < 2 * ns) {
     const int l = ty % ns + 1;
@@ -1679,7 +1617,6 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
       if (ce) { pf_a = F2(psa, j, i); pf_b = F2(psb, j, i); }
     }
   }
-#endif
   __syncthreads();
   PT_MARK();
   if (!valid) return;
@@ -1693,7 +1630,7 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
   }
   for (int w = ty; w < 2 * ns; w += SPG) {
     const int l = w % ns + 1;
-    const bool pf = SP_PF && w == ty;
+    const bool pf = w == ty;
     if (w < ns) {
       const double ds = pf ? pf_st : dstor[(long)(l - 1) * g.plane + q];
       double d3 = d_zero, d2 = d_zero;
@@ -1837,11 +1774,7 @@ __global__ __launch_bounds__((SB + 2 * SPH) * (SB + 2 * SPH)) void k_spstep_fuse
   const int jr0 = J1 - SPH, ir0 = I1 - SPH;          // region origin (global)
   const int tx = threadIdx.x, ty = threadIdx.y;        // R x R, one region point each
   const double aam = c->aam[l - 1], dtau = c->dtau[l - 1], hbar = c->hbar[l - 1];
-#ifdef RCM_SP_TIMING_M2      // timing-only builds (wrong results): the sub-step count capped
-  const int m2 = min((int)aam * 2, RCM_SP_TIMING_M2);
-#else
   const int m2 = (int)aam * 2;
-#endif
   const double dtau2 = dtau * d_two, rdx2 = d_one / c->dx2;
 #define WSLOT(a, l, s) ((a) + ((long)((s) - 1) * c->nsplit + ((l) - 1)) * w.plane)
   const double* D1 = WSLOT(deld, l, 1); const double* D2 = WSLOT(deld, l, 2); const double* D3 = WSLOT(deld, l, 3);
@@ -2003,30 +1936,18 @@ __device__ __forceinline__ void split_correct_body(
     PT_PRINT(6);
     return;
   }
-#if SCOR_FLAT
   // the (pair, row) points of a level flattened: every lane of a block has a point (no idle
   // second block column on a 192-wide tile), rows follow one another in the lanes
   const int npr = (g.jdx2() - g.jde1 + 2) / 2;
-#if SCOR_XCD
   // the kz levels of one pair block run consecutively on one XCD: the 2-D sums, psdota and
   // msfd each level reads are fetched into that XCD's L2 once
   const int tq = xcd_range(((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x,
                            zbdy * (int)gridDim.x, kz * (int)gridDim.x);
   const int bxq = tq / kz, k = tq % kz + 1;
   const bool first = tq == 0;
-#else
-  const int bxq = (int)blockIdx.x, k = (int)blockIdx.z - zbdy + 1;
-  const bool first = blockIdx.x == 0 && (int)blockIdx.z == zbdy;
-#endif
   const int q = bxq * 256 + (int)threadIdx.y * 64 + (int)threadIdx.x;
   const int j = g.jde1 + q % npr;
   const int i = g.ide1 + q / npr;
-#else
-  const int j = g.jde1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  const int i = g.ide1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-  const int k = (int)blockIdx.z - zbdy + 1;
-  const bool first = blockIdx.x == 0 && blockIdx.y == 0 && (int)blockIdx.z == zbdy;
-#endif
   // last tile's launch, block 0: the Bleck noise sums of every tile (fixed-order tree over the
   // k_columns partials, Main/mod_tendency.F90:1449-1459), then rcmtimer%advance + dt switch
   // (:608-616); nothing else here reads the clock.  The same lane then copies the step's error

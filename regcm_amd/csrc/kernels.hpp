@@ -16,13 +16,6 @@ constexpr int MAXSEG = 64;
 constexpr int NEGFIX_BLOCKS = 64;
 // fused spstep tiling: SPB x SPB owned cross points + SPH halo (>= sub-steps per mode)
 constexpr int SPB = 16, SPH = 8;
-// the 8 x 8 form (k_spstep_fused<8>) below this many 16 x 16 blocks (engine.hip)
-// timing-only builds (wrong results): the scalars blocks run 1 = the t chain only, 2 = the
-// moisture chains only, 3 = the t chain only without the x**y of vadv3d, 4 = every chain
-// without the x**y of vadv3d
-#ifndef RCM_SC_TIMING_PART
-#define RCM_SC_TIMING_PART 0
-#endif
 // k_update: XCD-aware tile placement within each level (xcd_tile2d, devcommon.hpp) on tiles of
 // fewer points than this (rank tiles).  Alternating on one box (profiles/r05/tile_ab_uxcd.log,
 // c3_uxcd_ab.log): 96x48 0.0792 -> 0.0773-0.0783 ms, 96x96 0.0962 -> 0.0936, 96x192 0.1325 ->
@@ -30,11 +23,7 @@ constexpr int SPB = 16, SPH = 8;
 #ifndef UPD_XCD_BELOW
 #define UPD_XCD_BELOW (192 * 192 / 2 + 1)
 #endif
-// k_split_correct(_bdy): the level's point pairs flattened over the blocks (1) or 64 x 4 pair
-// tiles (0)
-#ifndef SCOR_FLAT
-#define SCOR_FLAT 1
-#endif
+// the 8 x 8 form (k_spstep_fused<8>) below this many 16 x 16 blocks (engine.hip)
 #ifndef SP8_BELOW
 #define SP8_BELOW 128
 #endif
@@ -57,26 +46,12 @@ constexpr int COLW = RCM_COLW, COLG = RCM_COLG, COLT = COLW * COLG;   // COLG le
 #define RCM_SPC 32
 #endif
 constexpr int SPC = RCM_SPC, SPG = 8;
-// k_split_project / k_split_correct(_bdy): XCD-contiguous block placement (xcd_range,
+// k_split_project / k_split_correct(_bdy) place their blocks XCD-contiguously (xcd_range,
 // devcommon.hpp): the rows a projection block shares with the next row's block, and the 2-D
-// split sums every level of a correction block column reads, stay in one L2.  Round 6,
-// alternating on one box (profiles/r06/tile_ab_split_xcd.log): k_split_project 24.4 -> 18.1-19.5
-// us at C3, the C3 step 193.9-199.8 -> 186.0-189.9 us; the correction placement is neutral at
-// C3 and takes the 96x48 rank tile's correction kernel 12.9 -> 10.9 us (step 0.0783-0.0788 ->
-// 0.0771-0.0772 ms with both)
-#ifndef SP_XCD
-#define SP_XCD 1
-#endif
-#ifndef SCOR_XCD
-#define SCOR_XCD 1
-#endif
-// k_columns: the same for its column blocks of a whole tile (part 0): the next row's column block,
-// whose loads overlap this one's (atm1 at i + 1, p* at i +- 1), on the same XCD.  C3 k_columns
-// 26.4-28.2 -> 24.3-25.6 us, the step 184.8 -> 183.7 us (3 alternations on one box), neutral on
-// the 96 x 48 rank tile (profiles/r06/tile_ab_colx_spbdy.log)
-#ifndef COL_XCD
-#define COL_XCD 1
-#endif
+// split sums every level of a correction block column reads, stay in one L2.  k_columns does
+// the same for its column blocks of a whole tile (part 0): the next row's column block, whose
+// loads overlap this one's (atm1 at i + 1, p* at i +- 1), runs on the same XCD.  The
+// measurements are in DESIGN.md section 4 (round 6)
 // depth of the wide exchange: SPH plus the ghost ring the fused split step also produces
 constexpr int SPX = SPH + 1;
 // LDS-tiled momentum block (dot points j x i at one level).  32 x 8 (256 threads, 39 KB of
@@ -213,11 +188,8 @@ __global__ void k_scalars(Geom g, const Consts* __restrict__ c, const StepState*
 __global__ void k_update(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm, Fields fs,
                          int mnx, int mny, int snx, int sny, int xcd);
 __global__ void k_qfilter(Geom g, const Consts* __restrict__ c, Fields f);
-// NEGFIX_POST (qxcommon.hpp): the serial fix passes resolve the chain, k_negfix_post / k_qx_post
-// apply the filters of the points they fixed
-#ifndef NEGFIX_POST
-#define NEGFIX_POST 1
-#endif
+// the serial fix passes resolve the chain (qxcommon.hpp), k_negfix_post / k_qx_post apply the
+// filters of the points they fixed
 __global__ void k_negfix_serial(Geom g, const Consts* __restrict__ c, QFix q);
 __global__ void k_negfix_post(Geom g, const Consts* __restrict__ c, QFix q);
 __global__ void k_split_project(Geom g, const Consts* __restrict__ c, const double* __restrict__ a1u,

@@ -40,7 +40,7 @@ static constexpr double P00 = 1.000000e5;                  // Share/mod_constant
 #define IN_CI(j, i) (in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2))
 #define IN_DI(j, i) (in(j, g.jdi1, g.jdi2) && in(i, g.idi1, g.idi2))
 #define IN_DE(j, i) (in(j, g.jde1, g.jde2) && in(i, g.ide1, g.ide2))
-// wrap_j (NH_WRAP): column of lane tx in block column bx over the n columns from j1, the block
+// wrap_j: column of lane tx in block column bx over the n columns from j1, the block
 // columns starting on the 128-B line at or below j1; lanes below j1 (block column 0 only) take
 // the columns past the last of the ceil(n/64) block columns
 __device__ __forceinline__ int wrap_j(const Geom& g, int j1, int n, int bx, int tx) {
@@ -50,25 +50,17 @@ __device__ __forceinline__ int wrap_j(const Geom& g, int j1, int n, int bx, int 
   return j;
 }
 // thread -> (j, i, k) over the columns j1..j2 on wrap_j's block columns (64 x 4 blocks, grid3's
-// count of block columns); NH_WRAP_PT = 0: THREAD_POINT from j1
-#if NH_WRAP_PT
+// count of block columns)
 #define WRAP_POINT(j1, j2, i1)                                                        \
   const int j = wrap_j(g, j1, (j2) - (j1) + 1, (int)blockIdx.x, (int)threadIdx.x);   \
   const int i = (i1) + (int)(blockIdx.y * blockDim.y + threadIdx.y);                 \
   const int k = (int)blockIdx.z + 1;                                                  \
   (void)k;
-#else
-#define WRAP_POINT(j1, j2, i1) THREAD_POINT(j1, i1)
-#endif
-#if NH_ZFIRST
+// the tendency kernels' (levels, tiles_j, tiles_i) grids: consecutive blocks on consecutive
+// levels of one tile
 #define TBX ((int)blockIdx.y)
 #define TBY ((int)blockIdx.z)
 #define TBZ ((int)blockIdx.x)
-#else
-#define TBX ((int)blockIdx.x)
-#define TBY ((int)blockIdx.y)
-#define TBZ ((int)blockIdx.z)
-#endif
 __device__ __forceinline__ int j0c(const Geom& g) { return g.j0; }
 __device__ __forceinline__ int i0c(const Geom& g) { return g.i0; }
 #define FRAME_POINT()                                                  \
@@ -110,29 +102,20 @@ __device__ __forceinline__ double2 udvd_nh_ld(const Geom& g, int iboudy, const N
 }
 
 // ---------------------------------------------------------------------------------------
-// decouple NH (Main/mod_tendency.F90:852-1066): the decoupled winds ud, vd (with the iboudy
-// inflow/outflow rule) on the dot frame; atm1 pr/rho, the buoyancy helper atmx%pr and the
-// potential temperature th of ithadv = 1 (:1349-1353) on the cross frame with its ghost ring,
-// the points exchange(th,1) fills: th is pointwise in atmx%t and atm1%pr, which are defined
-// there.  The other decoupled fields -- umc, vmc, umd, vmd and atmx w, pp, qv, qc -- are one
-// product (and clip) of a state field each and are formed by their readers.
+// decouple NH (Main/mod_tendency.F90:852-1066): atm1 pr/rho and the potential temperature th
+// of ithadv = 1 (:1349-1353) on the cross frame with its ghost ring, the points exchange(th,1)
+// fills: th is pointwise in atmx%t and atm1%pr, which are defined there.  The other decoupled
+// fields -- ud, vd (with the iboudy inflow/outflow rule, udvd_nh_ld), umc, vmc, umd, vmd, the
+// buoyancy helper atmx%pr and atmx w, pp, qv, qc -- are a product (and clip) of state fields
+// each and are formed by their readers.
 #if NH_OTHER_KERNELS
 __global__ void k_nh_decouple(Geom g, const Consts* __restrict__ c, NHFields f) {
   FRAME_POINT();
   const int kz = c->kz;
-#if !NH_UDFORM
-  if (k <= kz && in(j, g.jde1ga, g.jde2ga) && in(i, g.ide1ga, g.ide2ga)) {
-    const double2 d = udvd_nh(g, c->iboudy, f.a1u, f.a1v, f.rpsda, j, i, k);
-    F3(f.ud, j, i, k) = d.x;                           // umd = ud*msfd: formed by omega, tend_d
-    F3(f.vd, j, i, k) = d.y;
-  }
-#endif
   if (!(in(j, g.jce1ga, g.jce2ga) && in(i, g.ice1ga, g.ice2ga))) return;
   const double rp = F2(f.rpsa, j, i);
   if (k > kz) return;
-#if NH_NEGLIST
   if (j == g.jce1 && i == g.ice1 && k == 1) *f.negcnt = 0;      // k_nh_tend_c lists after this
-#endif
   const double xt = F3(f.a1t, j, i, k) * rp;
   const double xqv = dmax(F3(f.a1qv, j, i, k) * rp, MINQQ);
   const double xtv = xt * (d_one + c->ep1 * xqv);
@@ -141,10 +124,6 @@ __global__ void k_nh_decouple(Geom g, const Consts* __restrict__ c, NHFields f) 
   F3(f.pr1, j, i, k) = pr1;      // atmx t, tv, qv, qc, pp, w: formed by their readers
   F3(f.rho1, j, i, k) = pr1 / (c->rgas * xtv);
   F3(f.th, j, i, k) = xt * rcm_powpos(P00 / pr1, c->rovcp);
-#if !NH_XPRFORM
-  if (IN_CI(j, i))
-    F3(f.xpr, j, i, k) = (xtv - F3(f.t0, j, i, k) - xpp / (c->cpd * F3(f.rho0, j, i, k))) / xt;
-#endif
 }
 #endif
 
@@ -164,22 +143,12 @@ __global__ __launch_bounds__(256, NHOM_W) void k_nh_omega(Geom g, const Consts* 
   // umd, vmd = ud, vd * msfd (decouple :893-994) at the four dot points of the column
   const double m00 = F2(f.msfd, j, i), m01 = F2(f.msfd, j, i + 1), m10 = F2(f.msfd, j + 1, i),
                m11 = F2(f.msfd, j + 1, i + 1);
-  auto ucc = [&](int kk) {
-    return F3(f.ud, j, i, kk) * m00 + F3(f.ud, j, i + 1, kk) * m01 + F3(f.ud, j + 1, i, kk) * m10 +
-           F3(f.ud, j + 1, i + 1, kk) * m11;
-  };
-  auto vcc = [&](int kk) {
-    return F3(f.vd, j, i, kk) * m00 + F3(f.vd, j, i + 1, kk) * m01 + F3(f.vd, j + 1, i, kk) * m10 +
-           F3(f.vd, j + 1, i + 1, kk) * m11;
-  };
   const double ps0 = F2(f.ps0, j, i), dx = F2(f.dpsdxm, j, i), dy = F2(f.dpsdym, j, i);
   F3(f.qdot, j, i, 1) = d_zero;
   F3(f.qdot, j, i, kz + 1) = d_zero;
-#if NH_UDFORM
-  // ud, vd formed here from atm1 u, v at the column's four dot points (decouple no longer
-  // stores them), one pass over the levels: the level's winds give qdot(k) and, with
-  // qdot(k-1), the mass divergence cr(k-1) (the same expressions as the two loops below)
-  (void)ucc; (void)vcc;
+  // ud, vd formed here from atm1 u, v at the column's four dot points (decouple does not
+  // store them), one pass over the levels: the level's winds give qdot(k) and, with
+  // qdot(k-1), the mass divergence cr(k-1)
   const double r00 = F2(f.rpsda, j, i), r01 = F2(f.rpsda, j, i + 1), r10 = F2(f.rpsda, j + 1, i),
                r11 = F2(f.rpsda, j + 1, i + 1);
   const int ib = c->iboudy;
@@ -222,25 +191,6 @@ __global__ __launch_bounds__(256, NHOM_W) void k_nh_omega(Geom g, const Consts* 
     abm = crab(wb); qm = qk; um = uk; vm = vk;
   }
   F3(f.cr, j, i, kz) = abm * dummy + (d_zero - qm) * ps / c->dsigma[kz];
-#else
-  double um = ucc(1), vm = vcc(1);
-  for (int k = 2; k <= kz; k++) {
-    const double uk = ucc(k), vk = vcc(k);
-    F3(f.qdot, j, i, k) = -F3(f.rhof0, j, i, k) * EGRAV_NH * (F3(f.a1w, j, i, k) * F2(f.rpsa, j, i)) / ps0 -
-                          c->sigma[k] * (dx * (c->twt1[k] * uk + c->twt2[k] * um) +
-                                         dy * (c->twt1[k] * vk + c->twt2[k] * vm));
-    um = uk; vm = vk;
-  }
-  const double ps = F2(f.psa, j, i);
-  for (int k = 1; k <= kz; k++) {
-    // umc, vmc = atm1 u, v * msfd (decouple)
-    const double a = F3(f.a1u, j + 1, i + 1, k) * m11 + F3(f.a1u, j + 1, i, k) * m10 -
-                     F3(f.a1u, j, i + 1, k) * m01 - F3(f.a1u, j, i, k) * m00;
-    const double b = F3(f.a1v, j + 1, i + 1, k) * m11 + F3(f.a1v, j, i + 1, k) * m01 -
-                     F3(f.a1v, j + 1, i, k) * m10 - F3(f.a1v, j, i, k) * m00;
-    F3(f.cr, j, i, k) = (a + b) * dummy + (F3(f.qdot, j, i, k + 1) - F3(f.qdot, j, i, k)) * ps / c->dsigma[k];
-  }
-#endif
 }
 #endif
 
@@ -255,9 +205,8 @@ __global__ __launch_bounds__(256, NHOM_W) void k_nh_omega(Geom g, const Consts* 
 // calc_coeff NH (Main/mod_diffusion.F90:215-250): Smagorinsky coefficient with the
 // vertical-velocity term, unscaled (xkcr) ...
 #if NH_OTHER_KERNELS
-#if NH_XKCOL
 // one thread per cross frame column walking k = 1..kz: a2w * (1/p*b) of level k+1 is carried to
-// the next level (the point form reads it again from the k+1 plane); the same values
+// the next level
 __global__ void k_nh_coeff_raw(Geom g, const Consts* __restrict__ c, NHFields f) {
   WRAP_POINT(g.jce1, g.jce2, g.ice1);
   if (!IN_CE(j, i)) return;
@@ -283,22 +232,6 @@ __global__ void k_nh_coeff_raw(Geom g, const Consts* __restrict__ c, NHFields f)
     wk = wk1;
   }
 }
-#else
-__global__ void k_nh_coeff_raw(Geom g, const Consts* __restrict__ c, NHFields f) {
-  WRAP_POINT(g.jce1, g.jce2, g.ice1);
-  if (!IN_CE(j, i)) return;
-  const double u00 = UBD(j, i, k), u10 = UBD(j + 1, i, k), u01 = UBD(j, i + 1, k), u11 = UBD(j + 1, i + 1, k);
-  const double v00 = VBD(j, i, k), v10 = VBD(j + 1, i, k), v01 = VBD(j, i + 1, k), v11 = VBD(j + 1, i + 1, k);
-  const double dudx = u10 + u11 - u00 - u01;
-  const double dvdx = v10 + v11 - v00 - v01;
-  const double dudy = u01 + u11 - u00 - u10;
-  const double dvdy = v01 + v11 - v00 - v10;
-  const double rpb = F2(f.rpsb, j, i);
-  const double dwdz = F3(f.a2w, j, i, k) * rpb - F3(f.a2w, j, i, k + 1) * rpb;
-  const double duv = sqrt(dmax((dudx - dvdy) * (dudx - dvdy) + (dvdx + dudy) * (dvdx + dudy) - dwdz * dwdz, d_zero));
-  F3(f.xkcr, j, i, k) = dmin(F2(f.hgfact, j, i) + c->dydc * duv, c->xkhmax);
-}
-#endif
 #endif
 
 // ... then scaled by rdxsq and p* (b) by their readers: xkc, xkcf (cross interior, full
@@ -496,12 +429,6 @@ constexpr int TC_NF = 5;
 #ifndef TC_W
 #define TC_W 1      // 6 or 8 waves/SIMD measured slower (4.73, 5.35 ms against 3.82)
 #endif
-#ifndef TC_UV
-#define TC_UV 1
-#endif
-#ifndef TD_X
-#define TD_X 1
-#endif
 // relaxation and physics-tendency terms of k_nh_tend_c and k_nh_tend_d (#undef after k_nh_tend_d)
 #define FG(b0, bt, a, J, I) ((F3(b0, J, I, k) + xt * F3(bt, J, I, k)) - F3(a, J, I, k))
 #define RELAX5(x, b0, bt, a) \
@@ -522,8 +449,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   const int kz = c->kz;
   const double xt = s->xbctime + s->dt;
   const bool inframe = j < g.j0 + g.nj && i < g.i0 + g.ni;
-#if TC_UV
-  // TC_UV: atm1 u, v of levels k and k - 1 at the block's (32 + 1) x (8 + 1) dot points, staged
+  // atm1 u, v of levels k and k - 1 at the block's (32 + 1) x (8 + 1) dot points, staged
   // too: the four-point wind averages of start_advect and the adiabatic term read them at every
   // cross point of the block (the same values, so the same bits)
   __shared__ double sU[2][TCI + 1][TCJ + 1], sV[2][TCI + 1][TCJ + 1];
@@ -553,10 +479,6 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   }
 #define A1U(dj, di, kk) sU[(kk) == k ? 0 : 1][(int)threadIdx.y + (di)][(int)threadIdx.x + (dj)]
 #define A1V(dj, di, kk) sV[(kk) == k ? 0 : 1][(int)threadIdx.y + (di)][(int)threadIdx.x + (dj)]
-#else
-#define A1U(dj, di, kk) F3(f.a1u, j + (dj), i + (di), kk)
-#define A1V(dj, di, kk) F3(f.a1v, j + (dj), i + (di), kk)
-#endif
   {
     const int J0 = g.j0 + TBX * TCJ - 2, I0 = g.i0 + TBY * TCI - 2;
     const int tid = threadIdx.y * blockDim.x + threadIdx.x;
@@ -680,8 +602,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
                            (c->dsigma[k - 1] * F3(f.rho1, j, i, k) + c->dsigma[k] * F3(f.rho1, j, i, k - 1));
       const double uaq = d_rfour * (c->twt1[k] * uk + c->twt2[k] * um);
       const double vaq = d_rfour * (c->twt1[k] * vk + c->twt2[k] * vm);
-#if NH_XPRFORM
-      // decouple's atmx%pr (:1040-1048) at k and k-1, formed here as decouple formed it
+      // decouple's atmx%pr (:1040-1048) at k and k-1, formed here from the operands loaded
       auto xprat = [&](int kk) {
         const double xt = F3(f.a1t, j, i, kk) * r0;
         const double xqv = dmax(F3(f.a1qv, j, i, kk) * r0, MINQQ);
@@ -690,9 +611,6 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
         return (xtv - F3(f.t0, j, i, kk) - xpp / (c->cpd * F3(f.rho0, j, i, kk))) / xt;
       };
       const double xprm = xprat(k - 1), xprk = xprat(k);
-#else
-      const double xprm = F3(f.xpr, j, i, k - 1), xprk = F3(f.xpr, j, i, k);
-#endif
       wd = wd +
           (c->twt2[k] * xprm + c->twt1[k] * xprk) * rofac * EGRAV_NH * ps +
           ex * (uaq * crx - vaq * cry) + (uaq * uaq + vaq * vaq) * REARTHRAD * rps +
@@ -795,9 +713,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     F3(f.cqv, j, i, k) = cq;
     if (f.tfuse && !(cq < d_zero))      // a negative forecast: filtered after its fix
       nh_raw_qv(c, F3(f.a1qv, j, i, k), o2, cq, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
-#if NH_NEGLIST
     if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2);
-#endif
   }
   // ================= qc: hadvqx (or the semi-Lagrangian start), vadv4d ind = 1, adiabatic,
   // diffusion, forecast
@@ -825,9 +741,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     F3(f.cqc, j, i, k) = cq;
     if (f.tfuse && !(cq < d_zero))
       nh_raw_qc(c, F3(f.a1qc, j, i, k), o2, cq, F3(f.b1qc, j, i, k), F3(f.b2qc, j, i, k));
-#if NH_NEGLIST
     if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2 + 1);
-#endif
   }
 }
 
@@ -849,8 +763,7 @@ __global__ __launch_bounds__(TDT) void k_nh_tend_d(Geom g, const Consts* __restr
   __shared__ double sUA[TDH][TDW], sVA[TDH][TDW], sU[TDH][TDW], sV[TDH][TDW], sCR[TDH][TDW];
   __shared__ double sBU[TDH][TDW], sBV[TDH][TDW];
   const int j = g.jdi1 + TBX * 64 + (int)threadIdx.x, i = g.idi1 + TBY * TD_I + (int)threadIdx.y, k = TBZ + 1;
-#if TD_X
-  // TD_X: the cross fields a dot point averages over its four cross points -- qdot at k and
+  // the cross fields a dot point averages over its four cross points -- qdot at k and
   // k + 1 (vadvuv), atm1 w at k and k + 1 (the curvature terms) and xkcr at k (calc_coeff's xkd)
   // -- at the block's 65 x (TD_I + 1) cross points (j - 1 .. j + 63, i - 1 .. i + TD_I - 1)
   __shared__ double sQD[2][TD_I + 1][65], sWD[2][TD_I + 1][65], sXK[TD_I + 1][65];
@@ -882,11 +795,6 @@ __global__ __launch_bounds__(TDT) void k_nh_tend_d(Geom g, const Consts* __restr
 #define QDC(dj, di, kk) sQD[(kk) == k ? 0 : 1][(int)threadIdx.y + 1 + (di)][(int)threadIdx.x + 1 + (dj)]
 #define WDC(dj, di, kk) sWD[(kk) == k ? 0 : 1][(int)threadIdx.y + 1 + (di)][(int)threadIdx.x + 1 + (dj)]
 #define XKC(dj, di) sXK[(int)threadIdx.y + 1 + (di)][(int)threadIdx.x + 1 + (dj)]
-#else
-#define QDC(dj, di, kk) F3(f.qdot, j + (dj), i + (di), kk)
-#define WDC(dj, di, kk) F3(f.a1w, j + (dj), i + (di), kk)
-#define XKC(dj, di) F3(f.xkcr, j + (dj), i + (di), k)
-#endif
   {
     const int J0 = g.jdi1 + TBX * 64 - 2, I0 = g.idi1 + TBY * TD_I - 2;
     const int tid = threadIdx.y * 64 + threadIdx.x;
@@ -899,16 +807,11 @@ __global__ __launch_bounds__(TDT) void k_nh_tend_d(Geom g, const Consts* __restr
       ok[n] = q < TDW * TDH && jg >= g.j0 && jg < g.j0 + g.nj && ig >= g.i0 && ig < g.i0 + g.ni;
       const int jr = ok[n] ? jg : j0c(g), ir = ok[n] ? ig : i0c(g);
       const double m = F2(f.msfd, jr, ir);
-#if NH_UDFORM
-      // ud, vd formed from the atm1 winds loaded for umc, vmc (decouple no longer stores them)
+      // ud, vd formed from the atm1 winds loaded for umc, vmc (decouple does not store them)
       const double au = F3(f.a1u, jr, ir, k), av = F3(f.a1v, jr, ir, k);
       va[n][0] = au * m; va[n][1] = av * m;                                     // umc, vmc
       const double2 d = udvd_nh_ld(g, c->iboudy, f, au, av, F2(f.rpsda, jr, ir), jr, ir, k);
       va[n][2] = d.x; va[n][3] = d.y; va[n][4] = F3(f.cr, jr, ir, k);
-#else
-      va[n][0] = F3(f.a1u, jr, ir, k) * m; va[n][1] = F3(f.a1v, jr, ir, k) * m;   // umc, vmc
-      va[n][2] = F3(f.ud, jr, ir, k); va[n][3] = F3(f.vd, jr, ir, k); va[n][4] = F3(f.cr, jr, ir, k);
-#endif
       va[n][5] = UBD(jr, ir, k); va[n][6] = VBD(jr, ir, k);
       va[n][5] = va[n][5] / m; va[n][6] = va[n][6] / m;     // UM of diffu_d, Main/mod_diffusion.F90:281-411
     }
@@ -1088,9 +991,8 @@ __device__ __forceinline__ void nh_negfix_at(const Geom& g, const Consts* c, con
     if (f.tfuse) nh_filter_q_to(g, c, f, n, j, i, k, v);
   }
 }
-#if NH_NEGLIST
-// NH_NEGLIST: the entries k_nh_tend_c listed, grid-stride (the list is unordered; every entry is
-// an independent point, as in the point form below)
+// the entries k_nh_tend_c listed, grid-stride (the list is unordered; every entry is an
+// independent point)
 __global__ void k_nh_negfix(Geom g, const Consts* __restrict__ c, NHFields f) {
   const int cnt = *f.negcnt;
   for (int e = (int)(blockIdx.x * blockDim.x + threadIdx.x); e < cnt; e += (int)(gridDim.x * blockDim.x)) {
@@ -1103,14 +1005,6 @@ __global__ void k_nh_negfix(Geom g, const Consts* __restrict__ c, NHFields f) {
     nh_negfix_at(g, c, f, n, j, i, k);
   }
 }
-#else
-__global__ void k_nh_negfix(Geom g, const Consts* __restrict__ c, NHFields f) {
-  WRAP_POINT(g.jci1, g.jci2, g.ici1);
-  if (!IN_CI(j, i)) return;
-  for (int n = 0; n < 2; n++)
-    if (F3(n ? f.cqc : f.cqv, j, i, k) < d_zero) nh_negfix_at(g, c, f, n, j, i, k);
-}
-#endif
 
 // one 64-lane block per (n, k) plane: the marked rows swept in the reference order
 // (negfix_sweep, qxcommon.hpp; dynamic LDS negfix_lds(g))
@@ -1217,7 +1111,7 @@ __global__ void k_nh_a1_col(Geom g, const Consts* __restrict__ c, NHFields f) {
   F3(f.cw, j, i, kz + 1) = F3(f.a2w, j, i, kz + 1) * rpb;
 }
 
-// NH_DPRFORM: the acoustic u, v update forms dprddx / dprddy from atm0%pr; a host that puts
+// the acoustic u, v update forms dprddx / dprddy from atm0%pr; a host that puts
 // them is checked once, after the put, to hold exactly those sums (Main/mod_params.F90:2676-2686)
 // on the interior dot points the update reads (bad[0]: count of differing values)
 __global__ void k_nh_check_dprd(Geom g, NHFields f, int* bad) {
@@ -1253,15 +1147,11 @@ __device__ __forceinline__ void nh_sound_uv_at(const Geom& g, const Consts* __re
                                    F3(f.cdt, j - 1, i - 1, k));
   const double chh = d_half * dts / (rho * c->dx) / F2(f.msfd, j, i);
   const double* pp = f.cpp;
-#if NH_DPRFORM
   // atm0%dprddx / dprddy (Main/mod_params.F90:2678-2681), formed from atm0%pr as the reference
   // forms them once: the same four-point sums in the same order, so the same bits
   const double* pr = f.pr0;
   const double p00 = F3(pr, j, i, k), pm0 = F3(pr, j - 1, i, k), p0m = F3(pr, j, i - 1, k), pmm = F3(pr, j - 1, i - 1, k);
   const double dprx = p00 - pm0 + p0m - pmm, dpry = p00 - p0m + pm0 - pmm;
-#else
-  const double dprx = F3(f.dprddx, j, i, k), dpry = F3(f.dprddy, j, i, k);
-#endif
   double u = (first ? init_u(j, i) : F3(f.cu, j, i, k)) - chh * (F3(pp, j, i, k) - F3(pp, j - 1, i, k) + F3(pp, j, i - 1, k) -
                                         F3(pp, j - 1, i - 1, k) - dprx * dppdp0);
   double v = (first ? init_v(j, i) : F3(f.cv, j, i, k)) - chh * (F3(pp, j, i, k) - F3(pp, j, i - 1, k) + F3(pp, j - 1, i, k) -
@@ -1300,11 +1190,7 @@ __global__ void k_nh_sound_uv(Geom g, const Consts* __restrict__ c, const StepSt
     nh_sound_uv_at(g, c, s, f, istep, fin, first, j, i, k);
     return;
   }
-#if NH_WRAP_PT
   WRAP_POINT(g.jde1, g.jde2, g.ide1);
-#else
-  NH_SOUND_POINT(NH_ALIGN ? ALIGN_J(g.jde1) : g.jde1, g.ide1);
-#endif
   if (part == 1 && nh_uv_strip(g, j, i)) return;
   nh_sound_uv_at(g, c, s, f, istep, fin, first, j, i, k);
 }
@@ -1372,12 +1258,8 @@ __device__ __forceinline__ NhB1 nh_sound_b1_at(const Geom& g, const Consts* c, c
 __global__ __launch_bounds__(256, NHBC_W) void k_nh_sound_bc(Geom g, const Consts* __restrict__ c,
                                                              const StepState* __restrict__ s, NHFields f,
                                                              int istep, int it) {
-#if NH_WRAP
   const int j = wrap_j(g, g.jci1, g.jci2 - g.jci1 + 1, (int)blockIdx.x, (int)threadIdx.x);
   const int i = g.ici1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-#else
-  NH_SOUND_POINT(NH_ALIGN ? ALIGN_J(g.jci1) : g.jci1, g.ici1);
-#endif
   if (!IN_CI(j, i)) return;
   const int kz = c->kz;
   const double dts = s->dt / (double)istep;
@@ -1400,9 +1282,6 @@ __global__ __launch_bounds__(256, NHBC_W) void k_nh_sound_bc(Geom g, const Const
   double rho1k = F3(f.rho1, j, i, kz);
   double wk1 = F3(w, j, i, kz + 1), wk = F3(w, j, i, kz);
   double pnew = d_zero;
-#if defined(NHBC_UNROLL) && NHBC_UNROLL == 2    // measured: no change at C5
-#pragma unroll 2
-#endif
   for (int k = kz; k >= 1; k--) {
     // rings: qb/pcb at k, qa/pca at k-1
     const double wkm = (k >= 2) ? F3(w, j, i, k - 1) : d_zero;
@@ -1553,20 +1432,12 @@ __global__ NHCD_LB void k_nh_sound_cd(Geom g, Geom ge, const double* __restrict_
   __shared__ double sM[169];
   __shared__ unsigned long long sred[4];
   const int ilo = 2, ihi = g.nicross() - 1, jlo = 2, jhi = g.njcross() - 1;   // icross1+1 .. icross2-1
-#if NH_XCD
-  const Blk3 xb = xcd_block();
-#else
   const Blk3 xb = {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
-#endif
-#if NH_WRAP
   // block column 0's lanes below jci1 take the row's tail columns (wrap_j): their 13 x 13
   // neighbourhoods come from a second staged tile, sT2, at the tail
   const int nci = g.jci2 - g.jci1 + 1, ja = g.jci1 - jalign(g, g.jci1);
   const int J0 = ja + xb.x * 64, JT = ja + ((nci + 63) / 64) * 64;
   __shared__ double sT2[4 + 12][16 + 12];
-#else
-  const int J0 = (NH_ALIGN_CD ? ALIGN_J(g.jci1) : g.jci1) + xb.x * 64;
-#endif
   const int I0 = g.ici1 + xb.y * 4;
   const int tid = threadIdx.y * 64 + threadIdx.x;
   const bool upr = c->ifupr == 1;
@@ -1578,7 +1449,6 @@ __global__ NHCD_LB void k_nh_sound_cd(Geom g, Geom ge, const double* __restrict_
       in_ = (in_ < ilo) ? ilo : (in_ > ihi ? ihi : in_);
       sE[ii][jj] = est[ge.ix(jn, in_)];
     }
-#if NH_WRAP
     if (xb.x == 0 && J0 < g.jci1)
       for (int q = tid; q < 16 * 28; q += 256) {
         const int jj = q % 28, ii = q / 28;
@@ -1588,20 +1458,13 @@ __global__ NHCD_LB void k_nh_sound_cd(Geom g, Geom ge, const double* __restrict_
         in_ = (in_ < ilo) ? ilo : (in_ > ihi ? ihi : in_);
         sT2[ii][jj] = est[ge.ix(jn, in_)];
       }
-#endif
     if (tid < 169) sM[tid] = f.tmask[tid];
     __syncthreads();
   }
-#if NH_WRAP
   const bool tail = J0 + (int)threadIdx.x < g.jci1;
   const int j = tail ? JT + (J0 + (int)threadIdx.x - ja) : J0 + (int)threadIdx.x, i = I0 + (int)threadIdx.y;
   const double* tE = tail ? &sT2[0][0] : &sE[0][0];
   const int tW = tail ? 28 : 76, tJ = tail ? JT : J0;
-#else
-  const int j = J0 + (int)threadIdx.x, i = I0 + (int)threadIdx.y;
-  const double* tE = &sE[0][0];
-  const int tW = 76, tJ = J0;
-#endif
   const bool active = IN_CI(j, i);
   unsigned long long cfl = 0ull;                       // bits of the column's CFL maximum
   if (active) {
@@ -1641,12 +1504,7 @@ __global__ NHCD_LB void k_nh_sound_cd(Geom g, Geom ge, const double* __restrict_
     double wm = wpval;
     double cum = d_zero, cvm = d_zero;          // crs(cu/cv, k-1)
     double pam = d_zero, pamm = d_zero, prm = d_zero, prmm = d_zero;   // next part A: pp, pr0 at k-1, k-2
-#ifndef NHCD_UNROLL
-#define NHCD_UNROLL 2      // two levels per iteration: 910 -> 861 us at C5 (A/B)
-#endif
-#if NHCD_UNROLL == 2
-#pragma unroll 2
-#endif
+#pragma unroll 2      // two levels per iteration: 910 -> 861 us at C5 (A/B)
     for (int k = 1; k <= kz; k++) {
       const double wp = F3(f.se, j, i, k) * wm + F3(f.sf, j, i, k);
       wfilt(k + 1, wp);

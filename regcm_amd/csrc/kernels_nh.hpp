@@ -23,7 +23,11 @@ struct NHFields {
   // 2-D reciprocals (k_surface_pressures)
   const double *rpsa, *rpsb, *rpsda, *rpsdb, *psdota, *psdotb;
   // decoupled / derived fields of the step
-  double *ud, *vd, *pr1, *rho1, *xpr;
+  double *pr1, *rho1;
+  // unread and null (k_nh_tend_c forms atmx%pr itself): the slot stays because an 8-byte shift
+  // of the members after it regroups k_nh_tend_c's kernel-argument loads and changes its
+  // schedule (5 771 -> 5 996 instructions); remove it with the next change to that kernel
+  double *xpr;
   double *th;                    // potential temperature atmx%t*(p00/atm1%pr)**rovcp (ithadv = 1)
   double *cr, *qdot;
   double *xkcr;
@@ -56,14 +60,12 @@ struct NHFields {
   // in k_nh_tfilter_a1
   double *b1t, *b1qv, *b1qc, *b2t, *b2qv, *b2qc;
   int tfuse;
-  // NH_NEGLIST: k_nh_tend_c lists its negative qv/qc forecasts (entry (k-1)*plane + ix, times 2,
+  // k_nh_tend_c lists its negative qv/qc forecasts (entry (k-1)*plane + ix, times 2,
   // plus the species bit) for k_nh_negfix, which visits the list instead of every point
   unsigned* neglist;
   int* negcnt;
 };
 constexpr int NH_CFL_SLOTS = 1024;
-// block order of the NH tendency kernels: NH_ZFIRST = 1 launches them as (levels, tiles_j,
-// tiles_i) grids, consecutive blocks on consecutive levels of one tile
 // k_nh_tend_c block: TC_J x TC_I cross points of one level
 #ifndef TC_J
 #define TC_J 32
@@ -74,68 +76,6 @@ constexpr int NH_CFL_SLOTS = 1024;
 // rows of dot points per k_nh_tend_d block (64 x TD_I threads)
 #ifndef TD_I
 #define TD_I 8
-#endif
-#ifndef NH_ZFIRST
-#define NH_ZFIRST 1
-#endif
-// acoustic kernels: thread columns aligned to the frame's 128-B lines (ALIGN_J, devcommon.hpp).
-// C5, alternating on one box (profiles/r05/c5_nh_align_ab.log): k_nh_sound_bc 762 -> 747 us;
-// k_nh_sound_uv unchanged; k_nh_sound_cd 905-953 -> 981-1019 us (its 13th block column of
-// mostly idle lanes lengthens a latency-bound column walk), so cd keeps the unaligned map
-#ifndef NH_ALIGN
-#define NH_ALIGN 1
-#endif
-#ifndef NH_ALIGN_CD
-#define NH_ALIGN_CD 0
-#endif
-// NH_WRAP: the column kernels k_nh_sound_bc / k_nh_sound_cd on line-aligned block columns
-// without the extra column of waves ALIGN_J adds (wrap_j): the lanes of block column 0 that
-// fall below jci1 take the row's last columns instead, so a row of 768 columns is 12 waves,
-// 11 of them on whole 128-B lines (was 12 misaligned, or 13 aligned)
-#ifndef NH_WRAP
-#define NH_WRAP 1
-#endif
-// the same line-aligned columns for the NH point and column kernels that start at jce1, jci1 or
-// jde1 (k_nh_sound_uv, k_nh_omega, k_nh_coeff_raw, k_nh_a1_col, k_nh_negfix)
-#ifndef NH_WRAP_PT
-#define NH_WRAP_PT 1
-#endif
-#ifndef NH_NEGLIST
-#define NH_NEGLIST 1
-#endif
-// k_nh_tend_c forms decouple's buoyancy helper atmx%pr (xpr) at k and k-1 from the operands it
-// loads (decouple stops storing it, and reading t0, rho0 for it)
-#ifndef NH_XPRFORM
-#define NH_XPRFORM 1
-#endif
-// acoustic kernels: XCD-aware block placement (xcd_block, devcommon.hpp).  C5, alternating on
-// one box (profiles/r05/rejected/c5_xcd_ab.log): k_nh_sound_bc unchanged, k_nh_sound_cd
-// 884-894 -> 852-882 us, k_nh_sound_uv 519-521 -> 532-542 us, the step unchanged: off
-#ifndef NH_XCD
-#define NH_XCD 0
-#endif
-#if NH_XCD
-#define NH_SOUND_POINT(j1, i1) THREAD_POINT_XCD(j1, i1)
-#else
-#define NH_SOUND_POINT(j1, i1) THREAD_POINT(j1, i1)
-#endif
-// k_nh_sound_uv forms atm0%dprddx / dprddy from atm0%pr where it reads them
-// (Main/mod_params.F90:2676-2686: four-point sums, no rounding beyond the reference's)
-#ifndef NH_DPRFORM
-#define NH_DPRFORM 1
-#endif
-// decouple's ud, vd (atm1 u, v * 1/p*dot with the iboudy = 3/4 inflow/outflow rule) formed by
-// their readers, k_nh_omega and k_nh_tend_d's staging, from the atm1 winds they load anyway
-#ifndef NH_UDFORM
-#define NH_UDFORM 1
-#endif
-// part A of acoustic sub-step 1 (tfuse) and calc_coeff's xkcr as column walks (one thread per
-// column, k carried in registers) instead of one thread per point and level
-#ifndef NH_A1COL
-#define NH_A1COL 1
-#endif
-#ifndef NH_XKCOL
-#define NH_XKCOL 1
 #endif
 
 struct QxArgs;

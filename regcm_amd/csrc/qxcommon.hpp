@@ -168,100 +168,25 @@ __device__ __forceinline__ void lds_barrier() {
 // Dense planes (many marked rows): the sweep as a skewed wavefront.  Point (j, i) depends only
 // on its sweep-predecessors (j-1, i) and (j-1..j+1, i-1), so with one thread per row and row i
 // two steps behind row i-1 (step t = j - jci1 + 2 (i - ici1)) every dependency was resolved one
-// or more steps earlier: W + 2 (R - 1) steps, one LDS barrier each, for the whole plane.  Each
-// thread keeps the fixed value of its own previous point in a register and publishes its
-// fixed values in a 4-slot LDS ring per row (ring: 4 R doubles) for the row below; it streams
-// its 3 x 3 window of the original forecasts and the post inputs A::load of its row through a
-// register queue loaded P steps ahead, so no step waits on memory.  Every negative point of
-// the plane is evaluated (an independent one gives the parallel pass's value again); only the
-// dependent ones are stored and post-processed (A::apply).  Needs R <= the block's threads.
-template <class A>
-__device__ void negfix_dense(const Geom& g, const double* sv, double* fx, int k, double* ring, const A& acc) {
-  constexpr int P = 4, NQ = 3 + A::NI;
-  const int r = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
-  const int R = g.ici2 - g.ici1 + 1, W = g.jci2 - g.jci1 + 1, S = W + 2 * (R - 1);
-  const bool act = r < R;
-  const int i = g.ici1 + r;
-  auto qload = [&](int jc, double* q) {
-    const bool ok = act && jc >= g.jci1 - 1 && jc <= g.jci2 + 1;
-#pragma unroll
-    for (int d = 0; d < 3; d++) q[d] = ok ? F3(sv, jc, i - 1 + d, k) : 0.0;
-    if (act && in(jc, g.jci1, g.jci2)) acc.load(jc, i, q + 3);
-    else
-#pragma unroll
-      for (int d = 3; d < NQ; d++) q[d] = 0.0;
-  };
-  int j = g.jci1 - 2 * r;                    // this row's column at step 0
-  double w0[NQ], w1[NQ], w2[NQ], qa[P][NQ], qb[P][NQ];
-  qload(j - 1, w0);
-  qload(j, w1);
-  qload(j + 1, w2);
-#pragma unroll
-  for (int u = 0; u < P; u++) qload(j + 2 + u, qa[u]);
-  double prev = 0.0;                         // the fixed value of (j - 1, i)
-  const bool up = r >= 1;                    // row i - 1 is interior
-  for (int t0 = 0; t0 < S; t0 += P) {
-#pragma unroll
-    for (int u = 0; u < P; u++) qload(j + 2 + P + u, qb[u]);
-#pragma unroll
-    for (int u = 0; u < P; u++) {
-      const int jj = j + u;
-      if (act && t0 + u < S && in(jj, g.jci1, g.jci2) && w1[1] < d_zero) {
-        const bool p0 = up && jj - 1 >= g.jci1 && w0[0] < d_zero, p1 = up && w1[0] < d_zero;
-        const bool p2 = up && jj + 1 <= g.jci2 && w2[0] < d_zero, p3 = jj - 1 >= g.jci1 && w0[1] < d_zero;
-        const double* rp = ring + 4 * (r - 1);
-        double sum = 0.0;
-        sum = sum + fabs(p0 ? rp[(jj - 1) & 3] : w0[0]);
-        sum = sum + fabs(p1 ? rp[jj & 3] : w1[0]);
-        sum = sum + fabs(p2 ? rp[(jj + 1) & 3] : w2[0]);
-        sum = sum + fabs(p3 ? prev : w0[1]);
-        sum = sum + fabs(w1[1]);
-        sum = sum + fabs(w2[1]);
-        sum = sum + fabs(w0[2]);
-        sum = sum + fabs(w1[2]);
-        sum = sum + fabs(w2[2]);
-        // / 9 as div_by (fastmath.hpp: the division's bits from the rounded reciprocal in three
-        // dependent operations; the step's critical path runs through it), for normal operands
-        const double xs = 0.01 * sum;
-        const double v = xs >= 0x1p-960 ? div_by(xs, 9.0, 1.0 / 9.0) : xs / 9.0;
-        ring[4 * r + (jj & 3)] = v;
-        prev = v;
-        if (p0 || p1 || p2 || p3) {
-          F3(fx, jj, i, k) = v;
-          acc.apply(jj, i, v, w1 + 3);
-        }
-      }
-      lds_barrier();
-#pragma unroll
-      for (int d = 0; d < NQ; d++) { w0[d] = w1[d]; w1[d] = w2[d]; w2[d] = qa[u][d]; }
-    }
-#pragma unroll
-    for (int u = 0; u < P; u++)
-#pragma unroll
-      for (int d = 0; d < NQ; d++) qa[u][d] = qb[u][d];
-    j += P;
-  }
-}
-
-// The same wavefront with the row-to-row hand-over in registers (NEGFIX_DPP): lane l of a
-// wavefront holds row r = 64 w + l, and the value row r - 1 fixed in the previous step moves to
-// lane l with one cross-lane shift (DPP wave_shr:1, or __shfl_up with NEGFIX_DPP = 2) instead of
-// an LDS ring behind a block barrier every step.  Each lane keeps the three values of the row
-// above that its window reads (columns jj - 1, jj, jj + 1) in registers.  Lane 0 of wavefront w > 0
-// takes row 64 w - 1's values from an LDS ring written by lane 63 of wavefront w - 1, which runs
-// SK steps ahead (wavefront w's rows start SK steps later than the two-per-row skew gives), so one
-// block barrier every SK steps makes those writes visible: W + 2 (R - 1) + SK (nw - 1) steps.
-// Every value is the same expression on the same operands as negfix_dense's, bit for bit.
-#ifndef NEGFIX_DPP
-#define NEGFIX_DPP 1
-#endif
+// or more steps earlier.  Lane l of a wavefront holds row r = 64 w + l; each thread keeps the
+// fixed value of its own previous point in a register, and the value row r - 1 fixed in the
+// previous step moves to lane l with one cross-lane shift (lane_shr1).  Each lane keeps the three
+// values of the row above that its window reads (columns jj - 1, jj, jj + 1) in registers.  Lane 0
+// of wavefront w > 0 takes row 64 w - 1's values from an LDS ring written by lane 63 of wavefront
+// w - 1, which runs SK steps ahead (wavefront w's rows start SK steps later than the two-per-row
+// skew gives), so one block barrier every SK steps makes those writes visible: W + 2 (R - 1) +
+// SK (nw - 1) steps for the whole plane.  A thread streams its 3 x 3 window of the original
+// forecasts and the post inputs A::load of its row through a register queue loaded P steps ahead,
+// so no step waits on memory.  Every negative point of the plane is evaluated (an independent one
+// gives the parallel pass's value again); only the dependent ones are stored and post-processed
+// (A::apply).  Needs R <= the block's threads.
 __device__ __forceinline__ double lane_shr1(double x) {      // lane l gets lane l - 1's x
-#if NEGFIX_DPP == 2
-  return __shfl_up(x, 1, 64);
-#else
+#if defined(__GFX9__)      // the DPP wave_shr control exists on the GFX9 / CDNA family only
   const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xf, 0xf, false);   // wave_shr:1
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x138, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
+#else
+  return __shfl_up(x, 1, 64);
 #endif
 }
 template <class A>
@@ -317,6 +242,8 @@ __device__ void negfix_dense_dpp(const Geom& g, const double* sv, double* fx, in
         sum = sum + fabs(w0[2]);
         sum = sum + fabs(w1[2]);
         sum = sum + fabs(w2[2]);
+        // / 9 as div_by (fastmath.hpp: the division's bits from the rounded reciprocal in three
+        // dependent operations; the step's critical path runs through it), for normal operands
         const double xs = 0.01 * sum;
         const double v = xs >= 0x1p-960 ? div_by(xs, 9.0, 1.0 / 9.0) : xs / 9.0;
         pub = v;
@@ -338,8 +265,8 @@ __device__ void negfix_dense_dpp(const Geom& g, const double* sv, double* fx, in
   }
 }
 
-// NEGFIX_POST (kernels.hpp): the serial pass resolves the chain only (the fixed values into fx)
-// and a parallel launch afterwards (k_negfix_post, k_qx_post) applies the filters of the
+// k_negfix_serial(_qx) and k_qx_serial resolve the chain only (the fixed values into fx) and
+// a parallel launch afterwards (k_negfix_post, k_qx_post) applies the filters of the
 // dependent points, so the wavefront's steps carry the forecasts alone: every load of the
 // row-per-lane wavefront touches 64 lines, and the filters' inputs were 5 (qv/qc) or 2 (species)
 // more such loads per step (C3, nqx = 5: k_negfix_serial 365 -> 175 us, k_qx_serial 295 -> 220)
@@ -369,8 +296,7 @@ __device__ void negfix_resolve(const Geom& g, const double* sv, double* fx, unsi
   const int T = (int)(blockDim.x * blockDim.y * blockDim.z);
   const int tid = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
   if (mode == 0 && nm > NEGFIX_SPARSE && R <= T && 4 * R <= ldsn) {
-    if (NEGFIX_DPP) negfix_dense_dpp(g, sv, fx, k, lds, acc);
-    else negfix_dense(g, sv, fx, k, lds, acc);
+    negfix_dense_dpp(g, sv, fx, k, lds, acc);
     __syncthreads();                           // every wave read the bitmap before it is cleared
     for (int w = tid; w < nw; w += T) words[w] = 0;
     return;

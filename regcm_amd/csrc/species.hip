@@ -332,22 +332,13 @@ __device__ __forceinline__ void qx_serial_plane(const Geom& g, const Consts* __r
     }
     __syncthreads();
   }
-  if (NEGFIX_POST) {
-    negfix_resolve(g, q.cq[n], q.fq[n], q.dep, plane, k, lds, negfix_lds(g), NoPost{}, [](int, int, double) {}, c->negfix_mode);
-    return;
-  }
-  const QxRaw acc{g, q.a1[n], q.a2[n], q.b1[n], q.b2[n], c->gnu2, k};
-  negfix_resolve(g, q.cq[n], q.fq[n], q.dep, plane, k, lds, negfix_lds(g), acc, [&](int jj, int i, double v) {
-    double x[2];
-    acc.load(jj, i, x);
-    acc.apply(jj, i, v, x);
-  }, c->negfix_mode);
+  negfix_resolve(g, q.cq[n], q.fq[n], q.dep, plane, k, lds, negfix_lds(g), NoPost{}, [](int, int, double) {}, c->negfix_mode);
 }
 __global__ __launch_bounds__(512) void k_qx_serial(Geom g, const Consts* __restrict__ c, QxArgs q) {
   extern __shared__ double lds[];
   qx_serial_plane(g, c, q, (int)blockIdx.x, lds);
 }
-// NEGFIX_POST, hydrostatic qfuse: the serial chains of the qv / qc planes (blocks [0, 2 kz), as
+// hydrostatic qfuse: the serial chains of the qv / qc planes (blocks [0, 2 kz), as
 // k_negfix_serial) and of the species planes (k_qx_serial) in one launch after the split
 // corrections: the two sets of planes are independent, so the launch takes the longer chain's
 // time instead of the sum (k_qx_fix's flags wait for it; nothing of the split reads the species)
@@ -367,7 +358,7 @@ __global__ __launch_bounds__(512) void k_negfix_serial_qx(Geom g, const Consts* 
                  [](int, int, double) {}, c->negfix_mode);
 }
 
-// NEGFIX_POST: filter_raw_4d of the points k_qx_serial fixed, a thread per interior point of a
+// filter_raw_4d of the points k_qx_serial fixed, a thread per interior point of a
 // (species, level) plane (z = plane)
 __global__ void k_qx_post(Geom g, const Consts* __restrict__ c, QxArgs q) {
   const int j = g.jci1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);

@@ -2,7 +2,7 @@
 # A/B of engine variant libraries (varlib/var_<name>.so, tools/variant_build.sh output moved
 # there so it travels with gpurun) on the GPU box: hydrostatic parity tests on each variant,
 # then the C3 step with per-kernel times, the default engine first.
-#   VARS="pf1w4 pf0w4" bash tools/km_ab.sh
+#   CHECK="colw32" VARS="head colw32 head colw32" bash tools/km_ab.sh   (variant names as given to variant_build.sh)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=${OUT:-bench_out}   # logs and result lines of this script

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds an experimental engine variant: tools/variant_build.sh <name> <hipcc flags...>
 # into varlib/var_<name>.so (select it with RCMDYN_LIB=varlib/var_<name>.so, e.g. in
-# tools/ab_bench.sh or bench.py).  The sources are copied to a scratch tree first so the
+# tools/variant_ab.sh or bench.py).  The sources are copied to a temporary tree first so the
 # in-tree objects are untouched.
 set -eu
 cd "$(dirname "$0")/.."
