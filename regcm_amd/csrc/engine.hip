@@ -243,6 +243,68 @@ enum class FK {
 };
 inline FK fkq(FK base, int n) { return (FK)((int)base + n); }
 
+// The run-time switches, read from the environment by read() alone, once per engine
+// at the start of create(): engines built under different environments in one process keep their own.
+struct Switches {
+  // steps per replayed graph in rcmdyn_step (RCMDYN_GRAPH_STEPS, 1 or 2): two steps per launch
+  // return to the same ping-pong parity and halve the graph launches
+  int graph_steps = 2;
+  // RCMDYN_NO_GRAPH=1 runs rcmdyn_step eagerly (the path of RCCL-decomposed runs), for timing
+  bool no_graph = false;
+  // k_momentum and k_scalars as one launch (k_update); RCMDYN_NO_FUSE_UPDATE=1: two launches
+  bool fuse_update = true;
+  // NH: tend's time filters of t, qv, qc in k_nh_tend_c and the negative-moisture fix, into
+  // the other parity (Tile::tq); RCMDYN_NH_NO_TFUSE=1: in place in k_nh_tfilter_a1
+  bool nh_tfuse = true;
+  // rcmdyn_step's hydrostatic bdyval runs inside k_split_correct_bdy (RCMDYN_NO_FUSE_BDY: two
+  // launches of its own, as after rcmdyn_tend)
+  bool no_fuse_bdy = false;
+  // the drop-in pair (rcmdyn_tend, then rcmdyn_bdyval): tend leaves its split corrections
+  // pending and bdyval launches them with its boundary lines (k_split_correct_bdy, the form of
+  // rcmdyn_step); any other call in between launches them alone first (settle).
+  // RCMDYN_NO_DEFER_CORR=1: tend launches them itself.
+  bool no_defer_corr = false;
+  // lazy tend (drop-in pair): rcmdyn_tend does the host bookkeeping and leaves the launch to
+  // the next call: rcmdyn_bdyval replays the one-step graph of tend + bdyval (rcmdyn_step's),
+  // any other call (settle) replays tend's own graph first.  RCMDYN_NO_LAZY_TEND=1: off
+  bool lazy_tend = true;
+  // the hydrostatic step without k_qfilter (its work in k_columns, k_scalars and the extra
+  // blocks of k_split_project / k_split_correct); RCMDYN_NO_QFUSE=1 launches k_qfilter
+  bool no_qfuse = false;
+  // halo/compute overlap of the hydrostatic prologue exchange (Part, kernels.hpp) on a
+  // decomposed domain; RCMDYN_NO_OVERLAP=1: the atm1/p* part first, then the atm2 part beside
+  // k_columns only
+  bool no_overlap = false;
+  // RCMDYN_FORCE_RCCL=1: the halo messages between tiles held by this engine travel as RCCL
+  // sends/receives to itself (one-rank communicator), not as device copies
+  bool force_rccl = false;
+  // RCMDYN_NEGFIX_MODE=1 (tests): the row sweep for every marked plane, dense ones included
+  int negfix_mode = 0;
+  // fault injection for the tests (RCMDYN_INJECT_LAUNCH_FAILURE=n): the n-th launch of a lazy
+  // tend's graph fails before it is issued, as a failed hipGraphLaunch would
+  int inject_launch_failure = 0;
+  static Switches read() {
+    // the two rules by which a switch counts as set: its variable exists, or holds something but "" and "0"
+    auto present = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto nonzero = [](const char* name) { const char* v = std::getenv(name); return v && *v && std::strcmp(v, "0") != 0; };
+    auto number = [](const char* name, int unset) { const char* v = std::getenv(name); return v ? std::atoi(v) : unset; };
+    Switches s;
+    s.graph_steps = std::max(1, std::min(2, number("RCMDYN_GRAPH_STEPS", 2)));
+    s.no_graph = present("RCMDYN_NO_GRAPH");
+    s.fuse_update = !present("RCMDYN_NO_FUSE_UPDATE");
+    s.nh_tfuse = !present("RCMDYN_NH_NO_TFUSE");
+    s.no_fuse_bdy = nonzero("RCMDYN_NO_FUSE_BDY");
+    s.no_defer_corr = present("RCMDYN_NO_DEFER_CORR");
+    s.lazy_tend = !present("RCMDYN_NO_LAZY_TEND");
+    s.no_qfuse = nonzero("RCMDYN_NO_QFUSE");
+    s.no_overlap = nonzero("RCMDYN_NO_OVERLAP");
+    s.force_rccl = present("RCMDYN_FORCE_RCCL");
+    s.negfix_mode = number("RCMDYN_NEGFIX_MODE", 0);
+    s.inject_launch_failure = number("RCMDYN_INJECT_LAUNCH_FAILURE", 0);
+    return s;
+  }
+};
+
 struct rcmdyn_engine {
   rcmdyn_config cfg{};
   Consts hc{};
@@ -253,14 +315,34 @@ struct rcmdyn_engine {
   std::vector<Geom> all;     // every tile of the decomposition
   std::vector<Tile> tiles;   // tiles owned here
   hipStream_t stream = nullptr;
-  hipGraphExec_t gexec[2] = {nullptr, nullptr};   // tend + bdyval, per ping-pong parity
-  hipGraphExec_t gexec2[2] = {nullptr, nullptr};  // two steps (tend + bdyval) x 2, per parity
-  // steps per replayed graph in rcmdyn_step (RCMDYN_GRAPH_STEPS, 1 or 2): two steps per launch
-  // return to the same ping-pong parity and halve the graph launches
-  const int graph_steps = std::getenv("RCMDYN_GRAPH_STEPS") ? std::max(1, std::min(2, std::atoi(std::getenv("RCMDYN_GRAPH_STEPS")))) : 2;
-  hipGraphExec_t gtend[2] = {nullptr, nullptr};   // tend alone (the drop-in rcmdyn_tend)
-  hipGraphExec_t gbdy[2] = {nullptr, nullptr};    // bdyval alone (rcmdyn_bdyval)
-  hipGraphExec_t gbdyf[2] = {nullptr, nullptr};   // rcmdyn_bdyval with the deferred corrections
+  Switches sw;
+  // tend in two phases split where the reference calls physical_parametrizations
+  // (Main/mod_tendency.F90:271): TEND_PRE runs surface_pressures .. new_pressure (and the
+  // mkslice export when `slice`), TEND_POST the rest; a step runs both.
+  static constexpr int TEND_PRE = 1, TEND_POST = 2, TEND_ALL = 3;
+  // what a tend does with its split corrections: launch them, launch them with bdyval's
+  // boundary lines (k_split_correct_bdy: the bdyval that follows skips those), or leave them
+  // to the next call
+  enum class Corr { Launch, WithBdy, Defer };
+  // the replay graphs, each captured per ping-pong parity (gpar)
+  enum class Graph {
+    Step,        // tend + bdyval (rcmdyn_step; a lazy tend with its rcmdyn_bdyval)
+    TwoSteps,    // (tend + bdyval) x 2
+    Tend,        // tend alone (the drop-in rcmdyn_tend), its corrections deferred where can_defer()
+    Bdyval,      // bdyval alone (rcmdyn_bdyval)
+    CorrBdyval,  // rcmdyn_bdyval with the deferred corrections
+    Count
+  };
+  hipGraphExec_t graphs[(int)Graph::Count][2] = {};
+  // what of the last rcmdyn_tend is not launched yet: the whole tend (a lazy tend: only its host
+  // bookkeeping is done; recorded for the parity pend_par), or its split corrections.
+  //   tend_call / tend_post_physics: None -> Tend or Corrections (or None: nothing deferred)
+  //   settle (any call but rcmdyn_bdyval): Tend -> Corrections -> None
+  //   bdyval_call: Tend -> None (the Step graph), Corrections -> None (with the boundary lines)
+  // A transition happens only once its launch succeeded: a failed one leaves the state as it was.
+  enum class Pending { None, Tend, Corrections };
+  Pending pend = Pending::None;
+  int pend_par = 0;
   // step error flags: host-mapped snapshot ring written by the last launch of every tend,
   // one event per slot; the host checks a step's flags once its event completed and keeps
   // at most FLAG_LAG steps unchecked, so no entry point synchronises the stream per step
@@ -295,68 +377,20 @@ struct rcmdyn_engine {
   bool diag = false;         // write the per-tend diagnostic fields
   KernelProf* prof = nullptr;  // set while rcmdyn_kernel_times runs
   double last_ms = 0.0;
-  // RCMDYN_NO_GRAPH=1 runs rcmdyn_step eagerly (the path of RCCL-decomposed runs), for timing
-  const bool no_graph = std::getenv("RCMDYN_NO_GRAPH") != nullptr;
-  // k_momentum and k_scalars as one launch (k_update); RCMDYN_NO_FUSE_UPDATE=1: two launches
-  const bool fuse_update = std::getenv("RCMDYN_NO_FUSE_UPDATE") == nullptr;
-  // NH: tend's time filters of t, qv, qc in k_nh_tend_c and the negative-moisture fix, into
-  // the other parity (Tile::tq); RCMDYN_NH_NO_TFUSE=1: in place in k_nh_tfilter_a1
-  const bool nh_tfuse = std::getenv("RCMDYN_NH_NO_TFUSE") == nullptr;
   // parity of t, qv, qc: the step's ping-pong (hydrostatic), Tile::tq (NH)
   int thp(const Tile& t) const { return cfg.idynamic == 2 ? t.tq : t.cur; }
   // the parity the step graphs are captured for
   int gpar() const { return thp(tiles[0]); }
-  // rcmdyn_step's hydrostatic bdyval runs inside k_split_correct_bdy (RCMDYN_NO_FUSE_BDY: two
-  // launches of its own, as after rcmdyn_tend)
-  const bool no_fuse_bdy = [] {
-    const char* v = std::getenv("RCMDYN_NO_FUSE_BDY");
-    return v && *v && std::strcmp(v, "0") != 0;
-  }();
-  bool fuse_bdy = false;      // set by step_once for the tend + bdyval pair it runs
-  // the drop-in pair (rcmdyn_tend, then rcmdyn_bdyval): tend leaves its split corrections
-  // pending and bdyval launches them with its boundary lines (k_split_correct_bdy, the form of
-  // rcmdyn_step); any other call in between launches them alone first (settle).
-  // RCMDYN_NO_DEFER_CORR=1: tend launches them itself.
-  const bool no_defer_corr = std::getenv("RCMDYN_NO_DEFER_CORR") != nullptr;
-  bool defer_corr = false;    // set by tend_call / post_physics around the tend they run
-  bool corr_pending = false;  // the last tend's corrections are not launched yet
-  // lazy tend (drop-in pair): rcmdyn_tend does the host bookkeeping and leaves the launch to
-  // the next call: rcmdyn_bdyval replays the one-step graph of tend + bdyval (rcmdyn_step's),
-  // any other call (settle) replays tend's own graph first.  RCMDYN_NO_LAZY_TEND=1: off
-  const bool lazy_tend = std::getenv("RCMDYN_NO_LAZY_TEND") == nullptr;
-  bool tend_pending = false;
-  // fault injection for the tests (RCMDYN_INJECT_LAUNCH_FAILURE=n at create): the n-th launch of
-  // a lazy tend's graph fails before it is issued, as a failed hipGraphLaunch would
-  int inject_fail = 0;
-  void inject_launch_failure() {
-    if (inject_fail > 0 && --inject_fail == 0) throw std::runtime_error("rcmdyn: injected launch failure");
-  }
-  int lazy_par = 0;
-  // the hydrostatic step without k_qfilter (its work in k_columns, k_scalars and the extra
-  // blocks of k_split_project / k_split_correct); RCMDYN_NO_QFUSE=1 launches k_qfilter
-  const bool no_qfuse = [] {
-    const char* v = std::getenv("RCMDYN_NO_QFUSE");
-    return v && *v && std::strcmp(v, "0") != 0;
-  }();
-  bool qfuse() const { return cfg.idynamic != 2 && !no_qfuse; }
+  int inject_fail = 0;        // launches of a lazy tend's graph left before the injected failure
+  bool qfuse() const { return cfg.idynamic != 2 && !sw.no_qfuse; }
   // nqx = 5, hydrostatic qfuse: the species' serial fix joins the qv / qc one after the split
   // corrections (k_negfix_serial_qx)
   bool serial_with_corr() const { return qfuse() && hc.nsp > 0; }
-  // halo/compute overlap of the hydrostatic prologue exchange (Part, kernels.hpp) on a
-  // decomposed domain; RCMDYN_NO_OVERLAP=1: the atm1/p* part first, then the atm2 part beside
-  // k_columns only
-  const bool no_overlap = [] {
-    const char* v = std::getenv("RCMDYN_NO_OVERLAP");
-    return v && *v && std::strcmp(v, "0") != 0;
-  }();
-  // (idiffu = 3: the column terms are formed after the whole exchange, so no overlap)
-  bool overlap() const { return halo && cfg.idynamic != 2 && cfg.idiffu != 3 && !no_overlap; }
-  bool post_inner = false;    // tend_pre ran part 1 of k_momentum / k_scalars
+  // halo/compute overlap of the hydrostatic prologue exchange (Switches::no_overlap; idiffu = 3:
+  // the column terms are formed after the whole exchange, so no overlap)
+  bool overlap() const { return halo && cfg.idynamic != 2 && cfg.idiffu != 3 && !sw.no_overlap; }
   std::string err;
   std::unique_ptr<Comm> comm;
-  // RCMDYN_FORCE_RCCL=1: the halo messages between tiles held by this engine travel as RCCL
-  // sends/receives to itself (one-rank communicator), not as device copies
-  const bool force_rccl = std::getenv("RCMDYN_FORCE_RCCL") != nullptr;
   int device = 0;
   // halo/compute overlap: the second stream carries the atm2 part of the prologue exchange
   // while the first computes what needs only atm1 and p* (xch_begin / xch_join)
@@ -446,8 +480,7 @@ struct rcmdyn_engine {
       }
     }
     c.pd = cfg.pd;
-    // RCMDYN_NEGFIX_MODE=1 (tests): the row sweep for every marked plane, dense ones included
-    c.negfix_mode = std::getenv("RCMDYN_NEGFIX_MODE") ? std::atoi(std::getenv("RCMDYN_NEGFIX_MODE")) : 0;
+    c.negfix_mode = sw.negfix_mode;
     // non-hydrostatic core: diffusion constants (Main/mod_diffusion.F90:108-113), sound
     c.idynamic = cfg.idynamic;
     if (cfg.idynamic == 2) {
@@ -665,7 +698,7 @@ struct rcmdyn_engine {
     f.a2u = t.a2u[c]; f.a2v = t.a2v[c]; f.a2t = t.a2t[q]; f.a2qv = t.a2qv[q]; f.a2qc = t.a2qc[q];
     f.b1t = t.a1t[o]; f.b1qv = t.a1qv[o]; f.b1qc = t.a1qc[o];
     f.b2t = t.a2t[o]; f.b2qv = t.a2qv[o]; f.b2qc = t.a2qc[o];
-    f.tfuse = nh_tfuse ? 1 : 0;
+    f.tfuse = sw.nh_tfuse ? 1 : 0;
     f.psa = t.psa_[c]; f.psb = t.psb_[c];
     f.msfx = t.msfx; f.msfd = t.msfd; f.coriol = t.coriol; f.ht = t.ht; f.xmsf = t.xmsf; f.dmsf = t.dmsf;
     f.hgfact = t.hgfact; f.rgcr = t.rgcr; f.rgdt = t.rgdt; f.ibcr = t.ibcr; f.ibdt = t.ibdt;
@@ -722,6 +755,8 @@ struct rcmdyn_engine {
   }
 
   void create(const rcmdyn_config* c, std::vector<PlanOp>* plan = nullptr) {
+    sw = Switches::read();
+    inject_fail = sw.inject_launch_failure;
     cfg = *c;
     dry = plan != nullptr;
     if (cfg.abi_version != RCMDYN_ABI_VERSION) throw std::runtime_error("rcmdyn: ABI version mismatch");
@@ -800,7 +835,6 @@ struct rcmdyn_engine {
     }
     check_block_sizes();
     check_lds();
-    if (const char* e = std::getenv("RCMDYN_INJECT_LAUNCH_FAILURE")) inject_fail = std::atoi(e);
     HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     HIPCHK(hipMalloc(&dc, sizeof(Consts)));
     HIPCHK(hipMemcpy(dc, &hc, sizeof(Consts), hipMemcpyHostToDevice));
@@ -831,7 +865,7 @@ struct rcmdyn_engine {
         comm.reset(make_rccl_comm(cfg));
       }
     }
-    else if (force_rccl && halo) comm.reset(make_rccl_self_comm());
+    else if (sw.force_rccl && halo) comm.reset(make_rccl_self_comm());
     if (comm) {
       HIPCHK(hipMalloc(&derr, sizeof(int32_t)));
       HIPCHK(hipHostMalloc((void**)&hgerr, sizeof(int32_t) * NFLAGSLOT, hipHostMallocMapped | hipHostMallocCoherent));
@@ -872,9 +906,9 @@ struct rcmdyn_engine {
   }
 
   void invalidate_graphs() {
-    for (hipGraphExec_t* g : {gexec, gexec2, gtend, gbdy, gbdyf})
-      for (int p = 0; p < 2; p++)
-        if (g[p]) { (void)hipGraphExecDestroy(g[p]); g[p] = nullptr; }
+    for (auto& g : graphs)
+      for (hipGraphExec_t& x : g)
+        if (x) { (void)hipGraphExecDestroy(x); x = nullptr; }
   }
 
   // ------------------------------------------------------------------ step error flags
@@ -1410,7 +1444,7 @@ struct rcmdyn_engine {
         const int p = peer_of(t, d);
         if (p < 0) continue;
         Tile* pt = local_tile(p);
-        if (S[q].count[d] && pt && force_rccl && comm) {
+        if (S[q].count[d] && pt && sw.force_rccl && comm) {
           // one-rank communicator: the n-th send to self matches the n-th receive
           const size_t pq = pt - tiles.data();
           if (R[pq].count[OPP[d]] != S[q].count[d]) throw std::runtime_error("rcmdyn: halo size mismatch");
@@ -1807,7 +1841,7 @@ struct rcmdyn_engine {
     // halo/compute overlap of a whole tend on a decomposed domain: the cr/qdot/xkcr exchange
     // on the second stream beside k_nh_tend_c (which reads them at its own point only), the
     // cqv/cqc exchange beside k_nh_tend_d (which does not read them)
-    const bool ovl = halo && !no_overlap && phase == TEND_ALL && !slice && cfg.isladvec != 1;
+    const bool ovl = halo && !sw.no_overlap && phase == TEND_ALL && !slice && cfg.isladvec != 1;
     struct Grids { dim3 fr, ce1, ci1; };
     auto grids = [&](const Geom& g) {
       const int nce_j = g.jce2 - g.jce1 + 1, nce_i = g.ice2 - g.ice1 + 1;
@@ -1914,12 +1948,12 @@ struct rcmdyn_engine {
       KLAUNCH(k_nh_negfix, dim3(1024), dim3(256), 0, stream, g, dc, f);
       KLAUNCH(k_nh_negfix_serial, dim3(2 * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc, f);
       // tend's time filters (tfuse = 0) with part A of the first acoustic sub-step (sound, :163-718)
-      if (nh_tfuse)     // part A alone: one column walk per cross column
+      if (sw.nh_tfuse)     // part A alone: one column walk per cross column
         KLAUNCH(k_nh_a1_col, q.ce1, BLK, 0, stream, g, dc, f);
       else
         KLAUNCH(k_nh_tfilter_a1, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, kp), BLK, 0, stream, g, dc, f);
     });
-    if (nh_tfuse) for (auto& t : tiles) t.tq = 1 - t.tq;     // the filtered t, qv, qc
+    if (sw.nh_tfuse) for (auto& t : tiles) t.tq = 1 - t.tq;     // the filtered t, qv, qc
     // sound, Main/mod_sound.F90:163-718
     for (int it = 1; it <= istep; it++) {
       // part A: sub-step 1 in k_nh_tfilter_a1, the later ones in the previous k_nh_sound_cd
@@ -1938,7 +1972,7 @@ struct rcmdyn_engine {
         KLAUNCH(k_nh_sound_uv, grid3(g.jde2 - g.jde1 + 1, g.ide2 - g.ide1 + 1, kz),
                 BLK, 0, stream, g, dc, ds, nhfields(t), istep, fin, first, part);
       };
-      if (halo && !no_overlap) {
+      if (halo && !sw.no_overlap) {
         side_begin();
         each([&](Tile& t) { sound_uv(t, 1); });
         side_end(0);
@@ -2049,23 +2083,23 @@ struct rcmdyn_engine {
     hs.xbctime = hs.xbctime + cfg.dtsec;
   }
 
-  // tend in two phases split where the reference calls physical_parametrizations
-  // (Main/mod_tendency.F90:271): TEND_PRE runs surface_pressures .. new_pressure (and the
-  // mkslice export when `slice`), TEND_POST the rest; a step runs both.
-  static constexpr int TEND_PRE = 1, TEND_POST = 2, TEND_ALL = 3;
-  void tend(int phase = TEND_ALL, bool slice = false) {
+  // tend, whole or one of its two phases (TEND_PRE, TEND_POST); corr: what the hydrostatic
+  // TEND_POST does with the split corrections
+  void tend(Corr corr, int phase = TEND_ALL, bool slice = false) {
     if (cfg.idynamic == 2) nh_tend(phase, slice);
     else {
       // part 1 of k_momentum / k_scalars beside the prologue exchange only in a whole tend (no
-      // host work between) without the semi-Lagrangian pass that precedes them
-      if (phase & TEND_PRE) tend_pre(slice, phase == TEND_ALL && !slice && cfg.isladvec != 1);
-      if (phase & TEND_POST) tend_post();
+      // host work between) without the semi-Lagrangian pass that precedes them; a split tend
+      // never runs it, so nothing is carried from one phase's call to the other's
+      const bool post_inner = (phase & TEND_PRE) && tend_pre(slice, phase == TEND_ALL && !slice && cfg.isladvec != 1);
+      if (phase & TEND_POST) tend_post(corr, post_inner);
     }
     // the hydrostatic step's snapshot is written by k_split_correct's clock lane
     if ((phase & TEND_POST) && cfg.idynamic == 2) KLAUNCH(k_flag_snapshot, dim3(1), dim3(64), 0, stream, ds, dflags);
   }
 
-  void tend_pre(bool slice, bool with_post = false) {
+  // returns whether part 1 of k_momentum / k_scalars ran beside the exchange (with_post allows it)
+  bool tend_pre(bool slice, bool with_post) {
     const int kz = cfg.kz;
     // One exchange point for the whole prologue (Main/mod_tendency.F90:815-1116,
     // Main/mod_slice.F90:102-300): the decoupled fields are recomputed where read, so their
@@ -2113,7 +2147,6 @@ struct rcmdyn_engine {
       pro.insert(pro.end(), pro2.begin(), pro2.end());
       side_begin();
       each([&](Tile& t) { if (t.nint) columns(t, 1, t.nint, false); });
-      post_inner = with_post;
       if (with_post) each([&](Tile& t) { post_launch(t, 1); });
       side_end(0);
       xchv(pro);
@@ -2131,6 +2164,7 @@ struct rcmdyn_engine {
     }
     if (cfg.idiffu == 3) diffu6();
     if (slice) run_slice();
+    return overlap() && with_post;
   }
 
   // idiffu = 3: the column terms of every tile, then (decomposed) one width-1 exchange so the
@@ -2157,7 +2191,7 @@ struct rcmdyn_engine {
     const int pm = part == 0 ? 0 : (t.nint && t.mom_in ? part : (part == 1 ? -1 : 0));
     const int ps = part == 0 ? 0 : (t.nint && t.sca_in ? part : (part == 1 ? -1 : 0));
     const int mo = pm > 0 ? t.mj0 : g.jdi1, so = ps > 0 ? t.sj0 : g.jcx1();     // block-column origins
-    if (fuse_update && pm >= 0 && ps >= 0) {
+    if (sw.fuse_update && pm >= 0 && ps >= 0) {
       const int mnx = (mj2 - mo + MBJ) / MBJ, mny = (mi2 - g.idi1 + MBI) / MBI;
       const int snx = (g.jcx2() - so + SBJ) / SBJ, sny = (g.icx2() - g.icx1() + SBI) / SBI;
       KLAUNCH(k_update, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc, ds,
@@ -2173,7 +2207,7 @@ struct rcmdyn_engine {
               dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
   }
 
-  void tend_post() {
+  void tend_post(Corr corr, bool post_inner) {
     const int kz = cfg.kz, ns = cfg.nsplit;
     const bool fused = split_fused();
     // semi-Lagrangian moisture advection (isladvec = 1): owned points, then the ring k_scalars
@@ -2190,7 +2224,6 @@ struct rcmdyn_engine {
     }
     // fused tendencies + forecast + time filter (part 2 when tend_pre ran part 1)
     each([&](Tile& t) { post_launch(t, post_inner ? 2 : 0); });
-    post_inner = false;
     tke_step();
     if (hc.nsp) {
       // nqx = 5: the hydrometeors beyond qc, their forecast (and ring), then the fix and filter
@@ -2283,8 +2316,7 @@ struct rcmdyn_engine {
     // the fused split step also produced ddsum/dhsum on the left/bottom ghost ring
     if (!fused) xch({{FK::DHSUM, ns}}, 1, 1);
     // corrections + rcmtimer advance (last tile's launch); deferred to bdyval in the drop-in pair
-    if (defer_corr && !fuse_bdy) corr_pending = true;
-    else launch_corrections(fuse_bdy);
+    if (corr != Corr::Defer) launch_corrections(corr == Corr::WithBdy);
     hs.lcount += 1;
     if (hs.lcount == 2) hs.dt = 2.0 * cfg.dtsec;
   }
@@ -2342,34 +2374,26 @@ struct rcmdyn_engine {
   // not with a communicator: a rank-local call (a get) between tend and bdyval would then issue
   // the step's flag reduction on one rank only
   bool can_defer() const {
-    return cfg.idynamic != 2 && !comm && !no_fuse_bdy && !no_defer_corr && (!halo || split_fused());
+    return cfg.idynamic != 2 && !comm && !sw.no_fuse_bdy && !sw.no_defer_corr && (!halo || split_fused());
   }
+  Corr drop_in_corr() const { return can_defer() ? Corr::Defer : Corr::Launch; }
   // a call other than rcmdyn_bdyval after a tend that deferred its corrections: launch them
   void settle() {
-    if (tend_pending) {              // the lazy tend's own graph (captured with deferred corrections)
-      inject_launch_failure();
-      HIPCHK(hipGraphLaunch(gtend[lazy_par], stream));
-      tend_pending = false;          // only once launched: a failed launch leaves the tend pending
-      corr_pending = true;
+    if (pend == Pending::Tend) {  // the lazy tend's own graph (captured with deferred corrections)
+      replay(Graph::Tend, pend_par);
+      pend = Pending::Corrections;
     }
-    if (!corr_pending) return;
+    if (pend != Pending::Corrections) return;
     launch_corrections(false);     // if this throws, the corrections stay pending for the next call
-    corr_pending = false;
+    pend = Pending::None;
     note_step(hs.lcount);
   }
   // rcmdyn_bdyval after a deferring tend: the corrections with the boundary lines, then the
   // rest of bdyval as rcmdyn_step runs it
   void fused_bdyval() {
-    fuse_bdy = true;
-    try {
-      launch_corrections(true);
-      corr_pending = false;
-      bdyval();
-    } catch (...) {
-      fuse_bdy = false;
-      throw;
-    }
-    fuse_bdy = false;
+    launch_corrections(true);
+    pend = Pending::None;
+    bdyval(true);
   }
 
   // one spstep substep: gradient of delh(src) -> (uu,vv) -> divergence -> mode update
@@ -2413,12 +2437,12 @@ struct rcmdyn_engine {
     return a;
   }
 
-  void bdyval() {
+  // lines_done: the boundary lines and slices were set by k_split_correct_bdy (Corr::WithBdy),
+  // and the clock advance of the step moves here (last tile's launch)
+  void bdyval(bool lines_done) {
     if (cfg.idynamic == 2) { nh_bdyval(); return; }
     const int kz = cfg.kz;
-    // fused (step_once): the boundary lines and slices were set by k_split_correct_bdy, and
-    // the clock advance of the step moves here (last tile's launch)
-    if (!fuse_bdy) {
+    if (!lines_done) {
       each([&](Tile& t) {
         const Geom& g = t.g;
         KLAUNCH(k_bdyval_set, dim3((std::max(g.jde2 - g.jde1, g.ide2 - g.ide1) + 65) / 64, 6, kz), dim3(64), 0,
@@ -2429,9 +2453,9 @@ struct rcmdyn_engine {
     }
     for (size_t q = 0; q < tiles.size(); q++) {
       Tile& t = tiles[q];
-      const int adv = q + 1 == tiles.size() ? (fuse_bdy ? 2 : 1) : 0;
+      const int adv = q + 1 == tiles.size() ? (lines_done ? 2 : 1) : 0;
       if (hc.nsp)
-        KLAUNCH(k_bdyval_qx, dim3(kz, hc.nsp), dim3(256), 0, stream, t.g, ds, qx_args(t), fuse_bdy ? 1 : -1,
+        KLAUNCH(k_bdyval_qx, dim3(kz, hc.nsp), dim3(256), 0, stream, t.g, ds, qx_args(t), lines_done ? 1 : -1,
                 (int)!cfg.present_qc, t.psa_[t.cur], bdy_args(t, 1).sl, slen);
       KLAUNCH(k_bdyval_qc, dim3(kz), dim3(256), 0, stream, t.g, (int)!cfg.present_qc, (int)(cfg.iboudy == 3 || cfg.iboudy == 4),
               t.a1qc[t.cur], t.a1qv[t.cur], t.psa_[t.cur], bdy_args(t, 1).sl, slen, ds, cfg.dtsec, adv, dflags);
@@ -2445,15 +2469,9 @@ struct rcmdyn_engine {
   // inflow/outflow pass in a launch of its own.  A decomposed domain needs no slice exchange
   // then (split_fused: every tile computes its ghost ring).
   void step_once() {
-    fuse_bdy = cfg.idynamic != 2 && !no_fuse_bdy && (!halo || split_fused());
-    try {
-      tend();
-      bdyval();
-    } catch (...) {
-      fuse_bdy = false;
-      throw;
-    }
-    fuse_bdy = false;
+    const bool with_bdy = cfg.idynamic != 2 && !sw.no_fuse_bdy && (!halo || split_fused());
+    tend(with_bdy ? Corr::WithBdy : Corr::Launch);
+    bdyval(with_bdy);
   }
 
   // ------------------------------------------------------------------ graph replay
@@ -2461,7 +2479,7 @@ struct rcmdyn_engine {
   // for NH not a step of another shape (istep on the first two steps, the day alarm's
   // radiative coefficients)
   bool graph_ok(int nsteps = 1) const {
-    if (no_graph || prof || (comm && !comm->graph_safe())) return false;
+    if (sw.no_graph || prof || (comm && !comm->graph_safe())) return false;
     if (cfg.idynamic != 2) return true;
     for (int q = 0; q < nsteps; q++)
       if (hs.lcount + q < 2 || nh_day_alarm_at(hs.lcount + q)) return false;
@@ -2470,7 +2488,7 @@ struct rcmdyn_engine {
   // host bookkeeping of a replayed tend / bdyval (what tend() and bdyval() do on the host)
   void replayed_tend() {
     if (cfg.idynamic != 2) for (auto& t : tiles) t.cur = 1 - t.cur;
-    else if (nh_tfuse) for (auto& t : tiles) t.tq = 1 - t.tq;
+    else if (sw.nh_tfuse) for (auto& t : tiles) t.tq = 1 - t.tq;
     hs.lcount += 1;
     if (hs.lcount == 2) hs.dt = 2.0 * cfg.dtsec;
   }
@@ -2485,23 +2503,19 @@ struct rcmdyn_engine {
     HIPCHK(hipEventRecord(e0, stream));
     for (int s = 0; s < n; s++) {
       check(FLAG_LAG);
-      const int par = gpar();
-      if (graph_steps == 2 && s + 1 < n && graph_ok(2)) {
-        if (!gexec2[par]) capture(par, 3, 2);
-        HIPCHK(hipGraphLaunch(gexec2[par], stream));
-        replayed_tend();
-        replayed_bdyval();
-        note_step(hs.lcount);
-        replayed_tend();
-        replayed_bdyval();
-        s++;
-      } else if (graph_ok()) {
-        if (!gexec[par]) capture(par, 3);
-        HIPCHK(hipGraphLaunch(gexec[par], stream));
+      const bool two = sw.graph_steps == 2 && s + 1 < n && graph_ok(2);
+      if (two || graph_ok()) {
+        replay(two ? Graph::TwoSteps : Graph::Step, gpar());
         replayed_tend();
         replayed_bdyval();
       } else {
         step_once();
+      }
+      if (two) {                       // the second step of the graph
+        note_step(hs.lcount);
+        replayed_tend();
+        replayed_bdyval();
+        s++;
       }
       note_step(hs.lcount, s == n - 1);
     }
@@ -2518,95 +2532,103 @@ struct rcmdyn_engine {
   // the drop-in call sequence of RCM_run (Main/mod_regcm_interface.F90:189,208): each call
   // replays its own captured graph and returns without synchronising the stream
   void tend_call() {
-    prepare();
-    settle();
-    check(FLAG_LAG);
+    begin_tend();
     const int par = gpar();
-    defer_corr = can_defer();
-    try {
-      if (graph_ok()) {
-        if (!gtend[par]) capture(par, 1);
-        if (lazy_tend && defer_corr && !ghosts_stale) {
-          if (!gexec[par]) {
-            defer_corr = false;          // the step graph runs tend with its corrections
-            capture(par, 3);
-          }
-          defer_corr = false;
-          tend_pending = true;
-          lazy_par = par;
-          replayed_tend();               // the clock and parities as after the launch
-          return;                        // note_step: at the launch
-        }
-        HIPCHK(hipGraphLaunch(gtend[par], stream));
-        replayed_tend();
-        corr_pending = defer_corr;
-      } else {
-        tend();
+    const Corr corr = drop_in_corr();
+    if (graph_ok()) {
+      ensure(Graph::Tend, par);
+      if (sw.lazy_tend && corr == Corr::Defer && !ghosts_stale) {
+        ensure(Graph::Step, par);
+        pend = Pending::Tend;
+        pend_par = par;
+        replayed_tend();               // the clock and parities as after the launch
+        return;                        // note_step: at the launch
       }
-    } catch (...) {
-      defer_corr = false;
-      throw;
+      replay(Graph::Tend, par);
+      replayed_tend();
+    } else {
+      tend(corr);
     }
-    defer_corr = false;
-    if (!corr_pending) note_step(hs.lcount);     // else at the corrections' launch
+    tend_done(corr);
+  }
+  void begin_tend() { prepare(); settle(); check(FLAG_LAG); }     // every drop-in tend entry point starts so
+  // a tend was launched: its corrections are pending, or else its flags are noted (now, not at their launch)
+  void tend_done(Corr corr) {
+    if (corr == Corr::Defer) pend = Pending::Corrections;
+    else note_step(hs.lcount);
+  }
+  // rcmdyn_tend_pre_physics / rcmdyn_tend_post_physics: tend's two phases, run eagerly around
+  // the host's physics; the corrections go with the next rcmdyn_bdyval as after rcmdyn_tend
+  void tend_pre_physics() { begin_tend(); tend(Corr::Launch, TEND_PRE, true); }
+  void tend_post_physics() {
+    begin_tend();
+    const Corr corr = drop_in_corr();
+    tend(corr, TEND_POST);
+    tend_done(corr);
   }
   void bdyval_call() {
     prepare();
-    if (tend_pending) {              // the lazy tend and this bdyval: one step graph
-      inject_launch_failure();
-      HIPCHK(hipGraphLaunch(gexec[lazy_par], stream));
-      tend_pending = false;          // only once launched: a failure keeps the step pending
+    if (pend == Pending::Tend) {  // the lazy tend and this bdyval: one step graph
+      replay(Graph::Step, pend_par);
+      pend = Pending::None;
       replayed_bdyval();
-      note_step(hs.lcount);
-      return;
-    }
-    const int par = gpar();
-    if (corr_pending) {
-      if (graph_ok() && !ghosts_stale) {
-        if (!gbdyf[par]) capture(par, 4);
-        HIPCHK(hipGraphLaunch(gbdyf[par], stream));
-        corr_pending = false;
-        replayed_bdyval();
-      } else {
-        fused_bdyval();
-      }
       note_step(hs.lcount);
       return;
     }
     // after a put the ghost rings are not step results: bdyval runs eagerly (its slice
     // exchange depends on that, bdyval())
-    if (graph_ok() && !ghosts_stale) {
-      if (!gbdy[par]) capture(par, 2);
-      HIPCHK(hipGraphLaunch(gbdy[par], stream));
+    const bool graph = graph_ok() && !ghosts_stale;
+    if (pend == Pending::Corrections) {
+      if (graph) {
+        replay(Graph::CorrBdyval, gpar());
+        pend = Pending::None;
+        replayed_bdyval();
+      } else {
+        fused_bdyval();
+      }
+      note_step(hs.lcount);
+    } else if (graph) {
+      replay(Graph::Bdyval, gpar());
       replayed_bdyval();
     } else {
-      bdyval();
+      bdyval(false);
     }
   }
 
-  // capture tend (what & 1) and/or bdyval (what & 2) for the current ping-pong parity; the
-  // host bookkeeping done in tend()/bdyval() is rolled back, the replay redoes it per launch
-  void capture(int par, int what, int nsteps = 1) {
+  // record one graph for the ping-pong parity the engine is at (par = gpar()); the host
+  // bookkeeping done in tend() / bdyval() and the pending state are rolled back, the replay
+  // redoes them per launch
+  void capture(Graph kind, int par) {
     const StepState save = hs;
-    const bool pend = corr_pending;
+    const Pending saved = pend;
     std::vector<int> curs, tqs;
     for (auto& t : tiles) { curs.push_back(t.cur); tqs.push_back(t.tq); }
     hipGraph_t graph;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    for (int q = 0; q < nsteps; q++) {
-      if (what == 3) step_once();
-      else if (what == 4) fused_bdyval();
-      else if (what & 1) tend();
-      else bdyval();
+    switch (kind) {
+      case Graph::Step: step_once(); break;
+      case Graph::TwoSteps: step_once(); step_once(); break;
+      case Graph::Tend: tend(drop_in_corr()); break;
+      case Graph::Bdyval: bdyval(false); break;
+      case Graph::CorrBdyval: fused_bdyval(); break;
+      case Graph::Count: break;
     }
     HIPCHK(hipStreamEndCapture(stream, &graph));
-    hipGraphExec_t& x = nsteps == 2 ? gexec2[par] : what == 3 ? gexec[par] : what == 4 ? gbdyf[par]
-                        : what == 1 ? gtend[par] : gbdy[par];
-    HIPCHK(hipGraphInstantiate(&x, graph, nullptr, nullptr, 0));
+    HIPCHK(hipGraphInstantiate(&graphs[(int)kind][par], graph, nullptr, nullptr, 0));
     HIPCHK(hipGraphDestroy(graph));
     hs = save;
-    corr_pending = pend;
+    pend = saved;
     for (size_t q = 0; q < tiles.size(); q++) { tiles[q].cur = curs[q]; tiles[q].tq = tqs[q]; }
+  }
+  void ensure(Graph kind, int par) { if (!graphs[(int)kind][par]) capture(kind, par); }
+  // launch a graph, captured first if absent; the caller moves the pending state only after this
+  // returns.  RCMDYN_INJECT_LAUNCH_FAILURE=n counts the launches that carry a lazy tend (settle's
+  // Tend, bdyval_call's Step): the n-th fails before it is issued.
+  void replay(Graph kind, int par) {
+    ensure(kind, par);
+    if (pend == Pending::Tend && inject_fail > 0 && --inject_fail == 0)
+      throw std::runtime_error("rcmdyn: injected launch failure");
+    HIPCHK(hipGraphLaunch(graphs[(int)kind][par], stream));
   }
 
   // rcmdyn_exchange_plan: the communication calls of put + bdyval + nsteps x (tend + bdyval),
@@ -2615,7 +2637,7 @@ struct rcmdyn_engine {
   void plan_run(int nsteps) {
     prepare();
     ghosts_stale = true;           // as after rcmdyn_put
-    bdyval();
+    bdyval(false);
     for (int s = 0; s < nsteps; s++) {
       step_once();
       note_step(hs.lcount, s == nsteps - 1);
@@ -2627,14 +2649,10 @@ struct rcmdyn_engine {
     settle();
     KernelProf kp;
     HIPCHK(hipStreamSynchronize(stream));
-    prof = &kp;
-    try {
+    {
+      struct Scope { KernelProf*& p; ~Scope() { p = nullptr; } } profiling{prof = &kp};   // however the steps end
       for (int s = 0; s < nsteps; s++) step_once();
-    } catch (...) {
-      prof = nullptr;
-      throw;
     }
-    prof = nullptr;
     HIPCHK(hipStreamSynchronize(stream));
     std::vector<std::string> order;
     std::vector<double> tot;
@@ -2888,31 +2906,9 @@ int rcmdyn_get_time(rcmdyn_t* h, int64_t* lcount, double* dt, double* xbctime) {
 
 int rcmdyn_tend(rcmdyn_t* h) { return guard(h, [&] { h->tend_call(); }); }
 
-int rcmdyn_tend_pre_physics(rcmdyn_t* h) {
-  return guard(h, [&] {
-    h->prepare();
-    h->settle();
-    h->check(rcmdyn_engine::FLAG_LAG);
-    h->tend(rcmdyn_engine::TEND_PRE, true);
-  });
-}
+int rcmdyn_tend_pre_physics(rcmdyn_t* h) { return guard(h, [&] { h->tend_pre_physics(); }); }
 
-int rcmdyn_tend_post_physics(rcmdyn_t* h) {
-  return guard(h, [&] {
-    h->prepare();
-    h->settle();
-    h->check(rcmdyn_engine::FLAG_LAG);
-    h->defer_corr = h->can_defer();       // the corrections go with the next rcmdyn_bdyval
-    try {
-      h->tend(rcmdyn_engine::TEND_POST);
-    } catch (...) {
-      h->defer_corr = false;
-      throw;
-    }
-    h->defer_corr = false;
-    if (!h->corr_pending) h->note_step(h->hs.lcount);
-  });
-}
+int rcmdyn_tend_post_physics(rcmdyn_t* h) { return guard(h, [&] { h->tend_post_physics(); }); }
 
 int rcmdyn_bdyin(rcmdyn_t* h) {
   return guard(h, [&] {

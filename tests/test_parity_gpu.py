@@ -457,6 +457,41 @@ def test_lazy_tend_survives_failed_launch(c1_data, monkeypatch):
     a.close()                          # launches the pending tend; no error
 
 
+def test_pending_state_transitions(c1_data, monkeypatch):
+    """The transitions of the pending state that no other test drives: a tend settling the tend
+    before it, rcmdyn_step settling a pending tend before its two-step graph, a get settling
+    the corrections that the post-physics half deferred, and a bdyval with nothing pending.  Bit-identical after every round to an
+    engine that keeps nothing pending (RCMDYN_NO_LAZY_TEND and RCMDYN_NO_DEFER_CORR) and makes
+    the same calls."""
+    from regcm_amd.dycore import DynCore
+    rc, data = c1_data
+    a = DynCore(rc, data["split"])
+    monkeypatch.setenv("RCMDYN_NO_LAZY_TEND", "1")
+    monkeypatch.setenv("RCMDYN_NO_DEFER_CORR", "1")
+    ref = DynCore(rc, data["split"])
+    for e in (ref, a):
+        e.put_state(data["state"])
+        e.bdyval()
+    for n in range(3):
+        for e in (ref, a):
+            e.tend()
+            e.tend()                   # settles the first tend
+            e.bdyval()
+            e.tend()
+            e.step(2)                  # settles the tend, then two steps in one graph
+            e.tend_pre_physics()
+            e.tend_post_physics()
+            e.get("ATM1_T")            # settles the deferred corrections
+            e.bdyval()
+            e.tend()
+            e.bdyval()
+            e.bdyval()                 # nothing pending
+        assert a.get_time() == ref.get_time()
+        for name in STATE_FIELDS:
+            assert np.array_equal(a.get(name), ref.get(name)), name
+        assert np.array_equal(a.reductions(), ref.reductions())
+
+
 def _dependent_negatives(cq, rc):
     """(k, i, j) cross points of the interior where the reference's serial sweep reads an
     already-fixed predecessor (Main/mod_tendency.F90:382-393)."""
