@@ -223,11 +223,33 @@ def test_negfix_wavefront_equals_row_sweep(name, monkeypatch):
     """The serial fix of a dense plane two ways (qxcommon.hpp): the skewed wavefront (default)
     and the row sweep in the reference's order (RCMDYN_NEGFIX_MODE=1) give the same state bit for
     bit, on the patchy hydrometeor fields whose qi / qr / qs and qc planes hold chains of
-    dependent negatives (at C3, the grid of tools/species_bench.py, hundreds of links deep)."""
+    dependent negatives (at C3, the grid of tools/species_bench.py, hundreds of links deep).
+    That the two runs differ in the code they execute is asserted from the oracle's forecast of
+    the first step (tests/test_negfix_gpu.py restates the marking rule and negfix_resolve's
+    choice): some plane has more than 16 marked rows, and where the rows fill more than one
+    wavefront (C3) every 64-row boundary holds a dependent negative with a negative predecessor
+    on the row below it, so the ring between the wavefronts carries values that matter."""
+    from oracle.oracle import OracleCore
     from regcm_amd.dycore import DynCore
+    from tests.test_negfix_gpu import Marks, forecasts
     rc = dataclasses.replace(CONFIGS[name], ipptls=2)
     data = icbc.generate(CONFIGS[name])
     st = species_state(rc, data)
+    o = start(OracleCore, rc, data, st)
+    sp = ["QC", "QI", "QR", "QS"]
+    a2 = {nm: o.get(f"ATM2_{nm}") for nm in sp}
+    o.tend()
+    densest, hit, every = 0, set(), set()
+    for cq in forecasts(o, a2, sp).values():
+        m = Marks(cq, rc)
+        wf = m.takes_wavefront(False)
+        if wf.any():
+            densest = max(densest, int(m.nmarked()[wf].max()))
+            h, ev = m.ring_boundaries(wf)
+            hit |= set(h)
+            every |= set(ev)
+    assert densest > 16, densest
+    assert hit == every and (bool(every) or rc.iy - 3 <= 64), (sorted(hit), sorted(every))
     runs = []
     for mode in ("0", "1"):
         monkeypatch.setenv("RCMDYN_NEGFIX_MODE", mode)
