@@ -32,6 +32,7 @@
 #include "slice.hpp"
 #include "bdyin.hpp"
 #include "tke.hpp"
+#include "fieldtab.hpp"
 
 using namespace rcm;
 
@@ -1046,114 +1047,119 @@ struct rcmdyn_engine {
     return nullptr;
   }
 
-  // public field id -> (pointer, levels)
-  static int atms_levels(int q, int kz) {
-    const int f = RCMDYN_ATMS_UBX3D + q;
-    if (f == RCMDYN_ATMS_PF3D || f == RCMDYN_ATMS_WB3D || f == RCMDYN_ATMS_ZQ) return kz + 1;
-    if (f == RCMDYN_ATMS_PS2D || f == RCMDYN_ATMS_RHOX2D) return 1;
-    return kz;
-  }
-  double* field_ptr(Tile& t, int f, int& nk) {
-    nk = cfg.kz;
-    const int c = t.cur;
-    if (f >= RCMDYN_TPHY && f <= RCMDYN_WPHY) {
-      if (f == RCMDYN_WPHY) nk = cfg.kz + 1;
-      return t.phy[f - RCMDYN_TPHY];
-    }
-    if (f >= RCMDYN_ATMS_UBX3D && f <= RCMDYN_ATMS_RHB3D) {
-      nk = atms_levels(f - RCMDYN_ATMS_UBX3D, cfg.kz);
-      return t.atms[f - RCMDYN_ATMS_UBX3D];
-    }
-    if (f >= RCMDYN_XUB_B1 && f <= RCMDYN_XWWB_B1) {
-      if (f == RCMDYN_XPSB_B1) nk = 1;
-      if (f == RCMDYN_XWWB_B1) nk = cfg.kz + 1;
-      return t.bin[f - RCMDYN_XUB_B1];
-    }
-    if (f == RCMDYN_ATM0_PSDOT) { nk = 1; return t.psdot0; }
-    if (f >= RCMDYN_ATM1_TKE && f <= RCMDYN_TKEPHY) {
-      nk = cfg.kz + 1;
-      return f == RCMDYN_ATM1_TKE ? t.a1tke : f == RCMDYN_ATM2_TKE ? t.a2tke : t.tkephy;
-    }
-    if (f == RCMDYN_KPBL) { nk = 1; return t.kpbl; }
-    if (f >= RCMDYN_ATM1_QI && f <= RCMDYN_ATMS_QXB3D_QS) {      // nqx = 5 only
-      if (hc.nsp == 0) return nullptr;
-      if (f <= RCMDYN_ATM1_QS) return t.a1qx[f - RCMDYN_ATM1_QI][c];
-      if (f <= RCMDYN_ATM2_QS) return t.a2qx[f - RCMDYN_ATM2_QI][c];
-      if (f <= RCMDYN_QSPHY) return t.phyx[f - RCMDYN_QIPHY];
-      return t.atmsx[f - RCMDYN_ATMS_QXB3D_QI];
-    }
-    if (f >= RCMDYN_ATM1_PP && f <= RCMDYN_CRY) {
-      if (cfg.idynamic != 2) return nullptr;
-      NHFields& h = nhf[&t - tiles.data()];
-      auto cst = [](const double* p) { return const_cast<double*>(p); };
-      switch (f) {
-        case RCMDYN_ATM1_PP: return h.a1pp;  case RCMDYN_ATM2_PP: return h.a2pp;
-        case RCMDYN_XPPB_B0: return cst(h.ppb0); case RCMDYN_XPPB_BT: return cst(h.ppbt);
-        case RCMDYN_ATM0_PR: return cst(h.pr0); case RCMDYN_ATM0_T: return cst(h.t0);
-        case RCMDYN_ATM0_RHO: return cst(h.rho0); case RCMDYN_ATM0_Z: return cst(h.z0);
-        case RCMDYN_DPRDDX: return cst(h.dprddx); case RCMDYN_DPRDDY: return cst(h.dprddy);
-        default: break;
-      }
-      nk = cfg.kz + 1;
-      switch (f) {
-        case RCMDYN_ATM1_W: return h.a1w;  case RCMDYN_ATM2_W: return h.a2w;
-        case RCMDYN_XWWB_B0: return cst(h.wwb0); case RCMDYN_XWWB_BT: return cst(h.wwbt);
-        case RCMDYN_ATM0_PF: return cst(h.pf0); case RCMDYN_ATM0_RHOF: return cst(h.rhof0);
-        case RCMDYN_ATM0_ZF: return cst(h.zf0);
-        default: break;
-      }
-      nk = 1;
-      switch (f) {
-        case RCMDYN_ATM0_PS: return cst(h.ps0);
-        case RCMDYN_DPSDXM: return cst(h.dpsdxm); case RCMDYN_DPSDYM: return cst(h.dpsdym);
-        case RCMDYN_EF: return cst(h.ef); case RCMDYN_DDX: return cst(h.ddx); case RCMDYN_DDY: return cst(h.ddy);
-        case RCMDYN_DMDX: return cst(h.dmdx); case RCMDYN_DMDY: return cst(h.dmdy);
-        case RCMDYN_EX: return cst(h.ex); case RCMDYN_CRX: return cst(h.crx); case RCMDYN_CRY: return cst(h.cry);
-        default: return nullptr;
-      }
-    }
+  // public field id -> buffer on tile t, null where this engine holds none (an NH or nqx = 5
+  // field on an engine without that option, a lazily allocated one before its event); the
+  // attributes of the field are its row of fieldtab::TAB.  Every enumerator is named and there
+  // is no default, so -Wswitch reports an id without a buffer.
+  double* field_ptr(Tile& t, int id) {
+    const fieldtab::Row* r = fieldtab::row(id);
+    if (!r || !holds(r->need)) return nullptr;
+    const rcmdyn_field f = r->id;
+    auto nh = [&]() -> NHFields& { return nhf[&t - tiles.data()]; };
+    auto cst = [](const double* p) { return const_cast<double*>(p); };
     switch (f) {
-      case RCMDYN_ATM1_U: return t.a1u[c]; case RCMDYN_ATM1_V: return t.a1v[c];
-      case RCMDYN_ATM1_T: return t.a1t[thp(t)]; case RCMDYN_ATM1_QV: return t.a1qv[thp(t)];
-      case RCMDYN_ATM1_QC: return t.a1qc[thp(t)];
-      case RCMDYN_ATM2_U: return t.a2u[c]; case RCMDYN_ATM2_V: return t.a2v[c];
-      case RCMDYN_ATM2_T: return t.a2t[thp(t)]; case RCMDYN_ATM2_QV: return t.a2qv[thp(t)];
-      case RCMDYN_ATM2_QC: return t.a2qc[thp(t)];
-      case RCMDYN_XUB_B0: return t.ub0; case RCMDYN_XUB_BT: return t.ubt;
-      case RCMDYN_XVB_B0: return t.vb0; case RCMDYN_XVB_BT: return t.vbt;
-      case RCMDYN_XTB_B0: return t.tb0; case RCMDYN_XTB_BT: return t.tbt;
-      case RCMDYN_XQB_B0: return t.qb0; case RCMDYN_XQB_BT: return t.qbt;
-      case RCMDYN_TTEN: return t.tten; case RCMDYN_UTEN: return t.uten; case RCMDYN_VTEN: return t.vten;
-      case RCMDYN_QVTEN: return t.qvten; case RCMDYN_QCTEN: return t.qcten;
-      case RCMDYN_OMEGA: return t.omega; case RCMDYN_XKC: return t.xkcs; case RCMDYN_PHI: return t.phi;
-      case RCMDYN_QDOT: nk = cfg.kz + 1; return t.qdot;
-      case RCMDYN_DSTOR: nk = cfg.nsplit; return t.dstor;
-      case RCMDYN_HSTOR: nk = cfg.nsplit; return t.hstor;
-      default: break;
-    }
-    nk = 1;
-    switch (f) {
-      case RCMDYN_PSA: return t.psa_[c]; case RCMDYN_PSB: return t.psb_[c];
-      case RCMDYN_MSFX: return t.msfx; case RCMDYN_MSFD: return t.msfd;
-      case RCMDYN_CORIOL: return t.coriol; case RCMDYN_HT: return t.ht;
-      case RCMDYN_XPSB_B0: return t.pb0; case RCMDYN_XPSB_BT: return t.pbt;
+      case RCMDYN_ATM1_U: return fptr(t, FK::A1U); case RCMDYN_ATM1_V: return fptr(t, FK::A1V);
+      case RCMDYN_ATM1_T: return fptr(t, FK::A1T); case RCMDYN_ATM1_QV: return fptr(t, FK::A1QV);
+      case RCMDYN_ATM1_QC: return fptr(t, FK::A1QC);
+      case RCMDYN_ATM2_U: return fptr(t, FK::A2U); case RCMDYN_ATM2_V: return fptr(t, FK::A2V);
+      case RCMDYN_ATM2_T: return fptr(t, FK::A2T); case RCMDYN_ATM2_QV: return fptr(t, FK::A2QV);
+      case RCMDYN_ATM2_QC: return fptr(t, FK::A2QC);
+      case RCMDYN_PSA: return fptr(t, FK::PSA); case RCMDYN_PSB: return fptr(t, FK::PSB);
+      case RCMDYN_DSTOR: return fptr(t, FK::DSTOR); case RCMDYN_HSTOR: return fptr(t, FK::HSTOR);
+      case RCMDYN_MSFX: return fptr(t, FK::MSFX); case RCMDYN_MSFD: return fptr(t, FK::MSFD);
+      case RCMDYN_CORIOL: return fptr(t, FK::CORIOL); case RCMDYN_HT: return fptr(t, FK::HT);
+      case RCMDYN_XUB_B0: return fptr(t, FK::UB0); case RCMDYN_XUB_BT: return fptr(t, FK::UBT);
+      case RCMDYN_XVB_B0: return fptr(t, FK::VB0); case RCMDYN_XVB_BT: return fptr(t, FK::VBT);
+      case RCMDYN_XTB_B0: return fptr(t, FK::TB0); case RCMDYN_XTB_BT: return fptr(t, FK::TBT);
+      case RCMDYN_XQB_B0: return fptr(t, FK::QB0); case RCMDYN_XQB_BT: return fptr(t, FK::QBT);
+      case RCMDYN_XPSB_B0: return fptr(t, FK::PB0); case RCMDYN_XPSB_BT: return fptr(t, FK::PBT);
       case RCMDYN_PSC: return t.psc; case RCMDYN_PTEN: return t.pten + t.g.plane;
-      case RCMDYN_PSDOTA: return t.psdota;
-      default: return nullptr;
+      case RCMDYN_PSDOTA: return fptr(t, FK::PSDOTA);
+      case RCMDYN_TTEN: return t.tten; case RCMDYN_UTEN: return t.uten; case RCMDYN_VTEN: return t.vten;
+      case RCMDYN_QVTEN: return t.qvten; case RCMDYN_QCTEN: return t.qcten; case RCMDYN_OMEGA: return t.omega;
+      case RCMDYN_QDOT: return fptr(t, FK::QDOT); case RCMDYN_XKC: return t.xkcs; case RCMDYN_PHI: return fptr(t, FK::PHI);
+      case RCMDYN_ATM1_PP: return fptr(t, FK::A1PP); case RCMDYN_ATM2_PP: return fptr(t, FK::A2PP);
+      case RCMDYN_ATM1_W: return fptr(t, FK::A1W); case RCMDYN_ATM2_W: return fptr(t, FK::A2W);
+      case RCMDYN_XPPB_B0: return cst(nh().ppb0); case RCMDYN_XPPB_BT: return cst(nh().ppbt);
+      case RCMDYN_XWWB_B0: return cst(nh().wwb0); case RCMDYN_XWWB_BT: return cst(nh().wwbt);
+      case RCMDYN_ATM0_PS: return cst(nh().ps0); case RCMDYN_ATM0_PR: return cst(nh().pr0);
+      case RCMDYN_ATM0_T: return cst(nh().t0); case RCMDYN_ATM0_RHO: return cst(nh().rho0);
+      case RCMDYN_ATM0_Z: return cst(nh().z0); case RCMDYN_ATM0_PF: return cst(nh().pf0);
+      case RCMDYN_ATM0_RHOF: return cst(nh().rhof0); case RCMDYN_ATM0_ZF: return cst(nh().zf0);
+      case RCMDYN_DPSDXM: return cst(nh().dpsdxm); case RCMDYN_DPSDYM: return cst(nh().dpsdym);
+      case RCMDYN_DPRDDX: return cst(nh().dprddx); case RCMDYN_DPRDDY: return cst(nh().dprddy);
+      case RCMDYN_EF: return cst(nh().ef); case RCMDYN_DDX: return cst(nh().ddx); case RCMDYN_DDY: return cst(nh().ddy);
+      case RCMDYN_DMDX: return cst(nh().dmdx); case RCMDYN_DMDY: return cst(nh().dmdy);
+      case RCMDYN_EX: return cst(nh().ex); case RCMDYN_CRX: return cst(nh().crx); case RCMDYN_CRY: return cst(nh().cry);
+      case RCMDYN_TPHY: case RCMDYN_QVPHY: case RCMDYN_QCPHY: case RCMDYN_UPHY: case RCMDYN_VPHY:
+      case RCMDYN_PPPHY: case RCMDYN_WPHY:
+        return t.phy[f - RCMDYN_TPHY];
+      case RCMDYN_ATMS_UBX3D: case RCMDYN_ATMS_VBX3D: case RCMDYN_ATMS_UBD3D: case RCMDYN_ATMS_VBD3D:
+      case RCMDYN_ATMS_TB3D: case RCMDYN_ATMS_QVB3D: case RCMDYN_ATMS_QCB3D: case RCMDYN_ATMS_TV3D:
+      case RCMDYN_ATMS_PB3D: case RCMDYN_ATMS_PF3D: case RCMDYN_ATMS_PS2D: case RCMDYN_ATMS_RHOX2D:
+      case RCMDYN_ATMS_TH3D: case RCMDYN_ATMS_RHOB3D: case RCMDYN_ATMS_TP3D: case RCMDYN_ATMS_WPX3D:
+      case RCMDYN_ATMS_WB3D: case RCMDYN_ATMS_ZQ: case RCMDYN_ATMS_ZA: case RCMDYN_ATMS_DZQ:
+      case RCMDYN_ATMS_QSB3D: case RCMDYN_ATMS_RHB3D:
+        return t.atms[f - RCMDYN_ATMS_UBX3D];
+      case RCMDYN_XUB_B1: case RCMDYN_XVB_B1: case RCMDYN_XTB_B1: case RCMDYN_XQB_B1: case RCMDYN_XPSB_B1:
+      case RCMDYN_XPPB_B1: case RCMDYN_XWWB_B1:
+        return t.bin[f - RCMDYN_XUB_B1];
+      case RCMDYN_ATM0_PSDOT: return t.psdot0;
+      case RCMDYN_ATM1_TKE: return fptr(t, FK::A1TKE); case RCMDYN_ATM2_TKE: return fptr(t, FK::A2TKE);
+      case RCMDYN_TKEPHY: return t.tkephy; case RCMDYN_KPBL: return fptr(t, FK::KPBL);
+      case RCMDYN_ATM1_QI: case RCMDYN_ATM1_QR: case RCMDYN_ATM1_QS: return fptr(t, fkq(FK::A1QX0, f - RCMDYN_ATM1_QI));
+      case RCMDYN_ATM2_QI: case RCMDYN_ATM2_QR: case RCMDYN_ATM2_QS: return fptr(t, fkq(FK::A2QX0, f - RCMDYN_ATM2_QI));
+      case RCMDYN_QIPHY: case RCMDYN_QRPHY: case RCMDYN_QSPHY: return t.phyx[f - RCMDYN_QIPHY];
+      case RCMDYN_ATMS_QXB3D_QI: case RCMDYN_ATMS_QXB3D_QR: case RCMDYN_ATMS_QXB3D_QS:
+        return t.atmsx[f - RCMDYN_ATMS_QXB3D_QI];
+      case RCMDYN_NFIELDS: break;
     }
+    return nullptr;
   }
+  // whether an engine of this configuration keeps a buffer for a field with this need
+  bool holds(fieldtab::Need n) const {
+    return !(n == fieldtab::NH && cfg.idynamic != 2) && !(n == fieldtab::NQX5 && hc.nsp == 0);
+  }
+  int field_levels(int f) const { return fieldtab::levels(fieldtab::TAB[f].lev, cfg.kz, cfg.nsplit); }
+  size_t field_size(const Tile& t, int f) const { return t.g.plane * (size_t)field_levels(f); }
+  // why an engine of this configuration refuses a field with this need, null when it does not
+  const char* lacks(fieldtab::Need n) const {
+    const bool nh = cfg.idynamic == 2;
+    switch (n) {
+      case fieldtab::ANY: break;
+      case fieldtab::NH: return nh ? nullptr : "non-hydrostatic field on a hydrostatic engine";
+      case fieldtab::HYD_PS: return nh ? "the non-hydrostatic core reads no ps record (p* is atm0%ps)" : nullptr;
+      case fieldtab::HYD_Z: return nh ? "zq/za/dzq are not computed by mkslice for idynamic=2" : nullptr;
+      case fieldtab::NQX5: return hc.nsp ? nullptr : "qi/qr/qs fields need nqx = 5 (ipptls = 2)";
+      case fieldtab::UW: return cfg.ibltyp == 2 ? nullptr : "TKE/kpbl fields need ibltyp=2 (UW PBL)";
+    }
+    return nullptr;
+  }
+  // whether the buffers of a lazily allocated group exist (DIAG: are being written)
+  bool have(fieldtab::Lazy g) const {
+    if (tiles.empty()) return true;
+    const Tile& t = tiles[0];
+    switch (g) {
+      case fieldtab::NONE: break;
+      case fieldtab::PHYSICS: return t.phy[0];
+      case fieldtab::BDYIN: return t.bin[0];
+      case fieldtab::TKEPHY: return t.tkephy;
+      case fieldtab::SLICE: return t.atms[0];
+      case fieldtab::DIAG: return diag;
+    }
+    return true;
+  }
+  // what a get says of a group that does not exist yet (the bdyin record: 'unknown field')
+  static constexpr const char* WAITS_FOR[] = {
+      nullptr, "no physics tendencies were put", nullptr, "no TKE tendency was put",
+      "no slice fields yet (rcmdyn_tend_pre_physics)", "tendency diagnostics are off (rcmdyn_set_diagnostics)"};
+  static_assert(fieldtab::DIAG == 5 && sizeof(WAITS_FOR) / sizeof(WAITS_FOR[0]) == 6, "one text per fieldtab::Lazy");
 
   void put(int f, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
     settle();
-    const bool qxf = f >= RCMDYN_ATM1_QI && f <= RCMDYN_QSPHY;
-    const bool phyf = (f >= RCMDYN_TPHY && f <= RCMDYN_WPHY) || (f >= RCMDYN_QIPHY && f <= RCMDYN_QSPHY);
-    const bool binf = f >= RCMDYN_XUB_B1 && f <= RCMDYN_ATM0_PSDOT;
-    const bool tkef = (f >= RCMDYN_ATM1_TKE && f <= RCMDYN_TKEPHY) || f == RCMDYN_KPBL;
-    if (f < 0 || f >= RCMDYN_NFIELDS || (f > RCMDYN_XPSB_BT && f < RCMDYN_ATM1_PP) ||
-        (f > RCMDYN_CRY && !phyf && !binf && !tkef && !qxf))
-      throw std::runtime_error("rcmdyn_put: field is read-only or unknown");
-    if (qxf && hc.nsp == 0) throw std::runtime_error("rcmdyn_put: qi/qr/qs fields need nqx = 5 (ipptls = 2)");
-    if (tkef && cfg.ibltyp != 2) throw std::runtime_error("rcmdyn_put: TKE/kpbl fields need ibltyp=2 (UW PBL)");
+    const fieldtab::Row* r = fieldtab::row(f);
+    if (!r || r->acc == fieldtab::RO) throw std::runtime_error("rcmdyn_put: field is read-only or unknown");
+    if (const char* m = lacks(r->need)) throw std::runtime_error(std::string("rcmdyn_put: ") + m);
     if (f == RCMDYN_KPBL) {
       // vadv4d ind = 3 stops on a PBL top above the model (Main/mod_advection.F90:923-925)
       const size_t n = (size_t)(j2 - j1 + 1) * (i2 - i1 + 1) * std::max(1, k2 - k1 + 1);
@@ -1162,23 +1168,13 @@ struct rcmdyn_engine {
         if (src[q] != std::floor(src[q])) throw std::runtime_error("rcmdyn_put: kpbl must hold integers");
       }
     }
-    if (f == RCMDYN_TKEPHY && !tiles.empty() && !tiles[0].tkephy) {
-      HIPCHK(hipStreamSynchronize(stream));
-      for (auto& t : tiles) t.tkephy = dalloc(t, t.g.plane * (cfg.kz + 1));
-      invalidate_graphs();
-    }
-    if (((f >= RCMDYN_ATM1_PP && f <= RCMDYN_CRY) || f == RCMDYN_PPPHY || f == RCMDYN_WPHY ||
-         f == RCMDYN_XPPB_B1 || f == RCMDYN_XWWB_B1 || f == RCMDYN_ATM0_PSDOT) && cfg.idynamic != 2)
-      throw std::runtime_error("rcmdyn_put: non-hydrostatic field on a hydrostatic engine");
-    if (f == RCMDYN_XPSB_B1 && cfg.idynamic == 2)
-      throw std::runtime_error("rcmdyn_put: the non-hydrostatic core reads no ps record (p* is atm0%ps)");
-    if (phyf) enable_physics();
-    if (binf) enable_bdyin();
+    if (!have(r->lazy)) enable(r->lazy);
     HIPCHK(hipStreamSynchronize(stream));
     const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const int nk = field_levels(f);
     for (auto& t : tiles) {
-      int nk;
-      double* d = field_ptr(t, f, nk);
+      double* d = field_ptr(t, f);
+      if (!d) throw std::runtime_error("rcmdyn_put: unknown field");
       const Geom& g = t.g;
       std::vector<double> h((size_t)nk * g.plane);
       HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
@@ -1196,46 +1192,37 @@ struct rcmdyn_engine {
         }
       HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
     }
-    if (f >= RCMDYN_MSFX && f <= RCMDYN_HT) statics_dirty = true;
-    if ((f >= RCMDYN_XUB_B0 && f <= RCMDYN_XPSB_BT) || (f >= RCMDYN_XPPB_B0 && f <= RCMDYN_XWWB_BT)) bdy_dirty = true;
-    // only the hydrostatic vadv4d ind = 3 (k_scalars, k_qx_tend) reads kpbl on the ghost ring;
-    // the NH kernels read it at their own point
-    if (f == RCMDYN_KPBL && hc.iqxvadv == 3 && cfg.idynamic != 2) kpbl_dirty = true;
     ghosts_stale = true;
-    if (f >= RCMDYN_ATM0_PS && f <= RCMDYN_CRY) invalidate_graphs();
-    if (f == RCMDYN_DPRDDX || f == RCMDYN_DPRDDY) dprd_any = true;
-    if (f == RCMDYN_DPRDDX || f == RCMDYN_DPRDDY || (dprd_any && f == RCMDYN_ATM0_PR)) dprd_put = true;
-  }
-
-  // physics coupling seam: the pc_physic buffers exist from the first put of one of them on
-  // (zero-filled), and every later tend adds them; the captured graphs held null pointers
-  void enable_physics() {
-    if (tiles.empty() || tiles[0].phy[0]) return;
-    HIPCHK(hipStreamSynchronize(stream));
-    for (auto& t : tiles) {
-      const size_t P = t.g.plane;
-      for (int q = 0; q < 5; q++) t.phy[q] = dalloc(t, P * cfg.kz);
-      if (cfg.idynamic == 2) { t.phy[5] = dalloc(t, P * cfg.kz); t.phy[6] = dalloc(t, P * (cfg.kz + 1)); }
-      for (int n = 0; n < hc.nsp; n++) t.phyx[n] = dalloc(t, P * cfg.kz);
+    switch (r->after) {
+      case fieldtab::NOTHING: break;
+      case fieldtab::STATICS: statics_dirty = true; break;
+      case fieldtab::BDY: bdy_dirty = true; break;
+      // only the hydrostatic vadv4d ind = 3 (k_scalars, k_qx_tend) reads kpbl on the ghost ring;
+      // the NH kernels read it at their own point
+      case fieldtab::KPBL_RING: if (hc.iqxvadv == 3 && cfg.idynamic != 2) kpbl_dirty = true; break;
+      case fieldtab::DPRD: dprd_any = dprd_put = true; invalidate_graphs(); break;
+      case fieldtab::PR0: if (dprd_any) dprd_put = true; invalidate_graphs(); break;
+      case fieldtab::GRAPHS: invalidate_graphs(); break;
     }
-    invalidate_graphs();
   }
 
-  // device bdyin buffers (raw record, coupled b1; NH atm0%psdot), zero-filled
-  void enable_bdyin() {
-    if (tiles.empty() || tiles[0].bin[0]) return;
+  // The zero-filled buffers of a group that exists from the first put of one of its fields on,
+  // for the fields this configuration offers.  PHYSICS: the pc_physic seam, which every later
+  // tend adds; TKEPHY: the UW scheme's tendency; the captured graphs held null pointers for
+  // both.  BDYIN: the raw ICBC record and NH atm0%psdot, with the coupled b1 (bb1) beside it.
+  void enable(fieldtab::Lazy g) {
     HIPCHK(hipStreamSynchronize(stream));
-    const bool nh = cfg.idynamic == 2;
-    for (auto& t : tiles) {
-      const size_t P = t.g.plane, P3 = P * cfg.kz, P4 = P * (cfg.kz + 1);
-      for (int q = 0; q < 4; q++) { t.bin[q] = dalloc(t, P3); t.bb1[q] = dalloc(t, P3); }
-      t.bin[4] = dalloc(t, P); t.bb1[4] = dalloc(t, P);
-      if (nh) {
-        t.bin[5] = dalloc(t, P3); t.bb1[5] = dalloc(t, P3);
-        t.bin[6] = dalloc(t, P4); t.bb1[6] = dalloc(t, P4);
-        t.psdot0 = dalloc(t, P);
+    for (auto& t : tiles)
+      for (const fieldtab::Row& r : fieldtab::TAB) {
+        if (r.lazy != g || !holds(r.need)) continue;
+        const rcmdyn_field f = r.id;
+        double* d = dalloc(t, field_size(t, f));
+        if (g == fieldtab::PHYSICS) (f < RCMDYN_QIPHY ? t.phy[f - RCMDYN_TPHY] : t.phyx[f - RCMDYN_QIPHY]) = d;
+        else if (g == fieldtab::TKEPHY) t.tkephy = d;
+        else if (f == RCMDYN_ATM0_PSDOT) t.psdot0 = d;
+        else { t.bin[f - RCMDYN_XUB_B1] = d; t.bb1[f - RCMDYN_XUB_B1] = dalloc(t, field_size(t, f)); }
       }
-    }
+    if (g != fieldtab::BDYIN) invalidate_graphs();
   }
 
   // mod_bdycod::bdyin from read_icbc on (bdyin.hip)
@@ -1283,8 +1270,8 @@ struct rcmdyn_engine {
   void run_slice() {
     for (auto& t : tiles) {
       if (t.atms[0]) continue;
-      for (int q = 0; q < 22; q++) t.atms[q] = dalloc(t, t.g.plane * (size_t)atms_levels(q, cfg.kz));
-      for (int n = 0; n < hc.nsp; n++) t.atmsx[n] = dalloc(t, t.g.plane * (size_t)cfg.kz);
+      for (int q = 0; q < fieldtab::NATMS; q++) t.atms[q] = dalloc(t, field_size(t, RCMDYN_ATMS_UBX3D + q));
+      for (int n = 0; n < hc.nsp; n++) t.atmsx[n] = dalloc(t, field_size(t, RCMDYN_ATMS_QXB3D_QI + n));
     }
     each([&](Tile& t) {
       const Geom& g = t.g;
@@ -1311,33 +1298,23 @@ struct rcmdyn_engine {
 
   void get(int f, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
     settle();
-    if (!diag && (f == RCMDYN_TTEN || f == RCMDYN_UTEN || f == RCMDYN_VTEN || f == RCMDYN_QVTEN ||
-                  f == RCMDYN_QCTEN || f == RCMDYN_OMEGA || f == RCMDYN_XKC))
-      throw std::runtime_error("rcmdyn_get: tendency diagnostics are off (rcmdyn_set_diagnostics)");
-    if (f >= RCMDYN_ATMS_UBX3D && f <= RCMDYN_ATMS_RHB3D) {
-      if (!tiles[0].atms[0]) throw std::runtime_error("rcmdyn_get: no slice fields yet (rcmdyn_tend_pre_physics)");
-      if (cfg.idynamic == 2 && (f == RCMDYN_ATMS_ZQ || f == RCMDYN_ATMS_ZA || f == RCMDYN_ATMS_DZQ))
-        throw std::runtime_error("rcmdyn_get: zq/za/dzq are not computed by mkslice for idynamic=2");
+    // A get names the option (nqx = 5, ibltyp = 2) or the event (the group's first put, the
+    // slice, the diagnostics switch) a field waits for, then what the NH slice leaves out.  It
+    // does not test NH and HYD_PS: a buffer this engine does not hold, the bdyin record before
+    // its first put among them, is an 'unknown field' below, and XPSB_B1 reads as it was stored.
+    if (const fieldtab::Row* r = fieldtab::row(f)) {
+      const char* m = r->need == fieldtab::NQX5 || r->need == fieldtab::UW ? lacks(r->need) : nullptr;
+      if (!m && !have(r->lazy)) m = WAITS_FOR[r->lazy];
+      if (!m && r->need == fieldtab::HYD_Z) m = lacks(r->need);
+      if (m) throw std::runtime_error(std::string("rcmdyn_get: ") + m);
     }
-    if (f >= RCMDYN_TPHY && f <= RCMDYN_WPHY && !tiles[0].phy[0])
-      throw std::runtime_error("rcmdyn_get: no physics tendencies were put");
-    if (f >= RCMDYN_ATM1_QI && f <= RCMDYN_ATMS_QXB3D_QS) {
-      if (hc.nsp == 0) throw std::runtime_error("rcmdyn_get: qi/qr/qs fields need nqx = 5 (ipptls = 2)");
-      if (f >= RCMDYN_QIPHY && f <= RCMDYN_QSPHY && !tiles[0].phyx[0])
-        throw std::runtime_error("rcmdyn_get: no physics tendencies were put");
-      if (f >= RCMDYN_ATMS_QXB3D_QI && !tiles[0].atmsx[0])
-        throw std::runtime_error("rcmdyn_get: no slice fields yet (rcmdyn_tend_pre_physics)");
-    }
-    if (((f >= RCMDYN_ATM1_TKE && f <= RCMDYN_TKEPHY) || f == RCMDYN_KPBL) && cfg.ibltyp != 2)
-      throw std::runtime_error("rcmdyn_get: TKE/kpbl fields need ibltyp=2 (UW PBL)");
-    if (f == RCMDYN_TKEPHY && !tiles[0].tkephy) throw std::runtime_error("rcmdyn_get: no TKE tendency was put");
     HIPCHK(hipStreamSynchronize(stream));
     check_now();
     const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
     for (auto& t : tiles) {
-      int nk;
-      double* d = field_ptr(t, f, nk);
+      double* d = field_ptr(t, f);
       if (!d) throw std::runtime_error("rcmdyn_get: unknown field");
+      const int nk = field_levels(f);
       const Geom& g = t.g;
       std::vector<double> h((size_t)nk * g.plane);
       HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
