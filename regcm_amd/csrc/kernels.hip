@@ -60,11 +60,7 @@ __global__ void k_surface_pressures(Geom g, Fields f) {
   surface_pressures_at(g, f, j, i);
 }
 
-// generic relaxation contribution (nudge*, Main/mod_bdycod.F90:4262-4263)
-__device__ __forceinline__ double relax(double ften, double xf, double xg, double f0, double f1, double f2,
-                                        double f3, double f4) {
-  return ften + xf * f0 - xg * (f1 + f2 + f3 + f4 - d_four * f0);
-}
+// the nudging coefficients of band line ib at level k (relax, pointops.hpp)
 __device__ __forceinline__ void nudge_coef(const Consts* c, int ib, int k, double& xf, double& xg) {
   if (c->iboudy == 1) { xf = c->fcx[ib]; xg = c->gcx[ib]; }
   else { xf = c->hefc[ib][k]; xg = c->hegc[ib][k]; }
@@ -420,30 +416,11 @@ template __global__ __launch_bounds__(COLT, COL_LB) void k_columns<true>(Geom, c
 // block instead of dependent per-operand rounds, and one division per staged point instead
 // of 13 per output.  Points outside jdi x idi keep their values (copied by k_qfilter).
 // decoupled boundary ud/vd of decouple with the inflow/outflow rule of iboudy = 3/4
-// (Main/mod_tendency.F90:893-994): an outflow boundary point takes the adjacent interior
-// value.  W/E run on the idi columns first, then S/N on the full jde rows, so a corner row
-// point copies the (possibly already replaced) W/E value.  The slice values the reference
-// multiplies (wui, wue, ...) equal atm1 there (bdyuv), so the default is atm1 * rpsda.
+// (udvd_rule, pointops.hpp) at the level of byte offset kof
 __device__ double2 udvd_bdy(const Geom& g, const Fields& f, int j, int i, uint32_t kof) {
-  auto base = [&](int jj, int ii) {
-    const uint32_t q2 = g.o2(jj, ii);
-    const double r = LD(f.rpsda, q2);
-    return make_double2(LD(f.a1u, q2 + kof) * r, LD(f.a1v, q2 + kof) * r);
-  };
-  // global boundary lines (a ghost point on them carries the value its owner computes and
-  // the reference exchanges)
-  auto we = [&](int jj, int ii) {
-    if (in(ii, 2, g.giy - 1)) {
-      if (g.gjeq(jj, 1) && LD(f.a1u, g.o2(jj, ii) + kof) <= d_zero) return base(2, ii);
-      if (g.gjeq(jj, g.gjx) && LD(f.a1u, g.o2(jj, ii) + kof) >= d_zero) return base(g.gjx - 1, ii);
-    }
-    return base(jj, ii);
-  };
-  if (g.band || in(j, 1, g.gjx)) {
-    if (i == 1 && LD(f.a1v, g.o2(j, i) + kof) >= d_zero) return we(j, 2);
-    if (i == g.giy && LD(f.a1v, g.o2(j, i) + kof) <= d_zero) return we(j, g.giy - 1);
-  }
-  return we(j, i);
+  return udvd_rule(g, j, i, [&](int jj, int ii) { return LD(f.a1u, g.o2(jj, ii) + kof); },
+                   [&](int jj, int ii) { return LD(f.a1v, g.o2(jj, ii) + kof); },
+                   [&](int jj, int ii) { return LD(f.rpsda, g.o2(jj, ii)); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -796,8 +773,8 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
     double xf, xg;
     const int ib = f.ibdt[o2 >> 3];
     if (c->iboudy == 1) { xf = c->fcx[ib]; xg = c->gcx[ib]; } else { xf = c->hefc[ib][k]; xg = c->hegc[ib][k]; }
-#define FGU(dj, di) ((LD(f.ub0, O3(dj, di)) + xt * LD(f.ubt, O3(dj, di))) - LD(f.a2u, O3(dj, di)))
-#define FGV(dj, di) ((LD(f.vb0, O3(dj, di)) + xt * LD(f.vbt, O3(dj, di))) - LD(f.a2v, O3(dj, di)))
+#define FGU(dj, di) bdy_minus_state(LD(f.ub0, O3(dj, di)), LD(f.ubt, O3(dj, di)), LD(f.a2u, O3(dj, di)), xt)
+#define FGV(dj, di) bdy_minus_state(LD(f.vb0, O3(dj, di)), LD(f.vbt, O3(dj, di)), LD(f.a2v, O3(dj, di)), xt)
     ut = relax(ut, xf, xg, FGU(0, 0), FGU(-1, 0), FGU(1, 0), FGU(0, -1), FGU(0, 1));
     vt = relax(vt, xf, xg, FGV(0, 0), FGV(-1, 0), FGV(1, 0), FGV(0, -1), FGV(0, 1));
 #undef FGU
@@ -937,36 +914,6 @@ __global__ void k_diffu6(Geom g, const Consts* __restrict__ c, Fields f, QxArgs 
   F3(q == 1 ? f.d6t : (q == 2 ? f.d6qv : (q == 3 ? f.d6qc : qx.d6[q - 4])), j, i, k) =
       xkc * diffu6_bracket(j, i, g.gjx - 1, g.giy - 1, fv, lv);
 }
-
-// diffu_x (idiffu = 1) at one point from a halo-2 LDS tile, Main/mod_diffusion.F90:673-713
-#define H2T(S, dj, di) S[a2 + (di)][b2 + (dj)]
-#define DIFFU_X(ften, S, D6)                                                                      \
-  do {                                                                                            \
-    if (c->idiffu == 3) {                   /* the column term of k_diffu6 */                     \
-      if (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) ften = ften + LD(D6, o3);                    \
-      break;                                                                                      \
-    }                                                                                             \
-    if (c->idiffu == 2) {                   /* 9-point scheme, :726-735, 881-891 */               \
-      ften = ften + d_one * xkcs *                                                                \
-          (o4_c1 * (H2T(S, 1, 0) + H2T(S, -1, 0) + H2T(S, 0, 1) + H2T(S, 0, -1)) +                \
-           o4_c2 * (H2T(S, 1, 1) + H2T(S, -1, -1) + H2T(S, -1, 1) + H2T(S, 1, -1)) +              \
-           o4_c3 * H2T(S, 0, 0));                                                                 \
-      break;                                                                                      \
-    }                                                                                             \
-    if (g.gcii(j, i))                                                                             \
-      ften = ften - d_one * xkcs *                                                                \
-          (z4_c1 * (H2T(S, 2, 0) + H2T(S, -2, 0) + H2T(S, 0, 2) + H2T(S, 0, -2)) +                \
-           z4_c2 * (H2T(S, 1, 0) + H2T(S, -1, 0) + H2T(S, 0, 1) + H2T(S, 0, -1)) +                \
-           z4_c3 * H2T(S, 0, 0));                                                                 \
-    if (g.gjeq(j, 2)) ften = ften + d_one * xkcs * (z4_c1 * (H2T(S, 1, 0) + H2T(S, -1, 0) + \
-        H2T(S, 0, 1) + H2T(S, 0, -1)) + z4_c2 * H2T(S, 0, 0));                                   \
-    if (g.gjeq(j, g.gjx - 2)) ften = ften + d_one * xkcs * (z4_c1 * (H2T(S, 1, 0) + H2T(S, -1, 0) + \
-        H2T(S, 0, 1) + H2T(S, 0, -1)) + z4_c2 * H2T(S, 0, 0));                                   \
-    if (i == 2) ften = ften + d_one * xkcs * (z4_c1 * (H2T(S, 1, 0) + H2T(S, -1, 0) + \
-        H2T(S, 0, 1) + H2T(S, 0, -1)) + z4_c2 * H2T(S, 0, 0));                                   \
-    if (i == g.giy - 2) ften = ften + d_one * xkcs * (z4_c1 * (H2T(S, 1, 0) + H2T(S, -1, 0) + \
-        H2T(S, 0, 1) + H2T(S, 0, -1)) + z4_c2 * H2T(S, 0, 0));                                   \
-  } while (0)
 
 // qfuse, k_scalars at an owned point: k_qfilter's work for one moisture forecast fq (n = 0 qv,
 // 1 qc).  A non-negative forecast is final (the negative-moisture fix, Main/mod_tendency.F90:
@@ -1136,6 +1083,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   const double ps = H1T(sPS, 0, 0);
   const double xkcs = xkc * c->rdxsq * pb;
   if (f.xkcs) ST(f.xkcs, o3, xkcs);
+  // diffu_x from a halo-2 LDS tile (Main/mod_diffusion.F90:673-735, 881-891); idiffu = 3: the
+  // column term of k_diffu6, on j = jci2 and on the ring column that is the left neighbour's
+  auto diffu = [&](double ften, const double (&S)[SH2][SW2], const double* d6) {
+    if (c->idiffu == 3) return (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) ? ften + LD(d6, o3) : ften;
+    return diffu_x(g, c, j, i, ften, xkcs, [&](int dj, int di) { return S[a2 + di][b2 + dj]; });
+  };
   // ================= temperature
   {
     double td = d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXT, 0, 0), H1T(sXT, -1, 0),
@@ -1180,11 +1133,11 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       const double xtb = s->xbctime + dt;
       double xf, xg;
       nudge_coef(c, f.ibcr[o2 >> 3], k, xf, xg);
-#define FGT(dj, di) ((LD(f.tb0, O3(dj, di)) + xtb * LD(f.tbt, O3(dj, di))) - LD(f.a2t, O3(dj, di)))
+#define FGT(dj, di) bdy_minus_state(LD(f.tb0, O3(dj, di)), LD(f.tbt, O3(dj, di)), LD(f.a2t, O3(dj, di)), xtb)
       td = relax(td, xf, xg, FGT(0, 0), FGT(-1, 0), FGT(1, 0), FGT(0, -1), FGT(0, 1));
 #undef FGT
     }
-    DIFFU_X(td, sTB, f.d6t);
+    td = diffu(td, sTB, f.d6t);
     // tten + tdyn + tphy (:285-288), then the SUBEX condensation term (:332-341, stubbed)
     // (pc_physic of the coupling seam, loaded here to keep registers free: absent = 0)
     const double tt = ((spt + td) + (f.tphy ? LD(f.tphy, o3) : d_zero)) + d_zero;
@@ -1221,12 +1174,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     const double nfac = 1.0e3, rfac = d_one / nfac;
     double xf, xg;
     nudge_coef(c, f.ibcr[o2 >> 3], k, xf, xg);
-#define FGQ(dj, di) (nfac * (LD(f.qb0, O3(dj, di)) + xtb * LD(f.qbt, O3(dj, di))) - nfac * LD(f.a2qv, O3(dj, di)))
+#define FGQ(dj, di) bdy_minus_state(LD(f.qb0, O3(dj, di)), LD(f.qbt, O3(dj, di)), LD(f.a2qv, O3(dj, di)), xtb, nfac)
     const double f0 = FGQ(0, 0), f1 = FGQ(-1, 0), f2 = FGQ(1, 0), f3 = FGQ(0, -1), f4 = FGQ(0, 1);
 #undef FGQ
     tq = tq + rfac * (xf * f0 - xg * (f1 + f2 + f3 + f4 - d_four * f0));
   }
-  DIFFU_X(tq, sQVB, f.d6qv);
+  tq = diffu(tq, sQVB, f.d6qv);
   // the qv sums and forecast (and with qfuse its RAW filter) before the qc chain, so the qv
   // operands are dead while it runs
   tq = ((spq + tq) + (f.qvphy ? LD(f.qvphy, o3) : d_zero)) + d_zero;
@@ -1265,7 +1218,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       tc = tc - fl * c->xds[k];
     }
   }
-  DIFFU_X(tc, sQCB, f.d6qc);
+  tc = diffu(tc, sQCB, f.d6qc);
 #undef DT
 #undef H1T
   tc = ((d_zero + tc) + (f.qcphy ? LD(f.qcphy, o3) : d_zero)) + d_zero;
@@ -1305,8 +1258,6 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __r
     scalars_block(g, c, s, fs, L.s, bx, by, lz);
   }
 }
-#undef DIFFU_X
-#undef H2T
 
 // ---------------------------------------------------------------------------------------
 // K6. Negative-moisture fix + the RA filter of p* + the RAW filter of qv/qc, one pass
@@ -1483,12 +1434,8 @@ __global__ void k_negfix_post(Geom g, const Consts* __restrict__ c, QFix q) {
 __device__ __forceinline__ void negfix_list(Geom g, const Consts* c, QFix q, int t0, int stride) {
   const int cnt = *q.negcnt;
   for (int e = t0; e < cnt; e += stride) {
-    const uint32_t w = q.neglist[e];
-    const int n = (int)(w & 1u);
-    const long el = (long)(w >> 1);
-    const int k = (int)(el / g.plane) + 1;
-    const long r = el % g.plane;
-    const int i = g.i0 + (int)(r / g.pitch), j = g.j0 + (int)(r % g.pitch);
+    int n, k, j, i;
+    negfix_entry(g, q.neglist[e], n, k, j, i);
     const double* sv = n ? q.cqc : q.cqv;
     if (negfix_dependent(g, sv, j, i, k)) {
       if (q.depf) q.depf[(n * c->kz + (k - 1)) * (g.ici2 - g.ici1 + 1) + (i - g.ici1)] = 1u;
@@ -1514,7 +1461,6 @@ __device__ __forceinline__ void negfix_list(Geom g, const Consts* c, QFix q, int
 // phase 2: one wavefront per (mode, divergence|geopotential) sum runs the k loop in the
 // reference's order.  Blocks [nproj, nproj + 2 kz) run the serial negative-moisture sweeps
 // (one plane each, usually an immediate exit).
-#define SLOT(a, l, s) ((a) + ((long)((s) - 1) * c->nsplit + ((l) - 1)) * g.plane)
 #ifndef SP_LB
 #define SP_LB 5
 #endif
@@ -1623,7 +1569,6 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
   const double rdx2 = d_one / c->dx2;
   // decomposed domain: the split step's inputs also go to the wide frame its exchange fills
   const long qw = wdeld ? gw.ix(j, i) : 0;
-#define WSLOT(a, l, s) ((a) + ((long)((s) - 1) * c->nsplit + ((l) - 1)) * gw.plane)
   if (wdeld && ty == 0) {
     wpsa[qw] = F2(psa, j, i);
     wpsdota[qw] = F2(psdota, j, i);
@@ -1642,10 +1587,14 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
           d2 = d2 + zr * rdx2 * mf * sD2[(k - 1) * SPC + tx];
         }
       }
-      SLOT(deld, l, 1)[q] = ds - d2;
-      SLOT(deld, l, 2)[q] = d2;
-      SLOT(deld, l, 3)[q] = d3 - ds;
-      if (wdeld) { WSLOT(wdeld, l, 1)[qw] = ds - d2; WSLOT(wdeld, l, 2)[qw] = d2; WSLOT(wdeld, l, 3)[qw] = d3 - ds; }
+      split_slot(deld, g.plane, c->nsplit, l, 1)[q] = ds - d2;
+      split_slot(deld, g.plane, c->nsplit, l, 2)[q] = d2;
+      split_slot(deld, g.plane, c->nsplit, l, 3)[q] = d3 - ds;
+      if (wdeld) {
+        split_slot(wdeld, gw.plane, c->nsplit, l, 1)[qw] = ds - d2;
+        split_slot(wdeld, gw.plane, c->nsplit, l, 2)[qw] = d2;
+        split_slot(wdeld, gw.plane, c->nsplit, l, 3)[qw] = d3 - ds;
+      }
       dstor[(long)(l - 1) * g.plane + q] = d2;
     } else {
       const double hs = pf ? pf_st : hstor[(long)(l - 1) * g.plane + q];
@@ -1661,14 +1610,17 @@ __global__ __launch_bounds__(SPC * SPG, SP_LB) void k_split_project(
           h2 = h2 + pdk + div_by(ta * sT2[(k - 1) * SPC + tx], pbv, rpbv) + ek * (pbv - c->pd);
         }
       }
-      SLOT(delh, l, 1)[q] = hs - h2;
-      SLOT(delh, l, 2)[q] = h2;
-      SLOT(delh, l, 3)[q] = h3 - hs;
-      if (wdeld) { WSLOT(wdelh, l, 1)[qw] = hs - h2; WSLOT(wdelh, l, 2)[qw] = h2; WSLOT(wdelh, l, 3)[qw] = h3 - hs; }
+      split_slot(delh, g.plane, c->nsplit, l, 1)[q] = hs - h2;
+      split_slot(delh, g.plane, c->nsplit, l, 2)[q] = h2;
+      split_slot(delh, g.plane, c->nsplit, l, 3)[q] = h3 - hs;
+      if (wdeld) {
+        split_slot(wdelh, gw.plane, c->nsplit, l, 1)[qw] = hs - h2;
+        split_slot(wdelh, gw.plane, c->nsplit, l, 2)[qw] = h2;
+        split_slot(wdelh, gw.plane, c->nsplit, l, 3)[qw] = h3 - hs;
+      }
       hstor[(long)(l - 1) * g.plane + q] = h2;
     }
   }
-#undef WSLOT
   PT_PRINT(5);
 }
 
@@ -1681,8 +1633,8 @@ __global__ void k_spstep_init(Geom g, const Consts* __restrict__ c, const double
   const long q = g.ix(j, i);
   const bool ce = in(j, g.jce1, g.jce2) && in(i, g.ice1, g.ice2);
   for (int l = 1; l <= c->nsplit; l++) {
-    ddsum[(long)(l - 1) * g.plane + q] = ce ? SLOT(deld, l, 1)[q] : d_zero;
-    dhsum[(long)(l - 1) * g.plane + q] = ce ? SLOT(delh, l, 1)[q] : d_zero;
+    ddsum[(long)(l - 1) * g.plane + q] = ce ? split_slot(deld, g.plane, c->nsplit, l, 1)[q] : d_zero;
+    dhsum[(long)(l - 1) * g.plane + q] = ce ? split_slot(delh, g.plane, c->nsplit, l, 1)[q] : d_zero;
   }
 }
 
@@ -1694,7 +1646,7 @@ __global__ void k_spstep_grad(Geom g, const Consts* __restrict__ c, int l, int s
   const int j = g.jdi1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int i = g.idi1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
   if (j > g.jdi2 || i > g.idi2) return;
-  const double* x = SLOT(delh, l, src);
+  const double* x = split_slot(delh, g.plane, c->nsplit, l, src);
   const double fac = c->dx2 * F2(msfx, j, i);
   double w1 = (F2(x, j, i) + F2(x, j, i - 1) - F2(x, j - 1, i) - F2(x, j - 1, i - 1)) / fac;
   double w2 = (F2(x, j, i) + F2(x, j - 1, i) - F2(x, j, i - 1) - F2(x, j - 1, i - 1)) / fac;
@@ -1714,9 +1666,11 @@ __global__ void k_spstep_update(Geom g, const Consts* __restrict__ c, int l, int
   const int i = g.ice1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
   if (j > g.jce2 || i > g.ice2) return;
   const long q = g.ix(j, i);
-  double* D0 = SLOT(deld, l, n0); double* D1 = SLOT(deld, l, n1); double* DN = SLOT(deld, l, nn);
-  double* H0 = SLOT(delh, l, n0); double* H1 = SLOT(delh, l, n1); double* HN = SLOT(delh, l, nn);
-  const double* D3 = SLOT(deld, l, 3); const double* H3 = SLOT(delh, l, 3);
+  const long P = g.plane;
+  const int ns = c->nsplit;
+  double* D0 = split_slot(deld, P, ns, l, n0); double* D1 = split_slot(deld, P, ns, l, n1); double* DN = split_slot(deld, P, ns, l, nn);
+  double* H0 = split_slot(delh, P, ns, l, n0); double* H1 = split_slot(delh, P, ns, l, n1); double* HN = split_slot(delh, P, ns, l, nn);
+  const double* D3 = split_slot(deld, P, ns, l, 3); const double* H3 = split_slot(delh, P, ns, l, 3);
   const double aam = c->aam[l - 1], dtau = c->dtau[l - 1], hbar = c->hbar[l - 1];
   const bool ci = in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
   if (ci) {
@@ -1776,10 +1730,10 @@ __global__ __launch_bounds__((SB + 2 * SPH) * (SB + 2 * SPH)) void k_spstep_fuse
   const double aam = c->aam[l - 1], dtau = c->dtau[l - 1], hbar = c->hbar[l - 1];
   const int m2 = (int)aam * 2;
   const double dtau2 = dtau * d_two, rdx2 = d_one / c->dx2;
-#define WSLOT(a, l, s) ((a) + ((long)((s) - 1) * c->nsplit + ((l) - 1)) * w.plane)
-  const double* D1 = WSLOT(deld, l, 1); const double* D2 = WSLOT(deld, l, 2); const double* D3 = WSLOT(deld, l, 3);
-  const double* H1 = WSLOT(delh, l, 1); const double* H2 = WSLOT(delh, l, 2); const double* H3 = WSLOT(delh, l, 3);
-#undef WSLOT
+  const long P = w.plane;
+  const int ns = c->nsplit;
+  const double* D1 = split_slot(deld, P, ns, l, 1); const double* D2 = split_slot(deld, P, ns, l, 2); const double* D3 = split_slot(deld, P, ns, l, 3);
+  const double* H1 = split_slot(delh, P, ns, l, 1); const double* H2 = split_slot(delh, P, ns, l, 2); const double* H3 = split_slot(delh, P, ns, l, 3);
   const int gjx = g.gjx, giy = g.giy;
   // the thread's region point (tx, ty); d3/m2, h3/m2 (forward step) and d3/aam, h3/aam
   // (leapfrog) are loop-invariant and formed once
@@ -1892,7 +1846,6 @@ template __global__ __launch_bounds__(24 * 24) void k_spstep_fused<8>(Geom, Geom
 
 __device__ __forceinline__ void bdyval_point(const Geom& g, double xt, bool integ, const BdyArgs& a, int line, int x,
                                              int k, bool interior);
-__device__ __forceinline__ int bdy_chunks_d(const Geom& g) { return (max(g.jde2 - g.jde1, g.ide2 - g.ide1) + 65) / 64; }
 
 // splitf corrections, Main/mod_split.F90:417-457 (ps and t on ci, u and v on di).
 // BDY (k_split_correct_bdy, rcmdyn_step): the step's bdyval (Main/mod_bdycod.F90:1109-1529 +
@@ -1926,7 +1879,7 @@ __device__ __forceinline__ void split_correct_body(
   const int zbdy = BDY ? (int)gridDim.z - nser - kz : 0;
   PT_DECL
   if (BDY && (int)blockIdx.z < zbdy) {
-    const int nchunk = bdy_chunks_d(g);
+    const int nchunk = bdy_chunks(g);
     const int item = (((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x) * 4 +
                      (int)threadIdx.y;
     if (item >= 6 * nchunk * kz) return;
@@ -2074,7 +2027,6 @@ __device__ __forceinline__ void split_correct_body(
     }
   }
 }
-#undef SLOT
 
 #ifndef SCOR_LB
 #define SCOR_LB 4

@@ -218,7 +218,10 @@ struct BdyArgs {
 };
 __global__ void k_bdyval_set(Geom g, const StepState* __restrict__ s, BdyArgs a);
 // 64-point chunks of the longest boundary line, one point past the tile included
-inline int bdy_chunks(const Geom& g) { return (std::max(g.jde2 - g.jde1, g.ide2 - g.ide1) + 65) / 64; }
+__host__ __device__ __forceinline__ int bdy_chunks(const Geom& g) {
+  const int nj = g.jde2 - g.jde1, ni = g.ide2 - g.ide1;
+  return ((nj > ni ? nj : ni) + 65) / 64;
+}
 template <int NS>
 __global__ __launch_bounds__(256) void k_split_correct_bdy(Geom g, const Consts* __restrict__ c, const double* __restrict__ ddsum, const double* __restrict__ dhsum, const double* __restrict__ psdota, const double* __restrict__ msfd, StepState* s, int advance, const double* __restrict__ red, int red_total, BdyArgs a, QFix qf, int nser);
 __global__ void k_bdyval_qc(Geom g, int do_qc, int do_qv, double* a1qc, double* a1qv, const double* __restrict__ psa, Slices sl, long slen, StepState* s, double dtsec, int advance, FlagSnap* ring);

@@ -67,29 +67,18 @@ __device__ __forceinline__ int i0c(const Geom& g) { return g.i0; }
   THREAD_POINT(g.j0, g.i0);                                             \
   if (j >= g.j0 + g.nj || i >= g.i0 + g.ni) return;
 
-// decoupled boundary ud/vd with the iboudy = 3/4 inflow/outflow rule (see udvd_bdy in
-// kernels.hip; Main/mod_tendency.F90:893-994)
+// decoupled ud/vd at level k: atm1 u, v * 1/p*dot, on the global boundary lines with the
+// iboudy = 3/4 inflow/outflow rule (udvd_rule, pointops.hpp; Main/mod_tendency.F90:893-994)
 __device__ double2 udvd_nh(const Geom& g, int iboudy, const double* a1u, const double* a1v, const double* rpsda,
                            int j, int i, int k) {
-  auto base = [&](int jj, int ii) {
-    const double r = F2(rpsda, jj, ii);
-    return make_double2(F3(a1u, jj, ii, k) * r, F3(a1v, jj, ii, k) * r);
-  };
-  if (iboudy != 3 && iboudy != 4) return base(j, i);
-  // global boundary lines (a ghost point on them carries the value its owner computes and
-  // the reference exchanges)
-  auto we = [&](int jj, int ii) {
-    if (in(ii, 2, g.giy - 1)) {
-      if (g.gjeq(jj, 1) && F3(a1u, jj, ii, k) <= d_zero) return base(2, ii);
-      if (g.gjeq(jj, g.gjx) && F3(a1u, jj, ii, k) >= d_zero) return base(g.gjx - 1, ii);
-    }
-    return base(jj, ii);
-  };
-  if (g.band || in(j, 1, g.gjx)) {
-    if (g.gieq(i, 1) && F3(a1v, j, i, k) >= d_zero) return we(j, 2);
-    if (g.gieq(i, g.giy) && F3(a1v, j, i, k) <= d_zero) return we(j, g.giy - 1);
+  auto u = [&](int jj, int ii) { return F3(a1u, jj, ii, k); };
+  auto v = [&](int jj, int ii) { return F3(a1v, jj, ii, k); };
+  auto r = [&](int jj, int ii) { return F2(rpsda, jj, ii); };
+  if (iboudy != 3 && iboudy != 4) {
+    const double rr = r(j, i);
+    return make_double2(u(j, i) * rr, v(j, i) * rr);
   }
-  return we(j, i);
+  return udvd_rule(g, j, i, u, v, r);
 }
 
 // ud, vd of one dot point from its atm1 u, v (au, av) and 1/p*dot (r), already loaded by the
@@ -238,62 +227,6 @@ __global__ void k_nh_coeff_raw(Geom g, const Consts* __restrict__ c, NHFields f)
 // levels: xkcr of level k-1) in k_nh_tend_c, xkd (dot interior, the four-point mean) in
 // k_nh_tend_d (Main/mod_diffusion.F90:236-250)
 
-// upstream flux form of hadvt/hadvqv/hadvqx/hadv3d ind 0 at one cross point
-// (Main/mod_advection.F90:337-386, 547-596, 639-653, 466-480) on the values of the advected
-// field at the point and its west/east/south/north neighbours; limiter 0 none, 1 t, 2 q
-__device__ __forceinline__ double hadv_v(const Consts* c, double fc, double fw, double fe, double fs, double fn,
-                                         double u1, double u2, double v1, double v2, double xmf, double ps,
-                                         int limiter) {
-  const double f1 = d_half * c->ul * (u2 + u1) / ps;
-  const double f2 = d_half * c->ul * (v2 + v1) / ps;
-  const double fx1 = (d_one + f1) * fw + (d_one - f1) * fc;
-  const double fx2 = (d_one + f1) * fc + (d_one - f1) * fe;
-  const double fy1 = (d_one + f2) * fs + (d_one - f2) * fc;
-  const double fy2 = (d_one + f2) * fc + (d_one - f2) * fn;
-  double fg = -xmf * (u2 * fx2 - u1 * fx1 + v2 * fy2 - v1 * fy1);
-  if (limiter && c->stability_enhance) {
-    double den, thr;
-    if (limiter == 1) { den = ps; thr = c->t_extrema; }
-    else { den = dmax(fc, DLOWVAL); thr = c->q_rel_extrema; }
-    if (fabs(fn + fs - d_two * fc) / den > thr) {
-      if (fc > fn && fc > fs) fg = dmin(fg, d_zero);
-      else if (fc < fn && fc < fs) fg = dmax(fg, d_zero);
-    }
-    if (fabs(fe + fw - d_two * fc) / den > thr) {
-      if (fc > fe && fc > fw) fg = dmin(fg, d_zero);
-      else if (fc < fe && fc < fw) fg = dmax(fg, d_zero);
-    }
-  }
-  return fg;
-}
-
-__device__ __forceinline__ double nh_relax(double ften, double xf, double xg, double f0, double f1, double f2,
-                                           double f3, double f4) {
-  return ften + xf * f0 - xg * (f1 + f2 + f3 + f4 - d_four * f0);
-}
-
-// 4th-order (idiffu = 1) / 9-point (idiffu = 2) diffusion of one cross field at (j,i,k)
-// (diffu_x3d / diffu_x3df / diffu_x4d3d, Main/mod_diffusion.F90:523-790)
-__device__ __forceinline__ double diffx_at(const Geom& g, const Consts* c, double ften, const double* fa,
-                                           const double* xk, int j, int i, int k) {
-  if (c->idiffu == 2) {
-    return ften + d_one * F3(xk, j, i, k) *
-        (o4_c1 * (F3(fa, j + 1, i, k) + F3(fa, j - 1, i, k) + F3(fa, j, i + 1, k) + F3(fa, j, i - 1, k)) +
-         o4_c2 * (F3(fa, j + 1, i + 1, k) + F3(fa, j - 1, i - 1, k) + F3(fa, j - 1, i + 1, k) + F3(fa, j + 1, i - 1, k)) +
-         o4_c3 * F3(fa, j, i, k));
-  }
-  if (in(j, g.jcii1, g.jcii2) && in(i, g.icii1, g.icii2))
-    ften = ften - d_one * F3(xk, j, i, k) *
-        (z4_c1 * (F3(fa, j + 2, i, k) + F3(fa, j - 2, i, k) + F3(fa, j, i + 2, k) + F3(fa, j, i - 2, k)) +
-         z4_c2 * (F3(fa, j + 1, i, k) + F3(fa, j - 1, i, k) + F3(fa, j, i + 1, k) + F3(fa, j, i - 1, k)) +
-         z4_c3 * F3(fa, j, i, k));
-  const double lap = z4_c1 * (F3(fa, j + 1, i, k) + F3(fa, j - 1, i, k) + F3(fa, j, i + 1, k) + F3(fa, j, i - 1, k)) +
-                     z4_c2 * F3(fa, j, i, k);
-  const int nb = (g.bl && j == g.jci1) + (g.br && j == g.jci2) + (g.bb && i == g.ici1) + (g.bt && i == g.ici2);
-  for (int q = 0; q < nb; q++) ften = ften + d_one * F3(xk, j, i, k) * lap;
-  return ften;
-}
-
 // idiffu = 3 (Main/mod_diffusion.F90:412-516, 602-651, 736-785, 893-942): the sixth-order
 // terms of the tile's column, j = jdi2 for u, v and j = jci2 for t, qv, qc, pp (levels 1..kz)
 // and w (1..kz+1; diffu_x3df reads xkc on level kz+1, one past its kz levels -- the
@@ -347,7 +280,11 @@ __device__ __forceinline__ double nh_tau(const Consts* c, double z, double zmax)
   return d_zero;
 }
 
-// diffx_at on a field staged in LDS: S[ti][tj] is the thread's point
+// diffu_x (pointops.hpp) on a field k_nh_tend_c staged in LDS, S[ti][tj] the thread's point, an
+// owned interior one, where the tile's index tests below equal diffu_x's global ones.  This
+// copy stays for k_nh_tend_c alone: through diffu_x (four separate boundary adds, on five
+// fields) the kernel measured 0.5 % slower at C5, 3 639-3 648 against 3 623-3 631 us
+// (profiles/r07/pointops_ab.log)
 template <int W>
 __device__ __forceinline__ double diffx_l(const Geom& g, const Consts* c, double ften, const double (*S)[W],
                                           double xk, int j, int i, int ti, int tj) {
@@ -370,38 +307,14 @@ __device__ __forceinline__ double diffx_l(const Geom& g, const Consts* c, double
 #undef SA
 }
 
-// time filters of t (RA), qv and qc (RAW), Main/mod_tendency.F90:422-427 (p* is constant):
-// o1, o2: atm1, atm2 before the filter; v: the forecast (for qv, qc fixed where negative);
-// n1, n2: atm1, atm2 after it
-__device__ __forceinline__ void nh_ra_t(const Consts* c, double o1, double o2, double v, double& n1, double& n2) {
-  const double d = c->gnu1 * (v + o2 - d_two * o1);
-  n2 = o1 + d;
-  n1 = v;
-}
-__device__ __forceinline__ void nh_raw_qv(const Consts* c, double o1, double o2, double v, double psa, double psb,
-                                          double& n1, double& n2) {
-  const double beta = 0.53;
-  const double d = c->gnu1 * (v + o2 - d_two * o1);
-  n2 = dmax(o1 + beta * d, MINQQ * psa);
-  n1 = dmax(v + (beta - d_one) * d, MINQQ * psb);
-}
-__device__ __forceinline__ void nh_raw_qc(const Consts* c, double o1, double o2, double v, double& n1, double& n2) {
-  const double beta = 0.53;
-  const double d = c->gnu2 * (v + o2 - d_two * o1);
-  double m = o1 + beta * d, q = v + (beta - d_one) * d;
-  if (m < d_zero) m = d_zero;
-  if (q < d_zero) q = d_zero;
-  n2 = m;
-  n1 = q;
-}
 // tfuse: the RAW filter of qv (n = 0) or qc (n = 1) at one point into the other parity
 __device__ __forceinline__ void nh_filter_q_to(const Geom& g, const Consts* c, const NHFields& f, int n, int j, int i, int k,
                                                double v) {
   double n1, n2;
   if (n == 0)
-    nh_raw_qv(c, F3(f.a1qv, j, i, k), F3(f.a2qv, j, i, k), v, F2(f.psa, j, i), F2(f.psb, j, i), n1, n2);
+    raw_qv(c, F3(f.a1qv, j, i, k), F3(f.a2qv, j, i, k), v, F2(f.psa, j, i), F2(f.psb, j, i), n1, n2);
   else
-    nh_raw_qc(c, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k), v, n1, n2);
+    raw_qc(c, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k), v, n1, n2);
   F3(n ? f.b1qc : f.b1qv, j, i, k) = n1;
   F3(n ? f.b2qc : f.b2qv, j, i, k) = n2;
 }
@@ -430,10 +343,10 @@ constexpr int TC_NF = 5;
 #define TC_W 1      // 6 or 8 waves/SIMD measured slower (4.73, 5.35 ms against 3.82)
 #endif
 // relaxation and physics-tendency terms of k_nh_tend_c and k_nh_tend_d (#undef after k_nh_tend_d)
-#define FG(b0, bt, a, J, I) ((F3(b0, J, I, k) + xt * F3(bt, J, I, k)) - F3(a, J, I, k))
+#define FG(b0, bt, a, J, I) bdy_minus_state(F3(b0, J, I, k), F3(bt, J, I, k), F3(a, J, I, k), xt)
 #define RELAX5(x, b0, bt, a) \
-  x = nh_relax(x, xf, xg, FG(b0, bt, a, j, i), FG(b0, bt, a, j - 1, i), FG(b0, bt, a, j + 1, i), \
-               FG(b0, bt, a, j, i - 1), FG(b0, bt, a, j, i + 1))
+  x = relax(x, xf, xg, FG(b0, bt, a, j, i), FG(b0, bt, a, j - 1, i), FG(b0, bt, a, j + 1, i), \
+            FG(b0, bt, a, j, i - 1), FG(b0, bt, a, j, i + 1))
 #define PHY(p) (f.p ? F3(f.p, j, i, k) : 0.0)
 #if !NH_OTHER_KERNELS
 template <bool QX>
@@ -533,7 +446,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
                    F3(a, j, i + 1, k) * rn};
     if (clip)
       for (int q = 0; q < 5; q++) x[q] = dmax(x[q], clip == 1 ? MINQQ : d_zero);
-    return hadv_v(c, x[0], x[1], x[2], x[3], x[4], u1, u2, v1, v2, xmf, ps, lim);
+    return hadv_flux(c, xmf, ps, u1, u2, v1, v2, x[0], x[1], x[2], x[3], x[4], lim);
   };
   auto xqcat = [&](int kk) { return dmax(F3(f.a1qc, j, i, kk) * r0, d_zero); };
   // the water load qcd: qc, or with nqx = 5 the sum over iqfrst..iqlst (decouple, :1107-1115)
@@ -657,8 +570,8 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   // ================= t, ithadv = 1 (:1347-1356, 1594-1600): thten = hadvt of th, then vadv3d
   // ind = 0 (nk = kz) of tha = th*p*, plus th*cr; tdyn = atm1%t*thten/tha
   {
-    double thd = d_zero + hadv_v(c, F3(f.th, j, i, k), F3(f.th, j - 1, i, k), F3(f.th, j + 1, i, k),
-                                 F3(f.th, j, i - 1, k), F3(f.th, j, i + 1, k), u1, u2, v1, v2, xmf, ps, 1);
+    double thd = d_zero + hadv_flux(c, xmf, ps, u1, u2, v1, v2, F3(f.th, j, i, k), F3(f.th, j - 1, i, k),
+                                    F3(f.th, j + 1, i, k), F3(f.th, j, i - 1, k), F3(f.th, j, i + 1, k), 1);
     auto thflux = [&](int kk) {
       return F3(f.qdot, j, i, kk) *
              (c->twt1[kk] * (F3(f.th, j, i, kk) * ps) + c->twt2[kk] * (F3(f.th, j, i, kk - 1) * ps));
@@ -677,7 +590,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     if (ray) tt = tt + tau * ((F3(f.tb0, j, i, k) + xt * F3(f.tbt, j, i, k)) - F3(f.a2t, j, i, k));
     if (wdiag) F3(f.tten, j, i, k) = tt;
     const double o2 = F3(f.a2t, j, i, k), ctv = o2 + dt * tt;
-    if (f.tfuse) nh_ra_t(c, F3(f.a1t, j, i, k), o2, ctv, F3(f.b1t, j, i, k), F3(f.b2t, j, i, k));
+    if (f.tfuse) ra_t(c, F3(f.a1t, j, i, k), o2, ctv, F3(f.b1t, j, i, k), F3(f.b2t, j, i, k));
     else F3(f.ct, j, i, k) = ctv;
   }
   // ================= qv: hadvqv (or the semi-Lagrangian start), vadvqv, adiabatic, boundary,
@@ -699,7 +612,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     if (sponge) qt0 = wsp * d_zero + (d_one - wsp) * F3(f.qbt, j, i, k);
     if (nudge) {
       const double nfac = 1.0e3, rfac = d_one / nfac;
-#define FQ(J, I) (nfac * (F3(f.qb0, J, I, k) + xt * F3(f.qbt, J, I, k)) - nfac * F3(f.a2qv, J, I, k))
+#define FQ(J, I) bdy_minus_state(F3(f.qb0, J, I, k), F3(f.qbt, J, I, k), F3(f.a2qv, J, I, k), xt, nfac)
       const double q0 = FQ(j, i), q1 = FQ(j - 1, i), q2 = FQ(j + 1, i), q3 = FQ(j, i - 1), q4 = FQ(j, i + 1);
 #undef FQ
       qd = qd + rfac * (xf * q0 - xg * (q1 + q2 + q3 + q4 - d_four * q0));
@@ -712,7 +625,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     const double o2 = F3(f.a2qv, j, i, k), cq = o2 + dt * qv;
     F3(f.cqv, j, i, k) = cq;
     if (f.tfuse && !(cq < d_zero))      // a negative forecast: filtered after its fix
-      nh_raw_qv(c, F3(f.a1qv, j, i, k), o2, cq, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
+      raw_qv(c, F3(f.a1qv, j, i, k), o2, cq, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
     if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2);
   }
   // ================= qc: hadvqx (or the semi-Lagrangian start), vadv4d ind = 1, adiabatic,
@@ -740,7 +653,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     const double o2 = F3(f.a2qc, j, i, k), cq = o2 + dt * qc;
     F3(f.cqc, j, i, k) = cq;
     if (f.tfuse && !(cq < d_zero))
-      nh_raw_qc(c, F3(f.a1qc, j, i, k), o2, cq, F3(f.b1qc, j, i, k), F3(f.b2qc, j, i, k));
+      raw_qc(c, F3(f.a1qc, j, i, k), o2, cq, F3(f.b1qc, j, i, k), F3(f.b2qc, j, i, k));
     if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2 + 1);
   }
 }
@@ -961,22 +874,9 @@ __global__ __launch_bounds__(TDT) void k_nh_tend_d(Geom g, const Consts* __restr
 #undef RELAX5
 #undef FG
 
-// negative-moisture fix (:382-393): see K6 in kernels.hip.  Parallel pass for the points
-// whose sweep predecessors are non-negative, serial sweep of the flagged planes after it.
-__device__ __forceinline__ double nh_negfix_sum(const Geom& g, const double* sv, const double* fx, int j, int i,
-                                                int k, bool use_fixed) {
-  double sum = 0.0;
-  for (int ii = i - 1; ii <= i + 1; ii++)
-    for (int jj = j - 1; jj <= j + 1; jj++) {
-      double v = F3(sv, jj, ii, k);
-      if (use_fixed) {
-        const bool pred = (ii < i) || (ii == i && jj < j);
-        if (pred && in(jj, g.jci1, g.jci2) && in(ii, g.ici1, g.ici2) && v < d_zero) v = F3(fx, jj, ii, k);
-      }
-      sum = sum + fabs(v);
-    }
-  return 0.01 * sum / 9.0;
-}
+// negative-moisture fix (:382-393; the scheme is described with the hydrostatic k_qfilter,
+// kernels.hip, and negfix_sweep, qxcommon.hpp).  Parallel pass for the points whose sweep
+// predecessors are non-negative, serial sweep of the flagged planes after it.
 // one negative forecast (species n) at an interior point: fixed in parallel when no sweep
 // predecessor is negative, else its plane's row is marked for the serial sweep
 __device__ __forceinline__ void nh_negfix_at(const Geom& g, const Consts* c, const NHFields& f, int n, int j, int i,
@@ -986,7 +886,7 @@ __device__ __forceinline__ void nh_negfix_at(const Geom& g, const Consts* c, con
   if (negfix_dependent(g, sv, j, i, k)) {
     negfix_mark(g, f.depplane, n * c->kz + (k - 1), i);
   } else {
-    const double v = nh_negfix_sum(g, sv, fx, j, i, k, false);
+    const double v = negfix_sum(g, sv, fx, j, i, k, false);
     F3(fx, j, i, k) = v;
     if (f.tfuse) nh_filter_q_to(g, c, f, n, j, i, k, v);
   }
@@ -996,12 +896,8 @@ __device__ __forceinline__ void nh_negfix_at(const Geom& g, const Consts* c, con
 __global__ void k_nh_negfix(Geom g, const Consts* __restrict__ c, NHFields f) {
   const int cnt = *f.negcnt;
   for (int e = (int)(blockIdx.x * blockDim.x + threadIdx.x); e < cnt; e += (int)(gridDim.x * blockDim.x)) {
-    const unsigned w = f.neglist[e];
-    const int n = (int)(w & 1u);
-    const long el = (long)(w >> 1);
-    const int k = (int)(el / g.plane) + 1;
-    const long r = el % g.plane;
-    const int i = g.i0 + (int)(r / g.pitch), j = g.j0 + (int)(r % g.pitch);
+    int n, k, j, i;
+    negfix_entry(g, f.neglist[e], n, k, j, i);
     nh_negfix_at(g, c, f, n, j, i, k);
   }
 }
@@ -1024,8 +920,8 @@ struct NhQRaw {
   __device__ void apply(int j, int i, double v, const double* x) const {
     if (!tfuse) return;
     double n1, n2;
-    if (n == 0) nh_raw_qv(c, x[0], x[1], v, x[2], x[3], n1, n2);
-    else nh_raw_qc(c, x[0], x[1], v, n1, n2);
+    if (n == 0) raw_qv(c, x[0], x[1], v, x[2], x[3], n1, n2);
+    else raw_qc(c, x[0], x[1], v, n1, n2);
     F3(b1, j, i, k) = n1;
     F3(b2, j, i, k) = n2;
   }
@@ -1045,17 +941,17 @@ __global__ __launch_bounds__(512) void k_nh_negfix_serial(Geom g, const Consts* 
 // tfuse = 0: the three time filters in place at one interior cross point and level
 __device__ __forceinline__ void nh_tfilter_at(const Geom& g, const Consts* c, const NHFields& f, int j, int i,
                                               int k) {
-  nh_ra_t(c, F3(f.a1t, j, i, k), F3(f.a2t, j, i, k), F3(f.ct, j, i, k), F3(f.a1t, j, i, k), F3(f.a2t, j, i, k));
+  ra_t(c, F3(f.a1t, j, i, k), F3(f.a2t, j, i, k), F3(f.ct, j, i, k), F3(f.a1t, j, i, k), F3(f.a2t, j, i, k));
   {
     double v = F3(f.cqv, j, i, k);
     if (v < d_zero) v = F3(f.fqv, j, i, k);
-    nh_raw_qv(c, F3(f.a1qv, j, i, k), F3(f.a2qv, j, i, k), v, F2(f.psa, j, i), F2(f.psb, j, i),
+    raw_qv(c, F3(f.a1qv, j, i, k), F3(f.a2qv, j, i, k), v, F2(f.psa, j, i), F2(f.psb, j, i),
               F3(f.a1qv, j, i, k), F3(f.a2qv, j, i, k));
   }
   {
     double v = F3(f.cqc, j, i, k);
     if (v < d_zero) v = F3(f.fqc, j, i, k);
-    nh_raw_qc(c, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k), v, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k));
+    raw_qc(c, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k), v, F3(f.a1qc, j, i, k), F3(f.a2qc, j, i, k));
   }
 }
 

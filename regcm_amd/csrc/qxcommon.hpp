@@ -1,14 +1,16 @@
 // qxcommon.hpp -- device helpers of the moisture species shared by the qv/qc kernels
-// (kernels.hip) and the hydrometeors of nqx = 5 (species.hip): the upstream flux form, the
-// negative-moisture fix, the RAW filters and bdyval's hydrometeor inflow/outflow lines.
+// (kernels.hip, kernels_nh.hip) and the hydrometeors of nqx = 5 (species.hip): the
+// negative-moisture fix and bdyval's hydrometeor inflow/outflow lines (the per-point formulas
+// are in pointops.hpp).
 #pragma once
 #include "kernels.hpp"
 #include "devcommon.hpp"
+#include "pointops.hpp"
 #include "fastmath.hpp"
 
 namespace rcm {
 
-// negative-moisture fix helpers (K6 below)
+// negative-moisture fix helpers (K6, kernels.hip): the reference's value of one point
 __device__ __forceinline__ double negfix_sum(const Geom& g, const double* sv, const double* fx, int j, int i, int k,
                                              bool use_fixed) {
   double sum = 0.0;
@@ -302,53 +304,6 @@ __device__ void negfix_resolve(const Geom& g, const double* sv, double* fx, unsi
     return;
   }
   if (tid < 64) negfix_sweep(g, sv, fx, dep, plane, k, negfix_sweep_lds(g) <= ldsn ? lds : nullptr, post);
-}
-
-// RAW filters of one point (filter_raw_qv / filter_raw_4d) with the filtered p*
-__device__ __forceinline__ void raw_filter(const Consts* c, int n, double fq, double o1, double o2v, double pa,
-                                           double pb, double& n1, double& n2) {
-  const double beta = 0.53;
-  if (n == 0) {
-    const double d = c->gnu1 * (fq + o2v - d_two * o1);
-    n2 = dmax(o1 + beta * d, MINQQ * pa);
-    n1 = dmax(fq + (beta - d_one) * d, MINQQ * pb);
-  } else {
-    const double d = c->gnu2 * (fq + o2v - d_two * o1);
-    double m = o1 + beta * d;
-    double q = fq + (beta - d_one) * d;
-    if (m < d_zero) m = d_zero;
-    if (q < d_zero) q = d_zero;
-    n2 = m;
-    n1 = q;
-  }
-}
-
-// upstream flux-form advection of one scalar (hadvt/hadvqv/hadvqx, Main/mod_advection.F90:
-// 337-386, 547-596, 639-653); limiter 0 none, 1 t_extrema, 2 q_rel_extrema
-__device__ __forceinline__ double hadv_flux(const Consts* c, double xm, double ps, double uavg1, double uavg2,
-                                            double vavg1, double vavg2, double fc, double fw, double fe, double fs,
-                                            double fn, int limiter) {
-  const double ul = c->ul;
-  const double f1 = d_half * ul * (uavg2 + uavg1) / ps;
-  const double f2 = d_half * ul * (vavg2 + vavg1) / ps;
-  const double fx1 = (d_one + f1) * fw + (d_one - f1) * fc;
-  const double fx2 = (d_one + f1) * fc + (d_one - f1) * fe;
-  const double fy1 = (d_one + f2) * fs + (d_one - f2) * fc;
-  const double fy2 = (d_one + f2) * fc + (d_one - f2) * fn;
-  double fg = -xm * (uavg2 * fx2 - uavg1 * fx1 + vavg2 * fy2 - vavg1 * fy1);
-  if (limiter && c->stability_enhance) {
-    double den, thr;
-    if (limiter == 1) { den = ps; thr = c->t_extrema; } else { den = dmax(fc, DLOWVAL); thr = c->q_rel_extrema; }
-    if (fabs(fn + fs - d_two * fc) / den > thr) {
-      if (fc > fn && fc > fs) fg = dmin(fg, d_zero);
-      else if (fc < fn && fc < fs) fg = dmax(fg, d_zero);
-    }
-    if (fabs(fe + fw - d_two * fc) / den > thr) {
-      if (fc > fe && fc > fw) fg = dmin(fg, d_zero);
-      else if (fc < fe && fc < fw) fg = dmax(fg, d_zero);
-    }
-  }
-  return fg;
 }
 
 // qc inflow/outflow (present_qc = .false., bdyflow), Main/mod_bdycod.F90:2153-2220, one

@@ -41,33 +41,6 @@ constexpr int QW1 = QBJ + 2, QH1 = QBI + 2;    // halo 1
 constexpr int QW2 = QBJ + 4, QH2 = QBI + 4;    // halo 2
 }  // namespace
 
-// diffu_x4d of one point (Main/mod_diffusion.F90:673-713 idiffu = 1, 726-735 / 881-891
-// idiffu = 2; idiffu = 3 adds k_diffu6's column term), f(dj, di) the mkslice field qxb3d
-template <class FB>
-__device__ __forceinline__ double qx_diffu(const Geom& g, const Consts* __restrict__ c, int j, int i, double ften,
-                                           double xkcs, FB f, const double* d6, uint32_t o3) {
-  if (c->idiffu == 3) {
-    if (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) ften = ften + LD(d6, o3);
-    return ften;
-  }
-  if (c->idiffu == 2)
-    return ften + d_one * xkcs *
-                      (o4_c1 * (f(1, 0) + f(-1, 0) + f(0, 1) + f(0, -1)) +
-                       o4_c2 * (f(1, 1) + f(-1, -1) + f(-1, 1) + f(1, -1)) + o4_c3 * f(0, 0));
-  if (g.gcii(j, i))
-    ften = ften - d_one * xkcs *
-                      (z4_c1 * (f(2, 0) + f(-2, 0) + f(0, 2) + f(0, -2)) +
-                       z4_c2 * (f(1, 0) + f(-1, 0) + f(0, 1) + f(0, -1)) + z4_c3 * f(0, 0));
-  auto lap = [&](double x) {
-    return x + d_one * xkcs * (z4_c1 * (f(1, 0) + f(-1, 0) + f(0, 1) + f(0, -1)) + z4_c2 * f(0, 0));
-  };
-  if (g.gjeq(j, 2)) ften = lap(ften);
-  if (g.gjeq(j, g.gjx - 2)) ften = lap(ften);
-  if (g.gieq(i, 2)) ften = lap(ften);
-  if (g.gieq(i, g.giy - 2)) ften = lap(ften);
-  return ften;
-}
-
 // K_QX1.  The tendencies and forecast of the hydrometeors beyond qc at the cross points of the
 // tile and its ghost ring (jcx x icx, as k_scalars: the ring is what the exchange of atmc%qx
 // would deliver), one level per block.  Reads the scaled diffusion coefficient k_scalars
@@ -163,7 +136,12 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
         tq = tq - fl * c->xds[k];
       }
     }
-    tq = qx_diffu(g, c, j, i, tq, xkcs, [&](int dj, int di) { return sB[n][a2 + di][b2 + dj]; }, q.d6[n], o3);
+    // diffu_x4d on the mkslice field qxb3d; idiffu = 3: k_diffu6's column term (as k_scalars)
+    if (c->idiffu == 3) {
+      if (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) tq = tq + LD(q.d6[n], o3);
+    } else {
+      tq = diffu_x(g, c, j, i, tq, xkcs, [&](int dj, int di) { return sB[n][a2 + di][b2 + dj]; });
+    }
     // qxten = (0 + qxdyn) + qxphy (:332-335); the forecast (:375-380)
     tq = (d_zero + tq) + (q.phy[n] ? LD(q.phy[n], o3) : d_zero);
     ST(q.cq[n], o3, LD(q.a2[n], o3) + dt * tq);
@@ -222,22 +200,13 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
     if (c->idiffu == 3) {
       if (j == g.jci2) cd = cd + F3(q.d6[n], j, i, k);
     } else {
-      // diffu_x4d on mkslice's qxb3d = max(atm2 * (1/psb), 0), Main/mod_diffusion.F90:792-947
+      // diffu_x4d on mkslice's qxb3d = max(atm2 * (1/psb), 0), Main/mod_diffusion.F90:792-947 (an
+      // owned interior point, where diffu_x's global index tests are the tile's)
       const double* b = q.a2[n];
       auto fb = [&](int dj, int di) {
         return dmax(F3(b, j + dj, i + di, k) * F2(f.rpsb, j + dj, i + di), d_zero);
       };
-      if (c->idiffu == 2) {
-        cd = cd + d_one * xkc * (o4_c1 * (fb(1, 0) + fb(-1, 0) + fb(0, 1) + fb(0, -1)) +
-                                 o4_c2 * (fb(1, 1) + fb(-1, -1) + fb(-1, 1) + fb(1, -1)) + o4_c3 * fb(0, 0));
-      } else {
-        if (in(j, g.jcii1, g.jcii2) && in(i, g.icii1, g.icii2))
-          cd = cd - d_one * xkc * (z4_c1 * (fb(2, 0) + fb(-2, 0) + fb(0, 2) + fb(0, -2)) +
-                                   z4_c2 * (fb(1, 0) + fb(-1, 0) + fb(0, 1) + fb(0, -1)) + z4_c3 * fb(0, 0));
-        const double lap = z4_c1 * (fb(1, 0) + fb(-1, 0) + fb(0, 1) + fb(0, -1)) + z4_c2 * fb(0, 0);
-        const int nb = (g.bl && j == g.jci1) + (g.br && j == g.jci2) + (g.bb && i == g.ici1) + (g.bt && i == g.ici2);
-        for (int r = 0; r < nb; r++) cd = cd + d_one * xkc * lap;
-      }
+      cd = diffu_x(g, c, j, i, cd, xkc, fb);
     }
     const double qt = d_zero + cd + (q.phy[n] ? F3(q.phy[n], j, i, k) : d_zero);
     F3(q.cq[n], j, i, k) = F3(q.a2[n], j, i, k) + dt * qt;
@@ -255,7 +224,6 @@ __global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q) {
   const uint32_t o3 = g.o3(j, i, k);
   const bool ci = in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
   const bool own = in(j, g.jde1, g.jde2) && in(i, g.ide1, g.ide2);
-  const double beta = 0.53;
   for (int n = 0; n < q.nsp; n++) {
     const double a1 = LD(q.a1[n], o3), a2 = LD(q.a2[n], o3);
     if (!ci) {
@@ -279,12 +247,10 @@ __global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q) {
       v = negfix_sum(g, q.cq[n], q.fq[n], j, i, k, false);
       ST(q.fq[n], o3, v);
     }
-    const double d = c->gnu2 * (v + a2 - d_two * a1);
-    double m = a1 + beta * d, x = v + (beta - d_one) * d;
-    if (m < d_zero) m = d_zero;
-    if (x < d_zero) x = d_zero;
-    ST(q.b2[n], o3, m);
-    ST(q.b1[n], o3, x);
+    double n1, n2;
+    raw_qc(c, a1, a2, v, n1, n2);
+    ST(q.b2[n], o3, n2);
+    ST(q.b1[n], o3, n1);
   }
 }
 
@@ -295,19 +261,16 @@ __global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q) {
 struct QxRaw {
   static constexpr int NI = 2;
   Geom g;
+  const Consts* c;
   const double *a1, *a2;
   double *b1, *b2;
-  double gnu2;
   int k;
   __device__ void load(int j, int i, double* x) const { x[0] = F3(a1, j, i, k); x[1] = F3(a2, j, i, k); }
   __device__ void apply(int j, int i, double v, const double* x) const {
-    const double beta = 0.53;
-    const double d = gnu2 * (v + x[1] - d_two * x[0]);
-    double m = x[0] + beta * d, y = v + (beta - d_one) * d;
-    if (m < d_zero) m = d_zero;
-    if (y < d_zero) y = d_zero;
-    F3(b2, j, i, k) = m;
-    F3(b1, j, i, k) = y;
+    double n1, n2;
+    raw_qc(c, x[0], x[1], v, n1, n2);
+    F3(b2, j, i, k) = n2;
+    F3(b1, j, i, k) = n1;
   }
 };
 // one (species, level) plane of k_qx_serial (lds: negfix_lds(g) doubles)
@@ -318,7 +281,10 @@ __device__ __forceinline__ void qx_serial_plane(const Geom& g, const Consts* __r
   const int n = plane / kz, k = plane % kz + 1;
   {
     // k_qx_fix's row flags into this plane's bitmap words (negfix_resolve reads those), flags
-    // cleared for the next step
+    // cleared for the next step.  negfix_collect's loop, but every word is stored where the
+    // helper ORs the non-zero ones in (the words are zero here: zero at allocation, marked by
+    // nothing else, cleared by negfix_resolve): the OR's load ahead of the barrier measured
+    // 0.5 us on k_negfix_serial_qx's serial chain (C3: 195.2-195.6 against 194.5-195.0 us)
     const int R = g.ici2 - g.ici1 + 1, T = (int)(blockDim.x * blockDim.y * blockDim.z);
     const int tid = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
     unsigned* fl = q.depf + plane * R;
@@ -366,7 +332,7 @@ __global__ void k_qx_post(Geom g, const Consts* __restrict__ c, QxArgs q) {
   const int plane = (int)blockIdx.z, kz = c->kz, n = plane / kz, k = plane % kz + 1;
   if (j > g.jci2 || i > g.ici2 || n >= q.nsp) return;
   if (!negfix_is_dependent(g, q.cq[n], j, i, k)) return;
-  const QxRaw acc{g, q.a1[n], q.a2[n], q.b1[n], q.b2[n], c->gnu2, k};
+  const QxRaw acc{g, c, q.a1[n], q.a2[n], q.b1[n], q.b2[n], k};
   double x[2];
   acc.load(j, i, x);
   acc.apply(j, i, F3(q.fq[n], j, i, k), x);

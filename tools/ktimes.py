@@ -1,7 +1,7 @@
 """Per-kernel device times of one configuration (HIP events around every launch, eager
 steps) plus the graph-replayed ms/step: the quick loop for kernel work.
 
-    python tools/ktimes.py [--config C3] [--steps 50] [--prof-steps 5]
+    python tools/ktimes.py [--config C3] [--steps 50] [--prof-steps 5] [--ipptls 2] [--isladvec 1]
 """
 import argparse
 import dataclasses
@@ -23,8 +23,9 @@ def main():
     ap.add_argument("--prof-steps", type=int, default=5)
     ap.add_argument("--nproc", default="1x1", help="local tiles jxi (all on this GPU)")
     ap.add_argument("--ipptls", type=int, default=1, help="2: nqx = 5 (qi, qr, qs with icbc.hydrometeor_state)")
+    ap.add_argument("--isladvec", type=int, default=0, help="1: semi-Lagrangian moisture advection (k_sladv)")
     args = ap.parse_args()
-    rc = dataclasses.replace(CONFIGS[args.config], ipptls=args.ipptls)
+    rc = dataclasses.replace(CONFIGS[args.config], ipptls=args.ipptls, isladvec=args.isladvec)
     data = icbc.generate_nh(rc) if rc.idynamic == 2 else icbc.generate(rc)
     st = dict(data["state"])
     if args.ipptls == 2:

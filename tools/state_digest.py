@@ -1,0 +1,94 @@
+"""One sha256 per named case over the raw bytes of the state and the tendency diagnostics after
+bdyval() and step(3) from the seeded state of regcm_amd/icbc.py: the bit-for-bit check of a
+kernel refactor.  Run it once under each engine library (RCMDYN_LIB) and compare the outputs
+line by line.
+
+    RCMDYN_LIB=varlib/var_parent.so python tools/state_digest.py > parent.txt
+    RCMDYN_LIB=varlib/var_new.so    python tools/state_digest.py > new.txt
+"""
+import dataclasses
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from regcm_amd import icbc  # noqa: E402
+from regcm_amd.config import (CONFIGS, NH_STATE_FIELDS, QX_STATE_FIELDS, STATE_FIELDS,  # noqa: E402
+                              TKE_STATE_FIELDS)
+from regcm_amd.dycore import DynCore  # noqa: E402
+
+TEND_DIAG = ["TTEN", "UTEN", "VTEN", "QVTEN", "QCTEN", "OMEGA", "XKC"]
+
+# (name, base config, RunConfig overrides, environment switches, local tiles)
+CASES = [("C1", "C1", {}, {}, (1, 1))]
+CASES += [(f"C1 {k}={v}", "C1", {k: v}, {}, (1, 1))
+          for k, v in (("iboudy", 1), ("iboudy", 4), ("idiffu", 2), ("idiffu", 3), ("isladvec", 1),
+                       ("upstream_mode", 0), ("stability_enhance", 0), ("ipptls", 2))]
+CASES += [(f"C1 ipptls=2 {k}={v}", "C1", {"ipptls": 2, k: v}, {}, (1, 1))
+          for k, v in (("idiffu", 2), ("idiffu", 3), ("isladvec", 1))]
+CASES += [
+    ("C1 ibltyp=2 iuwvadv=1", "C1", {"ibltyp": 2, "iuwvadv": 1}, {}, (1, 1)),
+    ("C1 NO_QFUSE", "C1", {}, {"RCMDYN_NO_QFUSE": "1"}, (1, 1)),
+    ("C1 ipptls=2 NO_QFUSE", "C1", {"ipptls": 2}, {"RCMDYN_NO_QFUSE": "1"}, (1, 1)),
+    ("C1 ipptls=2 NEGFIX_MODE=1", "C1", {"ipptls": 2}, {"RCMDYN_NEGFIX_MODE": "1"}, (1, 1)),
+    ("C1 2x2", "C1", {}, {}, (2, 2)),
+    ("C1 idiffu=2 2x2", "C1", {"idiffu": 2}, {}, (2, 2)),
+    ("C1 i_band=1", "C1", {"i_band": 1}, {}, (1, 1)),
+    ("N1", "N1", {}, {}, (1, 1)),
+]
+CASES += [(f"N1 {k}={v}", "N1", {k: v}, {}, (1, 1))
+          for k, v in (("iboudy", 4), ("idiffu", 2), ("idiffu", 3), ("isladvec", 1), ("ipptls", 2))]
+CASES += [
+    ("N1 ipptls=2 idiffu=2", "N1", {"ipptls": 2, "idiffu": 2}, {}, (1, 1)),
+    ("N1 NH_NO_TFUSE", "N1", {}, {"RCMDYN_NH_NO_TFUSE": "1"}, (1, 1)),
+    ("N1 2x2", "N1", {}, {}, (2, 2)),
+    ("CRM", "CRM", {}, {}, (1, 1)),
+]
+
+
+def digest(base, over, env, tiles):
+    rc = dataclasses.replace(CONFIGS[base], **over)
+    gen = icbc.generate_crm if rc.i_crm else icbc.generate_nh if rc.idynamic == 2 else icbc.generate
+    data = gen(rc)
+    st = dict(data["state"])
+    names = [n for n in STATE_FIELDS if rc.idynamic != 2 or n not in ("DSTOR", "HSTOR")]
+    if rc.idynamic == 2:
+        names += NH_STATE_FIELDS
+    if rc.ipptls == 2:
+        st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
+        names += QX_STATE_FIELDS
+    if rc.ibltyp == 2:
+        st.update({k: v for k, v in icbc.tke_state(rc).items() if k not in st})
+        names += TKE_STATE_FIELDS
+    if rc.iuwvadv == 1:     # a PBL top on every level 1..kz: vadv4d ind = 3 takes each of its branches
+        st["KPBL"] = np.random.Generator(np.random.PCG64(icbc.SEED)).integers(
+            1, rc.kz + 1, (1, rc.iy, rc.jx)).astype(np.float64)
+    os.environ.update(env)
+    try:
+        e = DynCore(rc, data["split"], nproc_j=tiles[0], nproc_i=tiles[1])
+    finally:
+        for k in env:
+            del os.environ[k]
+    e.put_state(st)
+    e.set_diagnostics(True)
+    e.bdyval()
+    e.step(3)
+    e.synchronize()
+    h = hashlib.sha256()
+    for n in names + TEND_DIAG:
+        h.update(n.encode())
+        h.update(np.ascontiguousarray(e.get(n)).tobytes())
+    e.close()
+    return h.hexdigest()
+
+
+def main():
+    for name, base, over, env, tiles in CASES:
+        print(f"{name:28s} {digest(base, over, env, tiles)}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
