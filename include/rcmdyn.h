@@ -346,6 +346,45 @@ int rcmdyn_last_step_ms(rcmdyn_t* h, double* ms);
  * results are identical either way. */
 int rcmdyn_set_diagnostics(rcmdyn_t* h, int32_t on);
 
+/* Tendency budget of t and qv (the reference's idiag = 1): off by default.  When on, every tend
+ * also adds, for each phase of tend, the change of the running dynamic tendency over that phase
+ * times rw to an accumulator, as mod_tendency does around its phases with ten0 / qen0 and
+ * ten2diag (Main/mod_tendency.F90:1276-1279, 1332-1376, 1465-1487, 1521-1530, 1557-1560,
+ * 1603-1606, 1673-1676, 2123-2175): tdiag / qdiag %adh (horizontal advection), adv (vertical
+ * advection), adi (adiabatic), bdy (boundary relaxation), dif (horizontal diffusion), the
+ * tten_* / qten_* variables of the ATM file (Main/mod_output.F90:668-871).  The accumulators
+ * are coupled with p* like aten, live on the interior cross points jci1:jci2 x ici1:ici2,
+ * k = 1..kz, and are zero elsewhere.  Each term is the rounded difference of two running sums,
+ * not the separately evaluated term.  With the reference's quirks: the NH core (ithadv = 1)
+ * books its whole theta path under T_ADH, never touches T_ADV and leaves T_ADI exactly 0;
+ * hydrostatic Q_ADI is exactly 0, NH Q_ADI is atmx%qx * cr; with isladvec = 1 Q_ADH is the
+ * semi-Lagrangian start; iboudy = 4 books the sponge value itself under *_BDY (no ten0), iboudy
+ * 1 and 5 the nudging increment, iboudy 0, 2, 3 nothing.  The *PHY tendencies, the NH Rayleigh
+ * damping and the physics terms (tbl, con, lsc, rad) stay the host's and enter no term.  The
+ * prognostic results and the TTEN.. diagnostics are identical with the budget on or off. */
+enum rcmdyn_budget_term {
+  RCMDYN_BUD_T_ADH = 0, RCMDYN_BUD_T_ADV, RCMDYN_BUD_T_ADI, RCMDYN_BUD_T_BDY, RCMDYN_BUD_T_DIF,
+  RCMDYN_BUD_Q_ADH, RCMDYN_BUD_Q_ADV, RCMDYN_BUD_Q_ADI, RCMDYN_BUD_Q_BDY, RCMDYN_BUD_Q_DIF,
+  RCMDYN_NBUDGET
+};
+/* Switches the budget on or off.  rw is the host's alarm_out_atm%rw (model_timestep / atmfrq,
+ * Main/mpplib/mod_timer.F90:300), applied from the next tend on; idgq is the species of qdiag
+ * and must be iqv = 1, the reference's default (another species is refused: the reference
+ * itself mixes iqv into that path, Main/mod_tendency.F90:1384-1391, 1559).  A non-finite or
+ * non-positive rw is refused.  The ten accumulators are allocated, zeroed, on the first call
+ * with on != 0 and keep their contents across later calls (off and on again, a new rw).  Waits
+ * for the device like rcmdyn_set_diagnostics. */
+int rcmdyn_set_budget(rcmdyn_t* h, int32_t on, int32_t idgq, double rw);
+/* Copies one accumulator (term: enum rcmdyn_budget_term) to the host, layout and global bounds
+ * as in rcmdyn_get; like rcmdyn_get it waits for the stream and reports step failures first.
+ * Fails while the budget is off and for a term out of range.  There is no put: the reference
+ * does not carry these sums through its SAV files either, so a restarted run starts them at
+ * zero. */
+int rcmdyn_get_budget(rcmdyn_t* h, int32_t term, double* dst,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+/* Zeroes the ten accumulators (mod_output's tdiag%x = d_zero after it wrote them). */
+int rcmdyn_reset_budget(rcmdyn_t* h);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

@@ -376,6 +376,15 @@ struct rcmdyn_engine {
   int red_total = 0;
   bool halo = false;          // ghost rings come from exchanges: a decomposition, or a band (periodic in j)
   bool diag = false;         // write the per-tend diagnostic fields
+  // tendency budget of t and qv (rcmdyn_set_budget): on, and the host's alarm_out_atm%rw
+  bool budget = false;
+  double bud_rw = 1.0;
+  Budget budget_args(const Tile& t) const {
+    Budget b{};
+    for (int q = 0; q < NBUDTERM; q++) { b.t[q] = t.bud[q]; b.q[q] = t.bud[NBUDTERM + q]; }
+    b.rw = bud_rw;
+    return b;
+  }
   KernelProf* prof = nullptr;  // set while rcmdyn_kernel_times runs
   double last_ms = 0.0;
   // parity of t, qv, qc: the step's ping-pong (hydrostatic), Tile::tq (NH)
@@ -728,6 +737,8 @@ struct rcmdyn_engine {
     const K ks[] = {{(const void*)k_update, SBT, "k_update"},
                     {(const void*)k_momentum, MBT, "k_momentum"},
                     {(const void*)k_scalars, SBT, "k_scalars"},
+                    {(const void*)k_update_bud, SBT, "k_update_bud"},
+                    {(const void*)k_scalars_bud, SBT, "k_scalars_bud"},
                     {(const void*)k_qx_tend, QBT, "k_qx_tend"}};
     for (const K& k : ks) {
       hipFuncAttributes a{};
@@ -1323,6 +1334,52 @@ struct rcmdyn_engine {
           for (int j = std::max(j1, g.jde1); j <= std::min(j2, g.jde2); j++)
             dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
     }
+  }
+
+  // Tendency budget of t and qv (idiag = 1): the switch, the host's read and its reset.  The
+  // accumulators are allocated (zeroed) on the first use and persist; rw is a kernel argument,
+  // so the captured graphs are dropped when it or the switch changes.
+  void set_budget(int on, int idgq, double rw) {
+    if (on) {
+      if (idgq != 1)
+        throw std::runtime_error("rcmdyn_set_budget: only the budget of qv (idgq = iqv = 1) is computed");
+      if (!(rw > 0.0) || !std::isfinite(rw))
+        throw std::runtime_error("rcmdyn_set_budget: rw must be finite and positive");
+    }
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    if (on && !tiles.empty() && !tiles[0].bud[0])
+      for (auto& t : tiles)
+        for (double*& d : t.bud) d = dalloc(t, t.g.plane * (size_t)cfg.kz);
+    const bool b = on != 0;
+    if (b != budget || (b && rw != bud_rw)) invalidate_graphs();
+    budget = b;
+    if (b) bud_rw = rw;
+  }
+  void get_budget(int term, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    settle();
+    if (!budget) throw std::runtime_error("rcmdyn_get_budget: the tendency budget is off (rcmdyn_set_budget)");
+    if (term < 0 || term >= RCMDYN_NBUDGET) throw std::runtime_error("rcmdyn_get_budget: unknown budget term");
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const int nk = cfg.kz;
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      std::vector<double> h((size_t)nk * g.plane);
+      HIPCHK(hipMemcpy(h.data(), t.bud[term], h.size() * 8, hipMemcpyDeviceToHost));
+      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
+        for (int i = std::max(i1, g.ide1); i <= std::min(i2, g.ide2); i++)
+          for (int j = std::max(j1, g.jde1); j <= std::min(j2, g.jde2); j++)
+            dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+    }
+  }
+  void reset_budget() {
+    settle();
+    if (!budget) throw std::runtime_error("rcmdyn_reset_budget: the tendency budget is off (rcmdyn_set_budget)");
+    HIPCHK(hipStreamSynchronize(stream));
+    for (auto& t : tiles)
+      for (double* d : t.bud) HIPCHK(hipMemset(d, 0, t.g.plane * (size_t)cfg.kz * sizeof(double)));
   }
 
   // ------------------------------------------------------------------ halo exchange
@@ -2011,11 +2068,18 @@ struct rcmdyn_engine {
     const Geom& g = t.g;
     const dim3 gc((g.nj + TC_J - 1) / TC_J, (g.ni + TC_I - 1) / TC_I, cfg.kz + 1);
     if (hc.nsp) {
-      KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-              (int)diag, istep);
+      if (budget)
+        KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+                (int)diag, istep, budget_args(t));
+      else
+        KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+                (int)diag, istep);
       // the chains of qi, qr, qs after it on the same stream
       KLAUNCH(k_nh_qx_tend, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0, stream, g, dc, ds, f,
               qx_args(t));
+    } else if (budget) {
+      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+              (int)diag, istep, budget_args(t));
     } else {
       KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
               (int)diag, istep);
@@ -2171,15 +2235,22 @@ struct rcmdyn_engine {
     if (sw.fuse_update && pm >= 0 && ps >= 0) {
       const int mnx = (mj2 - mo + MBJ) / MBJ, mny = (mi2 - g.idi1 + MBI) / MBI;
       const int snx = (g.jcx2() - so + SBJ) / SBJ, sny = (g.icx2() - g.icx1() + SBI) / SBI;
-      KLAUNCH(k_update, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc, ds,
-              fields(t, pm), fields(t, ps), mnx, mny, snx, sny,
-              (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW));
+      const int xcd = (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW);
+      if (budget)
+        KLAUNCH(k_update_bud, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc,
+                ds, fields(t, pm), fields(t, ps), mnx, mny, snx, sny, xcd, budget_args(t));
+      else
+        KLAUNCH(k_update, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc, ds,
+                fields(t, pm), fields(t, ps), mnx, mny, snx, sny, xcd);
       return;
     }
     if (pm >= 0)
       KLAUNCH(k_momentum, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz), dim3(MBT), 0,
               stream, g, dc, ds, fields(t, pm));
-    if (ps >= 0)
+    if (ps >= 0 && budget)
+      KLAUNCH(k_scalars_bud, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
+              dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t));
+    else if (ps >= 0)
       KLAUNCH(k_scalars, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
               dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
   }
@@ -2949,6 +3020,17 @@ int rcmdyn_set_diagnostics(rcmdyn_t* h, int32_t on) {
     }
   });
 }
+
+int rcmdyn_set_budget(rcmdyn_t* h, int32_t on, int32_t idgq, double rw) {
+  return guard(h, [&] { h->set_budget(on, idgq, rw); });
+}
+
+int rcmdyn_get_budget(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                      int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_budget(term, dst, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_reset_budget(rcmdyn_t* h) { return guard(h, [&] { h->reset_budget(); }); }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,
                         int32_t* count) {

@@ -215,6 +215,9 @@ struct Tile {
   double *deld, *delh, *ddsum, *dhsum, *uu, *vv;
   // diagnostics of the last tend
   double *tten, *uten, *vten, *qvten, *qcten, *omega, *xkcs;
+  // tendency budget of t and qv (rcmdyn_set_budget; allocated on its first use): tdiag then
+  // qdiag %adh, adv, adi, bdy, dif, in rcmdyn_budget_term order
+  double *bud[RCMDYN_NBUDGET] = {};
   // boundary slices (Main/mod_bdycod.F90:58-61): [k][frame index]
   double *sl[16];
   // wide frame of the fused split step on a decomposed domain (2-D inputs, ghost depth SPH)

@@ -942,9 +942,16 @@ struct ScaLDS {
   double sPS[SH1][SW1], sXT[SH1][SW1], sXQV[SH1][SW1], sXQC[SH1][SW1];
   double sTB[SH2][SW2], sQVB[SH2][SW2], sQCB[SH2][SW2];
 };
+// BUD: the budget instance (rcmdyn_set_budget).  It snapshots the running dynamic tendency
+// around each stage as tend does with ten0 / qen0 (Main/mod_tendency.F90:1276-1279, 1332-1376,
+// 1465-1487, 1521-1530, 1557-1560, 1673-1676) and adds the difference times rw to the stage's
+// accumulator (ten2diag, :2123-2175) at the tile's own interior points.  Hydrostatic qv has no
+// adiabatic term (its difference is 0 exactly: qdiag%adi is left alone); iboudy = 4 adds the
+// sponge value itself (pc_total, no ten0); iboudy 0, 2, 3 never write the bdy term.
+template <bool BUD>
 __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __restrict__ c,
                                               const StepState* __restrict__ s, const Fields& f, ScaLDS& L,
-                                              int bx, int by, int bz) {
+                                              int bx, int by, int bz, const Budget& b) {
   auto& sUMC = L.sUMC; auto& sVMC = L.sVMC; auto& sUD = L.sUD; auto& sVD = L.sVD; auto& sUB = L.sUB;
   auto& sVB = L.sVB; auto& sPS = L.sPS; auto& sXT = L.sXT; auto& sXQV = L.sXQV; auto& sXQC = L.sXQC;
   auto& sTB = L.sTB; auto& sQVB = L.sQVB; auto& sQCB = L.sQCB;
@@ -1074,6 +1081,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   const double dt = s->dt;
   const int b1 = tj + 1, a1 = ti + 1, b2 = tj + 2, a2 = ti + 2;
+  // budget: acc = acc + (after - before) * rw at an owned interior point
+  const bool bown = BUD && in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
+  const bool bbdy = c->iboudy == 1 || c->iboudy == 4 || c->iboudy == 5;
+  auto bud = [&](double* acc, double after, double before) {
+    if (bown) ST(acc, o3, LD(acc, o3) + (after - before) * b.rw);
+  };
 #define H1T(S, dj, di) S[a1 + (di)][b1 + (dj)]
   // mass fluxes of the cell (shared by the three scalars)
   const double uavg1 = DT(sUMC, 0, 1) + DT(sUMC, 0, 0);
@@ -1093,6 +1106,8 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   {
     double td = d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXT, 0, 0), H1T(sXT, -1, 0),
                                    H1T(sXT, 1, 0), H1T(sXT, 0, -1), H1T(sXT, 0, 1), 1);
+    double t0 = td;
+    if constexpr (BUD) bud(b.t[0], td, d_zero);
     // vadv3d ind = 1 (Main/mod_advection.F90:771-783): pf/pb from psb (mkslice :263-271)
     {
       const double ptop = c->ptop, c287 = c->c287;
@@ -1107,6 +1122,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
 #undef PB
 #undef PF
     }
+    if constexpr (BUD) { bud(b.t[1], td, t0); t0 = td; }
     // omega, Main/mod_tendency.F90:1200-1214
     double om;
     {
@@ -1124,6 +1140,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       const double rovcpm = c->rgas / (c->cpd * (d_one + 0.80 * qv));
       td = td + (om * rovcpm * tv) / (c->ptop * rp + c->hsigma[k]);
     }
+    if constexpr (BUD) { bud(b.t[2], td, t0); t0 = td; }
     // nudge3d (iboudy 1/5) or the sponge3d summand (iboudy 4, see k_momentum)
     double spt = d_zero;
     if (rgc > 0 && c->iboudy == 4) {
@@ -1137,7 +1154,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       td = relax(td, xf, xg, FGT(0, 0), FGT(-1, 0), FGT(1, 0), FGT(0, -1), FGT(0, 1));
 #undef FGT
     }
+    if constexpr (BUD) {
+      if (bbdy) bud(b.t[3], c->iboudy == 4 ? spt : td, c->iboudy == 4 ? d_zero : t0);
+      t0 = td;
+    }
     td = diffu(td, sTB, f.d6t);
+    if constexpr (BUD) bud(b.t[4], td, t0);
     // tten + tdyn + tphy (:285-288), then the SUBEX condensation term (:332-341, stubbed)
     // (pc_physic of the coupling seam, loaded here to keep registers free: absent = 0)
     const double tt = ((spt + td) + (f.tphy ? LD(f.tphy, o3) : d_zero)) + d_zero;
@@ -1153,6 +1175,8 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
                           : d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXQV, 0, 0),
                                                H1T(sXQV, -1, 0), H1T(sXQV, 1, 0), H1T(sXQV, 0, -1),
                                                H1T(sXQV, 0, 1), 2);
+  double tq0 = tq;
+  if constexpr (BUD) bud(b.q[0], tq, d_zero);
   {
     const double thr = MINQQ * ps;
     const double qc0 = qv1;
@@ -1165,6 +1189,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       tq = tq - q1 * ((qp > thr && qc0 > thr) ? qp * powpos(qc0 / qp, c->qcon[k + 1]) : d_zero) * c->xds[k];
     }
   }
+  if constexpr (BUD) { bud(b.q[1], tq, tq0); tq0 = tq; }
   double spq = d_zero;
   if (rgc > 0 && c->iboudy == 4) {
     const int ib = f.ibcr[o2 >> 3];
@@ -1179,7 +1204,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
 #undef FGQ
     tq = tq + rfac * (xf * f0 - xg * (f1 + f2 + f3 + f4 - d_four * f0));
   }
+  if constexpr (BUD) {
+    if (bbdy) bud(b.q[3], c->iboudy == 4 ? spq : tq, c->iboudy == 4 ? d_zero : tq0);
+    tq0 = tq;
+  }
   tq = diffu(tq, sQVB, f.d6qv);
+  if constexpr (BUD) bud(b.q[4], tq, tq0);
   // the qv sums and forecast (and with qfuse its RAW filter) before the qc chain, so the qv
   // operands are dead while it runs
   tq = ((spq + tq) + (f.qvphy ? LD(f.qvphy, o3) : d_zero)) + d_zero;
@@ -1233,7 +1263,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
 __global__ __launch_bounds__(SBT, SC_LB) void k_scalars(Geom g, const Consts* __restrict__ c,
                                                     const StepState* __restrict__ s, Fields f) {
   __shared__ ScaLDS L;
-  scalars_block(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+  scalars_block<false>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts* __restrict__ c,
+                                                        const StepState* __restrict__ s, Fields f, Budget b) {
+  __shared__ ScaLDS L;
+  scalars_block<true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b);
 }
 
 // k_momentum and k_scalars in one launch: blockIdx.z < kz a scalars block of level z + 1, else
@@ -1255,7 +1290,22 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __r
   if (mom) {
     if (bx < mnx && by < mny) momentum_block(g, c, s, fm, L.m, bx, by, lz);
   } else if (bx < snx && by < sny) {
-    scalars_block(g, c, s, fs, L.s, bx, by, lz);
+    scalars_block<false>(g, c, s, fs, L.s, bx, by, lz, Budget{});
+  }
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_update_bud(Geom g, const Consts* __restrict__ c,
+                                                       const StepState* __restrict__ s, Fields fm, Fields fs,
+                                                       int mnx, int mny, int snx, int sny, int xcd, Budget b) {
+  __shared__ union { MomLDS m; ScaLDS s; } L;
+  const int kz = c->kz, bz = (int)blockIdx.z;
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+  if (xcd) xcd_tile2d(bx, by);
+  const bool mom = bz >= kz;
+  const int lz = mom ? bz - kz : bz;
+  if (mom) {
+    if (bx < mnx && by < mny) momentum_block(g, c, s, fm, L.m, bx, by, lz);
+  } else if (bx < snx && by < sny) {
+    scalars_block<true>(g, c, s, fs, L.s, bx, by, lz, b);
   }
 }
 

@@ -143,6 +143,18 @@ struct Fields {
   Part pt;                     // the launch's overlap part (k_columns, k_momentum, k_scalars)
 };
 
+// Tendency budget of t and qv (idiag = 1, rcmdyn_set_budget): the accumulators tdiag / qdiag
+// %adh, adv, adi, bdy, dif of ten2diag (Main/mod_tendency.F90:2123-2175), frame planes like tten,
+// and the host's alarm_out_atm%rw.  An argument of its own of the budget instances of the
+// tendency kernels (k_scalars_bud, k_update_bud, k_nh_tend_c_bud); the default instances take
+// none and hold no code for it.  Each term is the rounded difference of the running tendency
+// around its stage, acc = acc + (after - before) * rw, on the tile's own interior cross points.
+constexpr int NBUDTERM = 5;          // adh, adv, adi, bdy, dif
+struct Budget {
+  double *t[NBUDTERM], *q[NBUDTERM];
+  double rw;
+};
+
 // nqx = 5: the hydrometeors beyond qc (qi, qr, qs) for the current (a*) and next (b*) time-level
 // buffers (species.hip; the non-hydrostatic core updates a* in place and leaves b* null)
 struct QxArgs {
@@ -187,6 +199,11 @@ __global__ void k_diffu6(Geom g, const Consts* __restrict__ c, Fields f, QxArgs 
 __global__ void k_scalars(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
 __global__ void k_update(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm, Fields fs,
                          int mnx, int mny, int snx, int sny, int xcd);
+// the budget instances of the two (the scalars blocks also accumulate the tendency budget)
+__global__ void k_scalars_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
+                              Budget b);
+__global__ void k_update_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
+                             Fields fs, int mnx, int mny, int snx, int sny, int xcd, Budget b);
 __global__ void k_qfilter(Geom g, const Consts* __restrict__ c, Fields f);
 // the serial fix passes resolve the chain (qxcommon.hpp), k_negfix_post / k_qx_post apply the
 // filters of the points they fixed

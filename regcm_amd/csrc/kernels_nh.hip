@@ -349,10 +349,21 @@ constexpr int TC_NF = 5;
             FG(b0, bt, a, j, i - 1), FG(b0, bt, a, j, i + 1))
 #define PHY(p) (f.p ? F3(f.p, j, i, k) : 0.0)
 #if !NH_OTHER_KERNELS
-template <bool QX>
+// B: empty, or Budget for the budget instance (rcmdyn_set_budget), which takes the accumulators
+// of the tendency budget of t and qv as a trailing argument b and adds acc = acc + (after -
+// before) * rw at the tile's interior points, with tend's snapshots: t adh is the whole theta
+// path (ten0 is taken before it and reset after it, Main/mod_tendency.F90:1595-1606), so
+// tdiag%adv is never touched and tdiag%adi is 0 exactly (both left alone); qv adi is atmx%qx *
+// cr (:1615-1617); the Rayleigh damping and the physics tendencies enter no term.  The default
+// instance has the signature and the code it had without the budget (an empty pack, not a shared
+// __device__ body: called from two kernels, the body was scheduled differently in the default one
+// under this file's device scheduler, 3 376 -> 3 390 VALU instructions and 128 -> 130 VGPRs).
+__device__ __forceinline__ const Budget& budget_arg(const Budget& b) { return b; }
+template <bool QX, class... B>
 __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* __restrict__ c,
                                                    const StepState* __restrict__ s, NHFields f, int wdiag,
-                                                   int istep) {
+                                                   int istep, B... b) {
+  constexpr bool BUD = sizeof...(B) != 0;
   // the horizontal stencil operands of this level for the 32 x 8 block and a 2-point halo,
   // staged in LDS once: the diffusion fields (13-point).  Staging the advected fields or the
   // relaxation differences as well measured slower at C5 (3.36 ms diffusion only, 3.66 ms
@@ -565,6 +576,14 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
                     ((c->crm ? d_zero : F3(f.ppb0, j, i, k) + xt * F3(f.ppbt, j, i, k)) - F3(f.a2pp, j, i, k));
     F3(f.ppten, j, i, k) = (pt * F2(f.rpsa, j, i)) * dts;
   }
+  // budget: var 0 t, 1 qv; term 0 adh, 1 adv, 2 adi, 3 bdy, 4 dif
+  auto bud = [&](int var, int term, double after, double before) {
+    if constexpr (BUD) {
+      const Budget& bb = budget_arg(b...);
+      double* acc = var ? bb.q[term] : bb.t[term];
+      F3(acc, j, i, k) = F3(acc, j, i, k) + (after - before) * bb.rw;
+    }
+  };
   const bool ray = c->ifrayd == 1 && k <= c->rayndamp && !c->crm;   // no t/qv damping in CRM mode (:359)
   const double tau = ray ? nh_tau(c, F3(f.z0, j, i, k), F3(f.z0, j, i, 1)) : d_zero;
   // ================= t, ithadv = 1 (:1347-1356, 1594-1600): thten = hadvt of th, then vadv3d
@@ -581,10 +600,18 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     const double th = F3(f.th, j, i, k);
     thd = thd + th * cr;
     double td = d_zero + F3(f.a1t, j, i, k) * thd / (th * ps);
+    double tb = td;
+    if constexpr (BUD) bud(0, 0, td, d_zero);
     double tt0 = d_zero;
     if (sponge) tt0 = wsp * d_zero + (d_one - wsp) * F3(f.tbt, j, i, k);
     if (nudge) RELAX5(td, f.tb0, f.tbt, f.a2t);
+    if constexpr (BUD) {
+      if (c->iboudy == 4) bud(0, 3, tt0, d_zero);
+      else if (c->iboudy == 1 || c->iboudy == 5) bud(0, 3, td, tb);
+      tb = td;
+    }
     td = c->idiffu == 3 ? diff6_add(g, td, f.d6t, g.jci2, j, i, k) : diffx_l(g, c, td, sT[0], xkc, j, i, ti, tj);
+    if constexpr (BUD) bud(0, 4, td, tb);
     double tt = tt0 + td + PHY(tphy);
     tt = tt + 0.0;
     if (ray) tt = tt + tau * ((F3(f.tb0, j, i, k) + xt * F3(f.tbt, j, i, k)) - F3(f.a2t, j, i, k));
@@ -598,6 +625,8 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   {
     double qd = d_zero + (c->isladvec ? F3(f.slqv, j, i, k)
                                       : hadx(f.a1qv, 1, u1, u2, v1, v2, 2));
+    double qb = qd;
+    if constexpr (BUD) bud(1, 0, qd, d_zero);
     const double thr = MINQQ * ps;
     auto qflux = [&](int kk) {
       const double fk = F3(f.a1qv, j, i, kk), fkm = F3(f.a1qv, j, i, kk - 1);
@@ -607,7 +636,9 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     };
     if (k >= 2) qd = qd + qflux(k) * c->xds[k];
     if (k + 1 <= kz) qd = qd - qflux(k + 1) * c->xds[k];
+    if constexpr (BUD) { bud(1, 1, qd, qb); qb = qd; }
     qd = qd + dmax(F3(f.a1qv, j, i, k) * r0, MINQQ) * cr;
+    if constexpr (BUD) { bud(1, 2, qd, qb); qb = qd; }
     double qt0 = d_zero;
     if (sponge) qt0 = wsp * d_zero + (d_one - wsp) * F3(f.qbt, j, i, k);
     if (nudge) {
@@ -617,7 +648,13 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
 #undef FQ
       qd = qd + rfac * (xf * q0 - xg * (q1 + q2 + q3 + q4 - d_four * q0));
     }
+    if constexpr (BUD) {
+      if (c->iboudy == 4) bud(1, 3, qt0, d_zero);
+      else if (c->iboudy == 1 || c->iboudy == 5) bud(1, 3, qd, qb);
+      qb = qd;
+    }
     qd = c->idiffu == 3 ? diff6_add(g, qd, f.d6qv, g.jci2, j, i, k) : diffx_l(g, c, qd, sT[1], xkc, j, i, ti, tj);
+    if constexpr (BUD) bud(1, 4, qd, qb);
     double qv = qt0 + qd + PHY(qvphy);
     qv = qv + 0.0;
     if (ray) qv = qv + tau * ((F3(f.qb0, j, i, k) + xt * F3(f.qbt, j, i, k)) - F3(f.a2qv, j, i, k));
@@ -664,6 +701,10 @@ template __global__ void k_nh_tend_c<false>(Geom, const Consts* __restrict__, co
                                              int, int);
 template __global__ void k_nh_tend_c<true>(Geom, const Consts* __restrict__, const StepState* __restrict__, NHFields,
                                             int, int);
+template __global__ void k_nh_tend_c<false, Budget>(Geom, const Consts* __restrict__, const StepState* __restrict__,
+                                                     NHFields, int, int, Budget);
+template __global__ void k_nh_tend_c<true, Budget>(Geom, const Consts* __restrict__, const StepState* __restrict__,
+                                                    NHFields, int, int, Budget);
 #endif
 #if NH_OTHER_KERNELS
 

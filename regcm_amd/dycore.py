@@ -31,7 +31,12 @@ EXPORTED = [
     "rcmdyn_comm_unique_id", "rcmdyn_last_step_ms", "rcmdyn_set_diagnostics", "rcmdyn_kernel_times",
     "rcmdyn_tend_pre_physics", "rcmdyn_tend_post_physics", "rcmdyn_bdyin", "rcmdyn_reductions", "rcmdyn_runtime_info",
     "rcmdyn_exchange_plan", "rcmdyn_overlap_shares",
+    "rcmdyn_set_budget", "rcmdyn_get_budget", "rcmdyn_reset_budget",
 ]
+
+# enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
+BUDGET_TERMS = ["T_ADH", "T_ADV", "T_ADI", "T_BDY", "T_DIF", "Q_ADH", "Q_ADV", "Q_ADI", "Q_BDY", "Q_DIF"]
+IQV = 1    # the reference's index of water vapour (Main/mpplib/mod_runparams.F90:38)
 
 
 class EngineError(RuntimeError):
@@ -77,6 +82,9 @@ def lib():
                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.rcmdyn_overlap_shares.argtypes = [ctypes.POINTER(RcmdynConfig), ctypes.POINTER(i32), i32]
     L.rcmdyn_kernel_times.argtypes = [P, i32, i32, ctypes.c_char_p, ctypes.POINTER(i32), dp, ctypes.POINTER(i32)]
+    L.rcmdyn_set_budget.argtypes = [P, i32, i32, ctypes.c_double]
+    L.rcmdyn_get_budget.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_reset_budget.argtypes = [P]
     _lib = L
     return L
 
@@ -252,6 +260,24 @@ class DynCore:
 
     def set_diagnostics(self, on: bool = True):
         self._check(lib().rcmdyn_set_diagnostics(self.h, 1 if on else 0))
+
+    def set_budget(self, on: bool = True, idgq: int = IQV, rw: float = 1.0):
+        """The tendency budget of t and qv (idiag = 1): every later tend adds each term times rw
+        (the host's alarm_out_atm%rw) to its accumulator; only idgq = iqv is computed."""
+        self._check(lib().rcmdyn_set_budget(self.h, 1 if on else 0, idgq, rw))
+
+    def get_budget(self, term) -> np.ndarray:
+        """One accumulator, by name (BUDGET_TERMS) or number, as a (kz, iy, jx) array: zero
+        outside the interior cross points."""
+        n = BUDGET_TERMS.index(term) if isinstance(term, str) else int(term)
+        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
+        self._check(lib().rcmdyn_get_budget(self.h, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
+        return out
+
+    def reset_budget(self):
+        """Zeroes the ten accumulators (the host does it after writing them to the ATM file)."""
+        self._check(lib().rcmdyn_reset_budget(self.h))
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

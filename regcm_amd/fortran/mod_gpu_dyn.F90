@@ -46,6 +46,13 @@ module mod_gpu_dyn
     f_atm2_qs = 114, f_qiphy = 115, f_qrphy = 116, f_qsphy = 117, &
     f_atms_qxb3d_qi = 118, f_atms_qxb3d_qr = 119, f_atms_qxb3d_qs = 120
 
+  ! tendency budget terms of t and qv (enum rcmdyn_budget_term; the reference's idiag = 1:
+  ! tdiag / qdiag %adh, adv, adi, bdy, dif) and the species the budget of qv follows
+  integer(c_int32_t), parameter, public :: &
+    bud_t_adh = 0, bud_t_adv = 1, bud_t_adi = 2, bud_t_bdy = 3, bud_t_dif = 4, &
+    bud_q_adh = 5, bud_q_adv = 6, bud_q_adi = 7, bud_q_bdy = 8, bud_q_dif = 9, &
+    rcmdyn_nbudget = 10
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -223,6 +230,27 @@ module mod_gpu_dyn
       type(c_ptr), value :: h
       integer(c_int32_t), value :: on
     end function
+    ! the tendency budget of t and qv on (1) or off (0, the default); idgq must be iqv, rw is
+    ! alarm_out_atm%rw
+    integer(c_int) function rcmdyn_set_budget(h, on, idgq, rw) bind(c, name='rcmdyn_set_budget')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on, idgq
+      real(c_double), value :: rw
+    end function
+    ! one accumulator (bud_t_adh .. bud_q_dif) into dst(j1:j2,i1:i2,k1:k2)
+    integer(c_int) function rcmdyn_get_budget(h, term, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_budget')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: term, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
+    ! zeroes the ten accumulators (after the host wrote them to the ATM file)
+    integer(c_int) function rcmdyn_reset_budget(h) bind(c, name='rcmdyn_reset_budget')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -241,7 +269,7 @@ module mod_gpu_dyn
   public :: rcmdyn_tend_pre_physics, rcmdyn_tend_post_physics, rcmdyn_bdyin, rcmdyn_last_error
   public :: rcmdyn_synchronize, rcmdyn_set_nproc, rcmdyn_tile_extent, rcmdyn_tile_extent_cfg, rcmdyn_exchange_plan
   public :: rcmdyn_overlap_shares, rcmdyn_runtime_info, rcmdyn_last_step_ms, rcmdyn_set_diagnostics
-  public :: rcmdyn_kernel_times
+  public :: rcmdyn_kernel_times, rcmdyn_set_budget, rcmdyn_get_budget, rcmdyn_reset_budget
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains
