@@ -385,6 +385,41 @@ int rcmdyn_get_budget(rcmdyn_t* h, int32_t term, double* dst,
 /* Zeroes the ten accumulators (mod_output's tdiag%x = d_zero after it wrote them). */
 int rcmdyn_reset_budget(rcmdyn_t* h);
 
+/* Mass check of tend (the reference's `if ( debug_level > 0 ) call massck`,
+ * Main/mod_tendency.F90:415, Main/mod_massck.F90:190-306, the idynamic /= 3 branch): off by
+ * default.  When on, every tend also sums, over the tiles this engine owns, from atm1 and sfs%psa
+ * as they stand after tend's prologue exchange:
+ *   drymass = (sum_k (sum_{jci,ici} psa) * dsigma(k)) * dxsq * 1000 * regrav
+ *   qmass   = (sum_{n=1..nqx} sum_k (sum_{jci,ici} atm1%qx(:,:,k,n)) * dsigma(k)) * dxsq * 1000 * regrav
+ *   dryadv  = the dry-air flux through the boundary lines a tile has, +- dt*3.e4*dsigma(k)*dx*regrav*f,
+ *             west/east f = atm1%u(jde1|jde2,i+1,k) + atm1%u(jde1|jde2,i,k), i = ice1..ice2,
+ *             south/north f = atm1%v(j+1,ide1|ide2,k) + atm1%v(j,ide1|ide2,k), j = jci1..jci2;
+ *             inflow positive; dt is the clock's leapfrog dt before the tend (rcmdyn_get_time)
+ *   qadv    = the same with f * atm1%qx / psa of the adjacent cross point, over every species
+ * A periodic side (i_band, i_crm) has no line.  One record of six doubles per tend,
+ *   { lcount, dt, drymass, dryadv, qmass, qadv }     (lcount, dt: the clock before the tend)
+ * goes to a ring of cap records on the device, inside the captured step: nothing is copied and
+ * no collective is issued until rcmdyn_get_massck.  The sums are fixed trees (no atomics): the
+ * same run gives the same bits.  The prognostic results are identical with the check on or off,
+ * and with it off the step issues no launch of it.  The scalar part of massck (the drift in %,
+ * the 24-hour means, the daily report; :69-70, 312-364) stays the host's, with its rain and
+ * evaporation sums (regcm_amd/massck.py restates it).
+ *
+ * rcmdyn_set_massck: on != 0 switches the check on with an empty log of cap records, 1 <= cap <=
+ * 65536 (refused otherwise, the switch staying as it was; cap is not read when on == 0).  A call
+ * that repeats the current on and cap keeps the log.  Waits for the device like
+ * rcmdyn_set_budget.
+ * rcmdyn_get_massck: like rcmdyn_get it waits for the stream and reports step failures first;
+ * then copies the records of the tends since the previous rcmdyn_get_massck (or the switch-on)
+ * to out[6 * cap], oldest first, at most min(cap, the log's cap) of them, the newest ones;
+ * *count is the number copied, *lost the number of older ones the ring overwrote or out had no
+ * room for.  The log is empty afterwards.  Fails with "the mass check is off" while it is off.
+ * On a job whose tiles span ranks every rank's log holds its own tiles' sums, and this call adds
+ * the four sums of each record over the job (the reference's sumall): it is then collective
+ * like rcmdyn_reductions, every rank calling it with the same cap after the same tends. */
+int rcmdyn_set_massck(rcmdyn_t* h, int32_t on, int32_t cap);
+int rcmdyn_get_massck(rcmdyn_t* h, double* out, int32_t cap, int32_t* count, int64_t* lost);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

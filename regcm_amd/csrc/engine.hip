@@ -33,6 +33,7 @@
 #include "bdyin.hpp"
 #include "tke.hpp"
 #include "fieldtab.hpp"
+#include "massck.hpp"
 
 using namespace rcm;
 
@@ -385,6 +386,16 @@ struct rcmdyn_engine {
     b.rw = bud_rw;
     return b;
   }
+  // mass check of tend (rcmdyn_set_massck; massck.hip): the switch, the ring's capacity, the
+  // tiles' slots with k_massck_final's table of them, the device log (its counter, then the
+  // records) and the counter's value at the host's last read
+  bool massck = false;
+  int mck_cap = 0;
+  std::vector<MassckTile> mck_lay;
+  double* mck_part = nullptr;
+  MassckTile* mck_tab = nullptr;
+  double* mck_log = nullptr;
+  long long mck_seen = 0;
   KernelProf* prof = nullptr;  // set while rcmdyn_kernel_times runs
   double last_ms = 0.0;
   // parity of t, qv, qc: the step's ping-pong (hydrostatic), Tile::tq (NH)
@@ -909,6 +920,9 @@ struct rcmdyn_engine {
     if (dc) (void)hipFree(dc);
     if (ds) (void)hipFree(ds);
     if (red) (void)hipFree(red);
+    if (mck_part) (void)hipFree(mck_part);
+    if (mck_tab) (void)hipFree(mck_tab);
+    if (mck_log) (void)hipFree(mck_log);
 
     if (evfork) (void)hipEventDestroy(evfork);
     for (hipEvent_t e : evjoin)
@@ -1380,6 +1394,98 @@ struct rcmdyn_engine {
     HIPCHK(hipStreamSynchronize(stream));
     for (auto& t : tiles)
       for (double* d : t.bud) HIPCHK(hipMemset(d, 0, t.g.plane * (size_t)cfg.kz * sizeof(double)));
+  }
+
+  // Mass check of tend (Main/mod_massck.F90:190-306): the switch, the launches tend issues after
+  // its prologue exchange, and the host's read of the log.  The log's capacity is a kernel
+  // argument, so the captured graphs are dropped when it or the switch changes.
+  static constexpr int MCK_HEAD = 8;     // doubles before the first record (the device counter)
+  long long* mck_count() const { return reinterpret_cast<long long*>(mck_log); }
+  void set_massck(int on, int cap) {
+    if (on && (cap < 1 || cap > 65536))
+      throw std::runtime_error("rcmdyn_set_massck: cap must be between 1 and 65536 records");
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    const bool b = on != 0;
+    if (b == massck && (!b || cap == mck_cap)) return;   // the same switch: the log is kept
+    invalidate_graphs();
+    if (b) {
+      if (!mck_part) {
+        int off = 0;
+        for (auto& t : tiles) {
+          const Geom& g = t.g;
+          const int line = std::max(g.ice2 - g.ice1 + 1, g.jci2 - g.jci1 + 1);
+          const int nbchunk = std::max(1, (line + 255) / 256);
+          MassckTile m{off, 4 * nbchunk * cfg.kz, (g.ici2 - g.ici1 + MCK_ROWS) / MCK_ROWS, nbchunk};
+          off += 2 * m.nbdy + (hc.nqx * cfg.kz + 1) * m.nchunk;
+          mck_lay.push_back(m);
+        }
+        HIPCHK(hipMalloc((void**)&mck_part, sizeof(double) * (size_t)off));
+        HIPCHK(hipMemset(mck_part, 0, sizeof(double) * (size_t)off));
+        HIPCHK(hipMalloc((void**)&mck_tab, sizeof(MassckTile) * mck_lay.size()));
+        HIPCHK(hipMemcpy(mck_tab, mck_lay.data(), sizeof(MassckTile) * mck_lay.size(), hipMemcpyHostToDevice));
+      }
+      if (mck_log) { (void)hipFree(mck_log); mck_log = nullptr; }
+      const size_t n = sizeof(double) * (MCK_HEAD + (size_t)cap * MCK_NREC);
+      HIPCHK(hipMalloc((void**)&mck_log, n));
+      HIPCHK(hipMemset(mck_log, 0, n));
+      mck_cap = cap;
+      mck_seen = 0;
+    }
+    massck = b;
+  }
+  // k_massck of every owned tile, then k_massck_final, on the engine's stream: after the exchange
+  // that fills the ghost points the boundary lines read (u at i + 1, v at j + 1), before anything
+  // of the step writes atm1 or p* of the current parity
+  void massck_launch() {
+    if (!massck) return;
+    for (size_t q = 0; q < tiles.size(); q++) {
+      Tile& t = tiles[q];
+      const MassckTile& m = mck_lay[q];
+      MassckArgs a{};
+      a.u = fptr(t, FK::A1U); a.v = fptr(t, FK::A1V); a.psa = fptr(t, FK::PSA);
+      a.qx[0] = fptr(t, FK::A1QV); a.qx[1] = fptr(t, FK::A1QC);
+      for (int n = 0; n < hc.nsp; n++) a.qx[2 + n] = fptr(t, fkq(FK::A1QX0, n));
+      a.nqx = hc.nqx;
+      a.part = mck_part + m.off;
+      a.nbdy = m.nbdy; a.nbchunk = m.nbchunk; a.nchunk = m.nchunk;
+      KLAUNCH(k_massck, dim3(m.nbdy + (hc.nqx * cfg.kz + 1) * m.nchunk), BLK, 0, stream, t.g, dc, ds, a);
+    }
+    KLAUNCH(k_massck_final, dim3(1), dim3(256), 0, stream, dc, ds, mck_part, mck_tab, (int)tiles.size(), hc.nqx,
+            mck_log + MCK_HEAD, mck_count(), mck_cap);
+  }
+  void get_massck(double* out, int cap, int32_t* count, int64_t* lost) {
+    settle();
+    if (!massck) throw std::runtime_error("rcmdyn_get_massck: the mass check is off (rcmdyn_set_massck)");
+    if (cap < 0) throw std::runtime_error("rcmdyn_get_massck: cap must not be negative");
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    std::vector<double> ring(MCK_HEAD + (size_t)mck_cap * MCK_NREC);
+    HIPCHK(hipMemcpy(ring.data(), mck_log, sizeof(double) * ring.size(), hipMemcpyDeviceToHost));
+    long long now = 0;
+    std::memcpy(&now, ring.data(), sizeof(now));
+    const long long fresh = now - mck_seen;
+    const int n = (int)std::min<long long>(fresh, std::min(cap, mck_cap));
+    for (int q = 0; q < n; q++)            // the newest n records, oldest first
+      std::memcpy(out + (size_t)q * MCK_NREC, ring.data() + MCK_HEAD + (size_t)((now - n + q) % mck_cap) * MCK_NREC,
+                  sizeof(double) * MCK_NREC);
+    if (n > 0 && comm && cfg.tile_count < ntiles) {   // sumall over the ranks: the four sums of every record
+      double* d = nullptr;
+      HIPCHK(hipMalloc(&d, sizeof(double) * 4 * (size_t)n));
+      std::vector<double> hv(4 * (size_t)n);
+      for (int q = 0; q < n; q++)
+        for (int e = 0; e < 4; e++) hv[4 * (size_t)q + e] = out[(size_t)q * MCK_NREC + 2 + e];
+      HIPCHK(hipMemcpy(d, hv.data(), sizeof(double) * hv.size(), hipMemcpyHostToDevice));
+      comm->allreduce_sum(d, hv.size(), stream);
+      HIPCHK(hipStreamSynchronize(stream));
+      HIPCHK(hipMemcpy(hv.data(), d, sizeof(double) * hv.size(), hipMemcpyDeviceToHost));
+      (void)hipFree(d);
+      for (int q = 0; q < n; q++)
+        for (int e = 0; e < 4; e++) out[(size_t)q * MCK_NREC + 2 + e] = hv[4 * (size_t)q + e];
+    }
+    mck_seen = now;
+    *count = n;
+    *lost = fresh - n;
   }
 
   // ------------------------------------------------------------------ halo exchange
@@ -1900,6 +2006,7 @@ struct rcmdyn_engine {
     xchv(pro);
     fork_after_exchange();
     xch_begin(pro2);
+    massck_launch();
     each([&](Tile& t) {
       const Geom& g = t.g;
       const NHFields f = nhfields(t);
@@ -2192,6 +2299,7 @@ struct rcmdyn_engine {
       side_end(0);
       xchv(pro);
       ghosts_stale = false;
+      massck_launch();
       side_join(0);
       each([&](Tile& t) { columns(t, t.nint ? 2 : 0, t.nint ? t.nring : t.nred, true); });
     } else {
@@ -2200,6 +2308,7 @@ struct rcmdyn_engine {
       fork_after_exchange();
       xch_begin(pro2);
       ghosts_stale = false;
+      massck_launch();
       each([&](Tile& t) { columns(t, 0, t.nred, true); });
       xch_join();
     }
@@ -3031,6 +3140,14 @@ int rcmdyn_get_budget(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_
 }
 
 int rcmdyn_reset_budget(rcmdyn_t* h) { return guard(h, [&] { h->reset_budget(); }); }
+
+int rcmdyn_set_massck(rcmdyn_t* h, int32_t on, int32_t cap) {
+  return guard(h, [&] { h->set_massck(on, cap); });
+}
+
+int rcmdyn_get_massck(rcmdyn_t* h, double* out, int32_t cap, int32_t* count, int64_t* lost) {
+  return guard(h, [&] { h->get_massck(out, cap, count, lost); });
+}
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,
                         int32_t* count) {

@@ -32,11 +32,14 @@ EXPORTED = [
     "rcmdyn_tend_pre_physics", "rcmdyn_tend_post_physics", "rcmdyn_bdyin", "rcmdyn_reductions", "rcmdyn_runtime_info",
     "rcmdyn_exchange_plan", "rcmdyn_overlap_shares",
     "rcmdyn_set_budget", "rcmdyn_get_budget", "rcmdyn_reset_budget",
+    "rcmdyn_set_massck", "rcmdyn_get_massck",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
 BUDGET_TERMS = ["T_ADH", "T_ADV", "T_ADI", "T_BDY", "T_DIF", "Q_ADH", "Q_ADV", "Q_ADI", "Q_BDY", "Q_DIF"]
 IQV = 1    # the reference's index of water vapour (Main/mpplib/mod_runparams.F90:38)
+# one record of the mass check (rcmdyn_get_massck), in order
+MASSCK_COLUMNS = ("lcount", "dt", "drymass", "dryadv", "qmass", "qadv")
 
 
 class EngineError(RuntimeError):
@@ -85,6 +88,8 @@ def lib():
     L.rcmdyn_set_budget.argtypes = [P, i32, i32, ctypes.c_double]
     L.rcmdyn_get_budget.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
     L.rcmdyn_reset_budget.argtypes = [P]
+    L.rcmdyn_set_massck.argtypes = [P, i32, i32]
+    L.rcmdyn_get_massck.argtypes = [P, dp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64)]
     _lib = L
     return L
 
@@ -278,6 +283,24 @@ class DynCore:
     def reset_budget(self):
         """Zeroes the ten accumulators (the host does it after writing them to the ATM file)."""
         self._check(lib().rcmdyn_reset_budget(self.h))
+
+    def set_massck(self, on: bool = True, cap: int = 1024):
+        """The mass check of tend (Main/mod_massck.F90): every later tend appends one record
+        (MASSCK_COLUMNS) to a device ring of cap records; the same on and cap keep the log."""
+        self._check(lib().rcmdyn_set_massck(self.h, 1 if on else 0, cap))
+        if on:
+            self._massck_cap = cap
+
+    def get_massck(self):
+        """(records [count, 6], lost): the records of the tends since the last call, oldest
+        first, and how many older ones the ring overwrote.  Empties the log; collective over
+        the ranks of a job (it adds the four sums over them)."""
+        cap = getattr(self, "_massck_cap", 1)
+        out = np.zeros((cap, len(MASSCK_COLUMNS)))
+        n, lost = ctypes.c_int32(), ctypes.c_int64()
+        self._check(lib().rcmdyn_get_massck(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap,
+                                            ctypes.byref(n), ctypes.byref(lost)))
+        return out[:n.value].copy(), int(lost.value)
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

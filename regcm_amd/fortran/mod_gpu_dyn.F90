@@ -251,6 +251,23 @@ module mod_gpu_dyn
       import :: c_int, c_ptr
       type(c_ptr), value :: h
     end function
+    ! the mass check of tend (Main/mod_massck.F90) on (1) or off (0, the default), with a device
+    ! log of cap records (1..65536)
+    integer(c_int) function rcmdyn_set_massck(h, on, cap) bind(c, name='rcmdyn_set_massck')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on, cap
+    end function
+    ! the records since the last call into recs(6,cap), oldest first: lcount, dt, drymass,
+    ! dryadv, qmass, qadv; count of them copied, lost older ones; collective over the ranks
+    integer(c_int) function rcmdyn_get_massck(h, recs, cap, count, lost) bind(c, name='rcmdyn_get_massck')
+      import :: c_int, c_ptr, c_int32_t, c_int64_t, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(out) :: recs(*)
+      integer(c_int32_t), value :: cap
+      integer(c_int32_t), intent(out) :: count
+      integer(c_int64_t), intent(out) :: lost
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -270,6 +287,7 @@ module mod_gpu_dyn
   public :: rcmdyn_synchronize, rcmdyn_set_nproc, rcmdyn_tile_extent, rcmdyn_tile_extent_cfg, rcmdyn_exchange_plan
   public :: rcmdyn_overlap_shares, rcmdyn_runtime_info, rcmdyn_last_step_ms, rcmdyn_set_diagnostics
   public :: rcmdyn_kernel_times, rcmdyn_set_budget, rcmdyn_get_budget, rcmdyn_reset_budget
+  public :: rcmdyn_set_massck, rcmdyn_get_massck
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains

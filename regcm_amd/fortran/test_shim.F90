@@ -3,8 +3,9 @@
 ! tests/test_fortran_shim.py).  It runs a script of C-ABI calls that the test writes, the
 ! calls a RegCM host makes around the dyn step (Main/mod_regcm_interface.F90:150-228:
 ! the state put, the init bdyval, nsteps x (tend + bdyval) or the physics split of tend,
-! bdyin after read_icbc, the 3-hourly sums, restarts), and writes every result it reads back
-! to a stream file, so the test can compare it with the Python host running the same script.
+! bdyin after read_icbc, the 3-hourly sums, restarts, the mass check's log), and writes every
+! result it reads back to a stream file, so the test can compare it with the Python host running
+! the same script.
 !
 ! Input (stream): int32 size of rcmdyn_config, its memory image, then ops (int32 code + args).
 ! A code of 24 makes the next op report its return code and message instead of aborting.
@@ -180,6 +181,17 @@ program test_shim
       ierr = rcmdyn_kernel_times(h, n, m, names, launches, avg, k1)
       if ( ierr == 0 ) write(11) k1, launches(1:k1), names(1:48*k1)
       deallocate(names, launches, avg)
+    case ( 26 )
+      ! the mass check on / off with a log of m records
+      read(10) n, m
+      ierr = rcmdyn_set_massck(h, n, m)
+    case ( 27 )
+      ! the mass check's records since the last read, at most n of them
+      read(10) n
+      allocate(avg(6*max(n,1)))
+      ierr = rcmdyn_get_massck(h, avg, n, k1, cnt)
+      if ( ierr == 0 ) write(11) k1, cnt, avg(1:6*k1)
+      deallocate(avg)
     case default
       write(0,*) 'test_shim: unknown op ', op
       error stop 3
