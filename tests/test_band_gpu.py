@@ -13,13 +13,11 @@ import dataclasses
 import numpy as np
 import pytest
 
-from regcm_amd.config import CONFIGS, QX_STATE_FIELDS, STATE_FIELDS
+from regcm_amd.config import CONFIGS
 from regcm_amd import icbc
+from tests.support import case, engine, pair, relerr, state_names, variant_id
 
 pytestmark = pytest.mark.gpu
-
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-         "DSTOR", "HSTOR", "ATM1_TKE", "ATM2_TKE"} | set(QX_STATE_FIELDS)
 
 # the options of tests/test_band_cpu.py plus the two whose result depends on the tiling
 # (idiffu = 3's last-column term and clamped stencil, the moisture fix's j-order sweep)
@@ -28,52 +26,20 @@ VARIANTS = [{}, {"isladvec": 1}, {"ibltyp": 2}, {"iboudy": 1}, {"iboudy": 4}, {"
 TILING_VARIANTS = [{}, {"isladvec": 1, "ibltyp": 2}, {"iboudy": 4}]
 
 
-def _vid(v):
-    return ",".join(f"{k}={x}" for k, x in v.items()) or "default"
-
-
-def relerr(a, b, rc, name):
-    if name in CROSS:                    # the cross grid: every j, rows 1..iy-1
-        a = a[:, : rc.iy - 1, :]
-        b = b[:, : rc.iy - 1, :]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
 def band_case(variant, name="C1"):
-    rc = dataclasses.replace(CONFIGS[name], i_band=1, **variant)
-    data = icbc.generate(rc)
-    st = dict(data["state"])
-    if rc.ibltyp == 2:
-        st.update(icbc.tke_state(rc))
-    if rc.nqx > 2:
-        st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-    return rc, data, st
+    return case(name, i_band=1, **variant)
 
 
 def fields(rc):
-    return (list(STATE_FIELDS) + (QX_STATE_FIELDS if rc.nqx > 2 else []) +
-            (["ATM1_TKE", "ATM2_TKE"] if rc.ibltyp == 2 else []))
+    return state_names(rc, tke=True)
 
 
-def engine(rc, data, st, nproc_j=1, nproc_i=1):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc_j, nproc_i=nproc_i)
-    e.put_state(st)
-    e.bdyval()
-    return e
-
-
-@pytest.mark.parametrize("variant", VARIANTS, ids=_vid)
+@pytest.mark.parametrize("variant", VARIANTS, ids=variant_id)
 def test_band_matches_oracle(variant):
     """One tile (its own periodic neighbour through the halo exchange) against the oracle's
     one tile: the initial bdyval exactly, then 1 and 3 steps."""
-    from oracle.oracle import OracleCore
     rc, data, st = band_case(variant)
-    o = OracleCore(rc, data["split"])
-    o.put_state(st)
-    o.bdyval()
-    e = engine(rc, data, st)
+    o, e = pair(rc, data, st)
     for name in fields(rc):
         assert relerr(e.get(name), o.get(name), rc, name) == 0.0, name
     for nsteps, tol in ((1, 1e-12), (2, 1e-11)):
@@ -86,12 +52,8 @@ def test_band_matches_oracle(variant):
 
 
 def test_band_twenty_steps_vs_oracle():
-    from oracle.oracle import OracleCore
     rc, data, st = band_case({})
-    o = OracleCore(rc, data["split"])
-    o.put_state(st)
-    o.bdyval()
-    e = engine(rc, data, st)
+    o, e = pair(rc, data, st)
     o.step(20)
     e.step(20)
     for name in fields(rc):
@@ -100,13 +62,13 @@ def test_band_twenty_steps_vs_oracle():
 
 
 @pytest.mark.parametrize("nproc", [(2, 1), (1, 2), (2, 2), (3, 1), (2, 4)], ids=str)
-@pytest.mark.parametrize("variant", TILING_VARIANTS, ids=_vid)
+@pytest.mark.parametrize("variant", TILING_VARIANTS, ids=variant_id)
 def test_band_tiles_bit_identical(variant, nproc):
     """Tiles of a band exchange around the period (with 2 tiles in j one tile is both the west
     and the east neighbour): bit-identical to one tile over 6 steps."""
     rc, data, st = band_case(variant)
     one = engine(rc, data, st)
-    til = engine(rc, data, st, *nproc)
+    til = engine(rc, data, st, nproc)
     one.step(6)
     til.step(6)
     for name in fields(rc):
@@ -117,12 +79,8 @@ def test_band_tiles_bit_identical(variant, nproc):
                                           ({"ipptls": 2}, (2, 2)), ({"ipptls": 2}, (1, 3))], ids=str)
 def test_band_tiles_match_oracle_tiles(variant, dims):
     """The tiling-dependent options against the oracle run as the same tiles (orc_par.c)."""
-    from oracle.oracle import OracleParallel
     rc, data, st = band_case(variant)
-    o = OracleParallel(rc, data["split"], dims=dims)
-    o.put_state(st)
-    o.bdyval()
-    e = engine(rc, data, st, *dims)
+    o, e = pair(rc, data, st, dims, tiles=dims)
     for nsteps, tol in ((1, 1e-12), (2, 1e-11)):
         o.step(nsteps)
         e.step(nsteps)
@@ -150,9 +108,9 @@ def test_band_rccl_transport(monkeypatch, nproc):
     """The periodic messages through RCCL (RCMDYN_FORCE_RCCL: a one-rank communicator; one
     tile in j sends to itself) equal the device-copy transport."""
     rc, data, st = band_case({})
-    ref = engine(rc, data, st, *nproc)
+    ref = engine(rc, data, st, nproc)
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
-    dec = engine(rc, data, st, *nproc)
+    dec = engine(rc, data, st, nproc)
     ref.step(6)
     dec.step(6)
     for name in fields(rc):
@@ -163,7 +121,7 @@ def test_band_c3_tiles_bit_identical():
     """The headline domain as a band on the 8-GPU tiling (2 x 4): bit-identical to one tile."""
     rc, data, st = band_case({}, "C3")
     one = engine(rc, data, st)
-    til = engine(rc, data, st, 2, 4)
+    til = engine(rc, data, st, (2, 4))
     one.step(4)
     til.step(4)
     for name in fields(rc):
@@ -174,16 +132,11 @@ def test_band_reference_grid_test_009():
     """The reference's own band run, Testing/test_009.in: 720 x 210 x 18 at ds = 55.5994675 km,
     dt = 150 s, i_band = 1, iboudy = 5 (:3-5, 16; a wide, non-square grid) against the oracle
     after 1, 3 and 10 steps, and its 8-GPU tiling (2 x 4) bit-identical to one tile."""
-    from oracle.oracle import OracleCore
     rc = dataclasses.replace(CONFIGS["C1"], jx=720, iy=210, kz=18, ds=55.5994675, dt=150.0, i_band=1,
                              name="test_009 band 720x210x18")
     data = icbc.generate(rc)
-    st = dict(data["state"])
-    o = OracleCore(rc, data["split"])
-    o.put_state(st)
-    o.bdyval()
-    e = engine(rc, data, st)
-    til = engine(rc, data, st, 2, 4)
+    o, e = pair(rc, data)
+    til = engine(rc, data, nproc=(2, 4))
     for name in fields(rc):
         assert relerr(e.get(name), o.get(name), rc, name) == 0.0, name
     for nsteps, tol in ((1, 1e-12), (2, 1e-11), (7, 1e-9)):

@@ -11,25 +11,14 @@ import numpy as np
 import pytest
 
 from regcm_amd import icbc
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, STATE_FIELDS
+from regcm_amd.config import STATE_FIELDS
+from tests.support import NH_FIELDS, case, engine, pair, relerr
 
 pytestmark = pytest.mark.gpu
 
 BDY = ["XUB_B0", "XUB_BT", "XVB_B0", "XVB_BT", "XTB_B0", "XTB_BT", "XQB_B0", "XQB_BT"]
 HBDY = BDY + ["XPSB_B0", "XPSB_BT"]
 NHBDY = BDY + ["XPPB_B0", "XPPB_BT", "XWWB_B0", "XWWB_BT"]
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-         "DSTOR", "HSTOR", "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"}
-
-
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
 def records(rc, data, nh, n=3, seed=5):
     """n raw ICBC records as read_icbc returns them (u, v m/s on dot points; t K, qv kg/kg on
     cross points; ps hPa; NH pp Pa, w m/s), drifting from the synthetic initial state."""
@@ -69,32 +58,16 @@ def feed(c, rec):
     c.bdyin()
 
 
-def make_pair(rc, data, nproc=(1, 1)):
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o = OracleCore(rc, data["split"])
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    for c in (o, e):
-        c.put_state(data["state"])
-    return o, e
-
-
 def check_bdy(o, e, names):
     for name in names:
         assert np.array_equal(e.get(name), o.get(name)), name
     assert e.get_time()[2] == 0.0 and o.get_time()[2] == 0.0
 
 
-@pytest.fixture(scope="module")
-def nh_data():
-    rc = CONFIGS["N1"]
-    return rc, icbc.generate_nh(rc)
-
-
 def test_bdyin_init_and_update_exact(c1_data):
     rc, data = c1_data
     recs = records(rc, data, False)
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data, bdyval=False)
     for c in (o, e):            # init_bdy: the records at the start and dtbdys later
         feed(c, recs[0])
         feed(c, recs[1])
@@ -115,12 +88,10 @@ def test_bdyin_init_and_update_exact(c1_data):
 
 @pytest.mark.parametrize("nproc", [(2, 2), (1, 3)])
 def test_bdyin_decomposition_invariance(c1_data, nproc):
-    from regcm_amd.dycore import DynCore
     rc, data = c1_data
     recs = records(rc, data, False)
-    cores = [DynCore(rc, data["split"]), DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])]
+    cores = [engine(rc, data, bdyval=False), engine(rc, data, nproc=nproc, bdyval=False)]
     for c in cores:
-        c.put_state(data["state"])
         feed(c, recs[0])
         feed(c, recs[1])
         c.bdyval()
@@ -129,10 +100,10 @@ def test_bdyin_decomposition_invariance(c1_data, nproc):
         assert np.array_equal(cores[0].get(name), cores[1].get(name)), name
 
 
-def test_nh_bdyin_exact(nh_data):
-    rc, data = nh_data
+def test_nh_bdyin_exact():
+    rc, data, _ = case("N1")
     recs = records(rc, data, True)
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data, bdyval=False)
     psdot = icbc.psc2psd_global(data["state"]["ATM0_PS"][0])[None]
     for c in (o, e):
         c.put("ATM0_PSDOT", psdot)
@@ -142,7 +113,7 @@ def test_nh_bdyin_exact(nh_data):
     for c in (o, e):
         c.bdyval()
         c.step(2)
-    for name in STATE_FIELDS[:12] + NH_STATE_FIELDS:
+    for name in NH_FIELDS:
         err = relerr(e.get(name), o.get(name), rc, name)
         assert err < 1e-10, (name, err)
 

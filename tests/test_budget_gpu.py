@@ -26,9 +26,9 @@ import dataclasses
 import numpy as np
 import pytest
 
-from regcm_amd import icbc
-from regcm_amd.config import (CONFIGS, NH_PHY_FIELDS, NH_STATE_FIELDS, PHY_FIELDS, STATE_FIELDS, field_levels)
 from regcm_amd.dycore import BUDGET_TERMS
+from tests import support
+from tests.support import advance, case, physics_tendencies, state_names
 
 pytestmark = pytest.mark.gpu
 
@@ -36,38 +36,8 @@ T_TERMS, Q_TERMS = BUDGET_TERMS[:5], BUDGET_TERMS[5:]
 OFF = "the tendency budget is off"
 
 
-def small(core, **kw):
-    """C1 ('C') or N1 ('N') on the 37 x 29 grid."""
-    return dataclasses.replace(CONFIGS["C1" if core == "C" else "N1"], jx=37, iy=29, nspgx=None, nspgd=None, **kw)
-
-
-def make(rc):
-    gen = icbc.generate_crm if rc.i_crm else icbc.generate_nh if rc.idynamic == 2 else icbc.generate
-    data = gen(rc)
-    st = dict(data["state"])
-    if rc.nqx > 2:
-        st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-    if rc.ibltyp == 2:
-        st.update({k: v for k, v in icbc.tke_state(rc).items() if k not in st})
-    return data, st
-
-
-_CASES = {}
-
-
-def case(core, **kw):
-    """(rc, data, state) of a small-grid variant, generated once."""
-    key = (core,) + tuple(sorted(kw.items()))
-    if key not in _CASES:
-        rc = CONFIGS["CRM"] if core == "CRM" else small(core, **kw)
-        _CASES[key] = (rc,) + make(rc)
-    return _CASES[key]
-
-
 def engine(rc, data, st, rw=None, nproc=(1, 1), diag=True):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    e.put_state(st)
+    e = support.engine(rc, data, st, nproc, bdyval=False)
     if diag:
         e.set_diagnostics(True)
     if rw is not None:
@@ -78,12 +48,6 @@ def engine(rc, data, st, rw=None, nproc=(1, 1), diag=True):
 
 def terms(e):
     return {n: e.get_budget(n) for n in BUDGET_TERMS}
-
-
-def state_names(rc):
-    if rc.idynamic == 2:
-        return [n for n in STATE_FIELDS if n not in ("DSTOR", "HSTOR")] + NH_STATE_FIELDS
-    return list(STATE_FIELDS)
 
 
 def interior(rc):
@@ -138,32 +102,6 @@ def test_budget_off_by_default_and_refusals(core):
 
 
 # ------------------------------------------------------------------ 2. non-interference
-def physics_tendencies(rc, seed=7):
-    """Synthetic pc_physic tendencies coupled with p* (as tests/test_physics_seam_gpu.py)."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    scale = {"TPHY": 5e-3, "QVPHY": 1e-6, "QCPHY": 1e-7, "UPHY": 5e-3, "VPHY": 5e-3, "PPPHY": 5e-2, "WPHY": 1e-4}
-    out = {}
-    for name in PHY_FIELDS + (NH_PHY_FIELDS if rc.idynamic == 2 else []):
-        x = rng.standard_normal((field_levels(name, rc.kz, rc.nsplit), rc.iy, rc.jx))
-        out[name] = scale[name] * (np.abs(x) if name in ("QVPHY", "QCPHY") else x)
-    return out
-
-
-def advance(e, path, nsteps, phy=None):
-    if path == "step":
-        e.step(nsteps)
-        return
-    for _ in range(nsteps):
-        if path == "pair":
-            e.tend()
-        else:
-            e.tend_pre_physics()
-            for name, arr in (phy or {}).items():
-                e.put(name, arr)
-            e.tend_post_physics()
-        e.bdyval()
-
-
 @pytest.mark.parametrize("path", ["step", "pair", "physics"])
 @pytest.mark.parametrize("core", ["C", "N"])
 def test_budget_does_not_change_the_step(core, path):
@@ -653,8 +591,7 @@ def test_budget_accumulates_and_resets(core):
 @pytest.mark.parametrize("transport", ["copy", "rccl"])
 @pytest.mark.parametrize("name", ["C1", "N1"])
 def test_budget_tiles_match_one_tile(name, transport, monkeypatch):
-    rc = CONFIGS[name]
-    data, st = make(rc)
+    rc, data, st = case(name)
     one = engine(rc, data, st, rw=1.0, diag=False)
     if transport == "rccl":
         monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
@@ -673,8 +610,7 @@ def test_budget_tiles_match_one_tile(name, transport, monkeypatch):
 def test_budget_two_launches_match_the_fused_update(nproc, monkeypatch):
     """k_momentum and k_scalars as two launches (RCMDYN_NO_FUSE_UPDATE: the budget instance of
     k_scalars itself, with the overlap parts on tiles) give the fused launch's terms bit for bit."""
-    rc = CONFIGS["C1"]
-    data, st = make(rc)
+    rc, data, st = case("C1")
     fused = engine(rc, data, st, rw=1.0, nproc=nproc, diag=False)
     monkeypatch.setenv("RCMDYN_NO_FUSE_UPDATE", "1")
     two = engine(rc, data, st, rw=1.0, nproc=nproc, diag=False)

@@ -19,31 +19,12 @@ import os
 import numpy as np
 import pytest
 
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, STATE_FIELDS
+from regcm_amd.config import CONFIGS, STATE_FIELDS
 from regcm_amd import icbc
+from tests import support
+from tests.support import NH_FIELDS, case, engine, rel_l2, relerr
 
 pytestmark = pytest.mark.gpu
-
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-         "DSTOR", "HSTOR", "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"}
-NH_FIELDS = ["ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T",
-             "ATM2_QV", "ATM2_QC", "PSA", "PSB"] + NH_STATE_FIELDS
-
-
-def _crop(a, rc, name):
-    return a[:, : rc.iy - 1, : rc.jx - 1] if name in CROSS else a
-
-
-def rel_l2(a, b, rc, name):
-    a, b = _crop(a, rc, name), _crop(b, rc, name)
-    den = float(np.sqrt(np.sum(b * b)))
-    return float(np.sqrt(np.sum((a - b) ** 2))) / max(den, 1e-300)
-
-
-def rel_max(a, b, rc, name):
-    a, b = _crop(a, rc, name), _crop(b, rc, name)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
-
 
 def _threads():
     n = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(16, len(os.sched_getaffinity(0)))
@@ -55,26 +36,14 @@ def say(*a):
 
 
 def oracle(rc, data):
-    from oracle.oracle import OracleParallel
-    o = OracleParallel(rc, data["split"], _threads())
-    o.put_state(data["state"])
-    o.bdyval()
-    return o
-
-
-def engine(rc, data, nproc_j=1, nproc_i=1):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc_j, nproc_i=nproc_i)
-    e.put_state(data["state"])
-    e.bdyval()
-    return e
+    return support.oracle(rc, data, tiles=_threads())
 
 
 def check_close(e, o, rc, fields, l2tol, maxtol, what):
     worst = (0.0, 0.0, "")
     for name in fields:
         a, b = e.get(name), o.get(name)
-        l2, mx = rel_l2(a, b, rc, name), rel_max(a, b, rc, name)
+        l2, mx = rel_l2(a, b, rc, name), relerr(a, b, rc, name)
         assert l2 <= l2tol and mx <= maxtol, (what, name, l2, mx)
         worst = max(worst, (l2, mx, name))
     say(what, "worst rel-L2 %.2e rel-max %.2e (%s)" % worst)
@@ -83,8 +52,7 @@ def check_close(e, o, rc, fields, l2tol, maxtol, what):
 def test_c3_five_steps_vs_oracle():
     """C3 (the headline grid): 1 step at rel-L2 1e-13 / rel-max 1e-12, 5 steps at rel-L2
     1e-12 / rel-max 1e-11."""
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
+    rc, data, _ = case("C3")
     o, e = oracle(rc, data), engine(rc, data)
     o.step(1)
     e.step(1)
@@ -97,8 +65,7 @@ def test_c3_five_steps_vs_oracle():
 
 def test_c2_hundred_steps_rel_l2():
     """rel-L2 <= 1e-9 after 100 steps (C2, dycore only)."""
-    rc = CONFIGS["C2"]
-    data = icbc.generate(rc)
+    rc, data, _ = case("C2")
     o, e = oracle(rc, data), engine(rc, data)
     for n in range(4):
         o.step(25)
@@ -112,8 +79,7 @@ def test_c3_hundred_steps_rel_l2():
     """The headline grid over a longer run: C3, 100 steps (4.2 simulated hours, past the
     leapfrog dt switch and two flag-reduction intervals of the graph replay), rel-L2 <= 1e-9
     per prognostic field, SURVEY 8(c)'s 100-step bound."""
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
+    rc, data, _ = case("C3")
     o, e = oracle(rc, data), engine(rc, data)
     for n in range(4):
         o.step(25)
@@ -126,8 +92,7 @@ def test_c3_hundred_steps_rel_l2():
 def test_c3_thousand_steps_rel_l2():
     """C3 over 1 000 steps (41.7 simulated hours, graph replay throughout): rel-L2 <= 1e-9 per
     prognostic field, the 100-step bound held ten times longer."""
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
+    rc, data, _ = case("C3")
     o, e = oracle(rc, data), engine(rc, data)
     for n in range(4):
         o.step(250)
@@ -141,8 +106,8 @@ def test_c4_two_by_two_tiles():
     """C4 (384x384x23 on 2x2 tiles): the decomposed engine is bit-identical to one tile over
     3 steps, and both match the oracle after 2 steps."""
     rc = CONFIGS["C4"]
-    data = icbc.generate(rc)
-    one, dec = engine(rc, data), engine(rc, data, 2, 2)
+    data = icbc.generate(rc)             # not case(): too large to keep for the session
+    one, dec = engine(rc, data), engine(rc, data, nproc=(2, 2))
     o = oracle(rc, data)
     for x in (one, dec, o):
         x.step(2)
@@ -167,7 +132,7 @@ def test_c5_two_by_four_tiles(c5_data):
     rc, data = c5_data
     one = engine(rc, data)
     say("C5 one tile ready")
-    dec = engine(rc, data, 2, 4)
+    dec = engine(rc, data, nproc=(2, 4))
     say("C5 2x4 tiles ready")
     one.step(3)
     dec.step(3)
@@ -192,8 +157,7 @@ def test_c5_vs_oracle(c5_data):
 
 def test_n2_vs_oracle():
     """N2 (96x96x41 NH): 1 step at rel-max 1e-11, 3 steps at 1e-10."""
-    rc = CONFIGS["N2"]
-    data = icbc.generate_nh(rc)
+    rc, data, _ = case("N2")
     o, e = oracle(rc, data), engine(rc, data)
     o.step(1)
     e.step(1)
@@ -206,8 +170,7 @@ def test_n2_vs_oracle():
 def test_n2_hundred_steps_rel_l2():
     """The NH core over a longer run: N2, 100 steps (graph-replayed after the first two),
     rel-L2 <= 1e-9 per prognostic field, SURVEY 8(c)'s 100-step bound."""
-    rc = CONFIGS["N2"]
-    data = icbc.generate_nh(rc)
+    rc, data, _ = case("N2")
     o, e = oracle(rc, data), engine(rc, data)
     for n in range(4):
         o.step(25)

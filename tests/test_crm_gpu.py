@@ -16,38 +16,17 @@ import numpy as np
 import pytest
 
 from regcm_amd import icbc
-from regcm_amd.config import CONFIGS
+from regcm_amd.config import CONFIGS, TKE_STATE_FIELDS
+from tests.support import NH_FIELDS, case, engine, oracle, relerr, state_names, variant_id
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ["ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T", "ATM2_QV",
-          "ATM2_QC", "PSA", "PSB", "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W", "ATM1_TKE", "ATM2_TKE"]
-
-
-def relerr(a, b):
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
+FIELDS = NH_FIELDS + TKE_STATE_FIELDS
 
 
 @pytest.fixture(scope="module")
 def crm_data():
-    rc = CONFIGS["CRM"]
-    return rc, icbc.generate_crm(rc)
-
-
-def engine(rc, data, st=None, nproc=(1, 1)):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    e.put_state(st if st is not None else data["state"])
-    e.bdyval()
-    return e
-
-
-def oracle(rc, data, st=None):
-    from oracle.oracle import OracleCore
-    o = OracleCore(rc, data["split"])
-    o.put_state(st if st is not None else data["state"])
-    o.bdyval()
-    return o
+    return case("CRM")[:2]
 
 
 def test_crm_matches_oracle(crm_data):
@@ -55,13 +34,13 @@ def test_crm_matches_oracle(crm_data):
     rc, data = crm_data
     o, e = oracle(rc, data), engine(rc, data)
     for name in FIELDS:
-        assert relerr(e.get(name), o.get(name)) == 0.0, name
+        assert relerr(e.get(name), o.get(name), rc, name) == 0.0, name
     for nsteps, tol in ((1, 1e-11), (1, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         assert e.get_time() == o.get_time()
         for name in FIELDS:
-            err = relerr(e.get(name), o.get(name))
+            err = relerr(e.get(name), o.get(name), rc, name)
             assert err < tol, (name, err, nsteps)
     o.step(18)
     e.step(18)
@@ -70,35 +49,29 @@ def test_crm_matches_oracle(crm_data):
     p = oracle(rc, data, st)
     p.step(20)
     for name in FIELDS:
-        err, spread = relerr(e.get(name), o.get(name)), relerr(p.get(name), o.get(name))
+        err, spread = relerr(e.get(name), o.get(name), rc, name), relerr(p.get(name), o.get(name), rc, name)
         assert err <= max(1e-9, 100.0 * spread), (name, err, spread)
 
 
 CRM_VARIANTS = [{"ipptls": 2}, {"isladvec": 1}, {"idiffu": 2}, {"ifrayd": 0}, {"ifupr": 0}]
 
 
-@pytest.mark.parametrize("variant", CRM_VARIANTS, ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()))
+@pytest.mark.parametrize("variant", CRM_VARIANTS, ids=variant_id)
 def test_crm_variants_match_oracle(variant):
     """crm_test.in's configuration with the options a CRM namelist may change: the hydrometeors
     of ipptls = 2 (their fix and filters on the doubly periodic planes), semi-Lagrangian
     moisture (departure points across both periods), the 9-point diffusion, no Rayleigh damping,
     no radiative upper condition; against the oracle at 1 and 2 steps."""
-    from regcm_amd.config import QX_STATE_FIELDS
-    rc = dataclasses.replace(CONFIGS["CRM"], **variant)
-    data = icbc.generate_crm(rc)
-    st = dict(data["state"])
-    names = list(FIELDS)
-    if rc.ipptls == 2:
-        st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-        names += QX_STATE_FIELDS
+    rc, data, st = case("CRM", **variant)
+    names = state_names(rc, tke=True)
     o, e = oracle(rc, data, st), engine(rc, data, st)
     for name in names:
-        assert relerr(e.get(name), o.get(name)) == 0.0, name
+        assert relerr(e.get(name), o.get(name), rc, name) == 0.0, name
     for nsteps, tol in ((1, 1e-11), (1, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         for name in names:
-            err = relerr(e.get(name), o.get(name))
+            err = relerr(e.get(name), o.get(name), rc, name)
             assert err < tol, (name, err, nsteps)
 
 
@@ -143,8 +116,7 @@ def test_crm_graph_replay_and_dropin_equal_eager(crm_data):
 def test_crm_rotation_commutes_with_step():
     """Without the radiative condition (its interior clamp is not translation invariant) the
     doubly periodic step commutes with a rotation of the state in j and i, bit for bit."""
-    rc = dataclasses.replace(CONFIGS["CRM"], ifupr=0)
-    data = icbc.generate_crm(rc)
+    rc, data, _ = case("CRM", ifupr=0)
     m, n = 13, 7
     rot = {k: np.roll(v, (n, m), axis=(-2, -1)) if v.ndim == 3 and v.shape[-2:] == (rc.iy, rc.jx) else v
            for k, v in data["state"].items()}
@@ -167,9 +139,7 @@ def test_crm_refusals(crm_data):
 
 # ---- the non-hydrostatic band (periodic in j, south / north boundaries) --------------------
 
-NHB_CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-             "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"}
-NHB_FIELDS = FIELDS[:16]
+NHB_FIELDS = NH_FIELDS
 
 
 def nh_band_case(variant=None):
@@ -181,24 +151,19 @@ def nh_band_case(variant=None):
     return rc, data, st
 
 
-def band_relerr(a, b, rc, name):
-    if name in NHB_CROSS:
-        a, b = a[:, : rc.iy - 1, :], b[:, : rc.iy - 1, :]
-    return relerr(a, b)
-
-
 @pytest.mark.parametrize("variant", [{}, {"iboudy": 1}, {"iboudy": 4}, {"ibltyp": 2}], ids=str)
 def test_nh_band_matches_oracle(variant):
     rc, data, st = nh_band_case(variant)
     o, e = oracle(rc, data, st), engine(rc, data, st)
-    names = NHB_FIELDS + (["ATM1_TKE", "ATM2_TKE"] if rc.ibltyp == 2 else [])
+    names = NHB_FIELDS + (TKE_STATE_FIELDS if rc.ibltyp == 2 else [])
+    whole = TKE_STATE_FIELDS            # compared on every row; the other cross fields on rows 1..iy-1
     for name in names:
-        assert band_relerr(e.get(name), o.get(name), rc, name) == 0.0, name
+        assert relerr(e.get(name), o.get(name), rc, name, crop=name not in whole) == 0.0, name
     for nsteps, tol in ((1, 1e-11), (2, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         for name in names:
-            err = band_relerr(e.get(name), o.get(name), rc, name)
+            err = relerr(e.get(name), o.get(name), rc, name, crop=name not in whole)
             assert err < tol, (name, err, nsteps)
 
 

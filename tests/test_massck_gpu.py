@@ -15,7 +15,6 @@ order errs by at most (n - 1) * 2**-53 * A, and the at most eight roundings insi
 8 * 2**-53 * |leaf| per side.  Everything else (non-interference, paths, ring, transports of the
 same decomposition) is bit for bit.
 """
-import dataclasses
 import os
 import struct
 import subprocess
@@ -24,11 +23,11 @@ import tempfile
 import numpy as np
 import pytest
 
-from regcm_amd import icbc
-from regcm_amd.config import (CONFIGS, FIELD, NH_PHY_FIELDS, NH_STATE_FIELDS, PHY_FIELDS, QX_STATE_FIELDS,
-                              STATE_FIELDS, TWO_D, build_config, field_levels)
+from regcm_amd.config import FIELD, TWO_D, build_config
 from regcm_amd.constants import egrav
 from regcm_amd.dycore import BUDGET_TERMS
+from tests import support
+from tests.support import advance, case, physics_tendencies, state_names
 
 pytestmark = pytest.mark.gpu
 
@@ -36,38 +35,8 @@ OFF = "the mass check is off"
 SUMS = ("drymass", "dryadv", "qmass", "qadv")          # columns 2..5 of a record
 
 
-def small(core, **kw):
-    """C1 ('C') or N1 ('N') on the 37 x 29 grid."""
-    return dataclasses.replace(CONFIGS["C1" if core == "C" else "N1"], jx=37, iy=29, nspgx=None, nspgd=None, **kw)
-
-
-def make(rc):
-    gen = icbc.generate_crm if rc.i_crm else icbc.generate_nh if rc.idynamic == 2 else icbc.generate
-    data = gen(rc)
-    st = dict(data["state"])
-    if rc.nqx > 2:
-        st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-    if rc.ibltyp == 2:
-        st.update({k: v for k, v in icbc.tke_state(rc).items() if k not in st})
-    return data, st
-
-
-_CASES = {}
-
-
-def case(core, **kw):
-    """(rc, data, state) of a variant, generated once: 'C' / 'N' on the small grid, or a CONFIGS name."""
-    key = (core,) + tuple(sorted(kw.items()))
-    if key not in _CASES:
-        rc = small(core, **kw) if core in ("C", "N") else CONFIGS[core]
-        _CASES[key] = (rc,) + make(rc)
-    return _CASES[key]
-
-
 def engine(rc, data, st, cap=None, nproc=(1, 1), budget=False, diag=False):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    e.put_state(st)
+    e = support.engine(rc, data, st, nproc, bdyval=False)
     if diag:
         e.set_diagnostics(True)
     if budget:
@@ -86,12 +55,6 @@ def inputs(e, rc):
     """What massck reads, as the engine holds it before a tend, and the clock."""
     f = {n: e.get(n) for n in ["ATM1_U", "ATM1_V", "PSA"] + qnames(rc)}
     return f, e.get_time()
-
-
-def state_names(rc):
-    names = list(STATE_FIELDS) if rc.idynamic != 2 else \
-        [n for n in STATE_FIELDS if n not in ("DSTOR", "HSTOR")] + NH_STATE_FIELDS
-    return names + (QX_STATE_FIELDS if rc.nqx == 5 else [])
 
 
 # ------------------------------------------------------------------ the reference text in NumPy
@@ -224,32 +187,6 @@ def test_massck_crm_has_no_lines_and_takes_every_point():
 
 
 # ------------------------------------------------------------------ 3. no effect on the step
-def physics_tendencies(rc, seed=7):
-    """Synthetic pc_physic tendencies coupled with p* (as tests/test_physics_seam_gpu.py)."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    scale = {"TPHY": 5e-3, "QVPHY": 1e-6, "QCPHY": 1e-7, "UPHY": 5e-3, "VPHY": 5e-3, "PPPHY": 5e-2, "WPHY": 1e-4}
-    out = {}
-    for name in PHY_FIELDS + (NH_PHY_FIELDS if rc.idynamic == 2 else []):
-        x = rng.standard_normal((field_levels(name, rc.kz, rc.nsplit), rc.iy, rc.jx))
-        out[name] = scale[name] * (np.abs(x) if name in ("QVPHY", "QCPHY") else x)
-    return out
-
-
-def advance(e, path, nsteps, phy=None):
-    if path == "step":
-        e.step(nsteps)
-        return
-    for _ in range(nsteps):
-        if path == "pair":
-            e.tend()
-        else:
-            e.tend_pre_physics()
-            for name, arr in (phy or {}).items():
-                e.put(name, arr)
-            e.tend_post_physics()
-        e.bdyval()
-
-
 @pytest.mark.parametrize("budget", [False, True], ids=["", "budget"])
 @pytest.mark.parametrize("path", ["step", "pair", "physics"])
 @pytest.mark.parametrize("core", ["C", "N"])

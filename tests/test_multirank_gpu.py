@@ -11,8 +11,9 @@ import threading
 import numpy as np
 import pytest
 
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, STATE_FIELDS
+from regcm_amd.config import CONFIGS, STATE_FIELDS, TKE_STATE_FIELDS
 from regcm_amd import icbc
+from tests.support import NH_FIELDS, case, engine
 
 pytestmark = pytest.mark.gpu
 
@@ -59,18 +60,14 @@ def gather(engs, name):
 
 
 def single(rc, data, nsteps):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"])
-    e.put_state(data["state"])
-    e.bdyval()
+    e = engine(rc, data)
     e.step(nsteps)
     return e
 
 
 @pytest.mark.parametrize("name,cj,ci", [("C1", 2, 2), ("C1", 1, 3), ("C3", 2, 4)])
 def test_hydrostatic_ranks_bit_identical(name, cj, ci):
-    rc = CONFIGS[name]
-    data = icbc.generate(rc)
+    rc, data, _ = case(name)
     nsteps = 10                     # crosses the 8-step job-wide flag reduction
     engs = run_ranks(rc, data, cj, ci, nsteps, f"h{name}{cj}{ci}")
     ref = single(rc, data, nsteps)
@@ -85,9 +82,7 @@ def test_band_ranks_bit_identical(cj, ci):
     neighbours across the period, with two tiles in j one rank is both the west and the east
     peer (its messages in the receiver's direction order), and with one tile in j a rank's
     periodic exchange stays inside it.  Bit-identical to one tile."""
-    import dataclasses
-    rc = dataclasses.replace(CONFIGS["C1"], i_band=1)
-    data = icbc.generate(rc)
+    rc, data, _ = case("C1", i_band=1)
     nsteps = 10
     engs = run_ranks(rc, data, cj, ci, nsteps, f"band{cj}{ci}")
     ref = single(rc, data, nsteps)
@@ -103,18 +98,17 @@ def test_hydrostatic_ranks_variant_sladv_tke():
     data = {"split": data["split"], "state": dict(data["state"], **icbc.tke_state(rc))}
     engs = run_ranks(rc, data, 2, 2, 4, "hvar")
     ref = single(rc, data, 4)
-    for f in STATE_FIELDS + ["ATM1_TKE", "ATM2_TKE"]:
+    for f in STATE_FIELDS + TKE_STATE_FIELDS:
         assert np.array_equal(gather(engs, f), ref.get(f)), f
 
 
 def test_nonhydrostatic_ranks_bit_identical():
     """NH on 2 x 2 ranks: the acoustic sub-step exchanges, the 6-deep estore halo and the
     day-alarm all-reduce of the radiative condition (3 steps: istep changes on the first two)."""
-    rc = CONFIGS["N1"]
-    data = icbc.generate_nh(rc)
+    rc, data, _ = case("N1")
     engs = run_ranks(rc, data, 2, 2, 3, "nh")
     ref = single(rc, data, 3)
-    for f in STATE_FIELDS[:12] + NH_STATE_FIELDS:
+    for f in NH_FIELDS:
         assert np.array_equal(gather(engs, f), ref.get(f)), f
 
 
@@ -125,20 +119,17 @@ def test_crm_ranks_bit_identical(cj, ci):
     tiles in a direction one rank is both neighbours there, with one tile the periodic exchange
     stays inside the rank), the corner peers wrap in both directions, and the day-alarm sums of
     the radiative condition are all-reduced.  Bit-identical to one tile."""
-    from regcm_amd.config import CONFIGS as C
-    rc = C["CRM"]
-    data = icbc.generate_crm(rc)
+    rc, data, _ = case("CRM")
     engs = run_ranks(rc, data, cj, ci, 4, f"crm{cj}{ci}")
     ref = single(rc, data, 4)
-    for f in STATE_FIELDS[:12] + NH_STATE_FIELDS + ["ATM1_TKE", "ATM2_TKE"]:
+    for f in NH_FIELDS + TKE_STATE_FIELDS:
         assert np.array_equal(gather(engs, f), ref.get(f)), f
 
 
 def test_job_reductions_over_ranks():
     """rcmdyn_reductions is collective: every rank gets the job-wide ptntot/pt2tot (sums of the
     tiles' partials) equal to the single tile's within the reordering of one sum."""
-    rc = CONFIGS["C1"]
-    data = icbc.generate(rc)
+    rc, data, _ = case("C1")
     engs = run_ranks(rc, data, 2, 2, 3, "red")
     ref = single(rc, data, 3).reductions()
     out = [None] * len(engs)
@@ -184,10 +175,7 @@ def test_uw_kpbl_put_on_own_points(band):
     engs = run_ranks(rc, data, cj, ci, 4, "uwk", per_rank=own_kpbl)
     # the reference: the same 2 x 2 tiles in one engine with the global put (the moisture fix
     # of the cloud edges depends on the decomposition, as the reference's)
-    from regcm_amd.dycore import DynCore
-    ref = DynCore(rc, base["split"], nproc_j=cj, nproc_i=ci)
-    ref.put_state(dict(st, KPBL=kpbl))
-    ref.bdyval()
+    ref = engine(rc, base, dict(st, KPBL=kpbl), (cj, ci))
     ref.step(4)
     for f in STATE_FIELDS:
         assert np.array_equal(gather(engs, f), ref.get(f)), f

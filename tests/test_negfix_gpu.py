@@ -27,13 +27,10 @@ level's own maximum (the fixed values lie orders of magnitude below the field's 
 whole-field norm would hide); the other fields to 1e-12 (hydrostatic) and 1e-11 (NH) after one
 step, the patterned levels to 1e-11 after three.
 """
-import dataclasses
-
 import numpy as np
 import pytest
 
-from regcm_amd import icbc
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, QX_STATE_FIELDS, STATE_FIELDS
+from tests.support import case, oracle, pair, relerr, state_names
 
 pytestmark = pytest.mark.gpu
 
@@ -46,36 +43,16 @@ DEEP = 2.0 ** -1010         # the sums of supplement_field's deep stack lie belo
 GRIDS = {"G1": (24, 67), "G2": (24, 68), "G3": (24, 132), "G4": (70, 68), "G5": (24, 515), "G6": (24, 516),
          "G7": (744, 24)}
 
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB", "DSTOR", "HSTOR",
-         "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"} | set(QX_STATE_FIELDS)
-NH_FIELDS = ["ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T", "ATM2_QV",
-             "ATM2_QC", "PSA", "PSB"] + NH_STATE_FIELDS
 # the oracle's total tendency of each species: a field, or a work array of the nqx = 5 chain
 TENDENCY = {"QV": "QVTEN", "QC": "QCTEN", "QI": "qteni", "QR": "qtenr", "QS": "qtens"}
 
 
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        je = rc.jx if rc.i_band else rc.jx - 1
-        a = a[:, : rc.iy - 1, :je]
-        b = b[:, : rc.iy - 1, :je]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
 # ------------------------------------------------------------------------------- the inputs
-_DATA = {}
-
-
 def grid_case(core, grid, nqx, band=False):
-    """(rc, data) of one grid, generated once per module run and never modified."""
-    key = (core, grid, nqx, band)
-    if key not in _DATA:
-        jx, iy = GRIDS[grid]
-        rc = dataclasses.replace(CONFIGS["N1" if core == "nh" else "C1"], jx=jx, iy=iy, nspgx=None, nspgd=None,
-                                 ipptls=2 if nqx == 5 else 1, i_band=1 if band else 0)
-        _DATA[key] = (rc, icbc.generate_nh(rc) if core == "nh" else icbc.generate(rc))
-    return _DATA[key]
+    """(rc, data) of one grid, generated once and never modified."""
+    jx, iy = GRIDS[grid]
+    return case("N1" if core == "nh" else "C1", jx=jx, iy=iy, nspgx=None, nspgd=None,
+                ipptls=2 if nqx == 5 else 1, i_band=1 if band else 0)[:2]
 
 
 # the single-level patterns (True: negative) on the global (i, j) index planes
@@ -354,26 +331,12 @@ def claims_of(grid, force_sweep):
     return c
 
 
-def start_pair(rc, data, st, nproc=(1, 1), oracle_tiles=None):
-    from oracle.oracle import OracleCore, OracleParallel
-    from regcm_amd.dycore import DynCore
-    if oracle_tiles is None:
-        o = OracleCore(rc, data["split"])
-    else:
-        o = OracleParallel(rc, data["split"], nthreads=oracle_tiles)
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    for c in (o, e):
-        c.put_state(st)
-        c.bdyval()
-    return o, e
-
-
 def compare(label, o, e, rc, levels, tol, exact=True):
     """The moisture species bit-identical on the interior (exact) or within tol per patterned
     level; qv's patterned levels and every state field within tol."""
     ii = slice(1, rc.iy - 2)
     jj = slice(None) if rc.i_band else slice(1, rc.jx - 2)
-    names = (NH_FIELDS if rc.idynamic == 2 else list(STATE_FIELDS)) + (QX_STATE_FIELDS if rc.nqx > 2 else [])
+    names = state_names(rc)
     got = {n: e.get(n) for n in names}
     ref = {n: o.get(n) for n in names}
     for nm, lev in levels.items():
@@ -419,14 +382,14 @@ def run_case(monkeypatch, atm1, core, grid, nqx, env=None, qv=False, band=False,
     st, levels = patterned_state(rc, data, qv=qv, supplement=supplement, atm1=atm1)
     for name, value in (env or {}).items():
         monkeypatch.setenv(name, value)
-    o, e = start_pair(rc, data, st)
+    o, e = pair(rc, data, st)
     label = f"{core} {grid} nqx={nqx} {env or ''}{' band' if band else ''}{' qv' if qv else ''}" + \
         (" supplement" if supplement else "") + f" atm1 {atm1}"
     sp = species_of(rc, qv)
     claims = (claims_of(grid, force_sweep) if claims is None else claims) | ({"qv"} if qv else set())
     tol1 = 1e-11 if core == "nh" else 1e-12
 
-    def advance(n):
+    def forward(n):
         a2 = {nm: o.get(f"ATM2_{nm}") for nm in sp}
         if steps:
             o.step(n)
@@ -436,12 +399,12 @@ def run_case(monkeypatch, atm1, core, grid, nqx, env=None, qv=False, band=False,
             e.tend()
         return {nm: [Marks(cq, rc)] for nm, cq in forecasts(o, a2, sp).items()}
 
-    marks = advance(1)
+    marks = forward(1)
     check_claims(label, marks, levels, claims, force_sweep, dense_species)
     check_visible(label, o, marks, atm1)
     compare(label, o, e, rc, levels, tol1)
     for n in range(2, steps + 1):
-        marks = advance(1)
+        marks = forward(1)
         ndep = sum(int(m.dep.sum()) for t in marks.values() for m in t)
         print(f"{label}: step {n} dependent negatives {ndep}")
         assert ndep > 0, (label, n)
@@ -529,15 +492,12 @@ def test_negfix_decomposed(nthreads, atm1):
     """G3, ipptls = 2, against the oracle run as the same set_nproc tiles: the fix depends on the
     tiles by design (a tile's first interior column reads its neighbour's unfixed forecast).  The
     forecast itself does not, so the marks are restated per tile on the one-tile oracle's."""
-    from oracle.oracle import OracleCore
     from regcm_amd.config import set_nproc
     rc, data = grid_case("hyd", "G3", 5)
     st, levels = patterned_state(rc, data, atm1=atm1)
     nproc = tuple(set_nproc(nthreads, rc.jx, rc.iy))
     sp = species_of(rc)
-    one = OracleCore(rc, data["split"])
-    one.put_state(st)
-    one.bdyval()
+    one = oracle(rc, data, st)
     a2 = {nm: one.get(f"ATM2_{nm}") for nm in sp}
     one.tend()
     marks = {nm: [Marks(cq, rc, nproc, t) for t in range(nproc[0] * nproc[1])]
@@ -545,7 +505,7 @@ def test_negfix_decomposed(nthreads, atm1):
     label = f"hyd G3 nqx=5 tiles {nproc} atm1 {atm1}"
     tallest = max(m.R for m in marks["QC"])
     check_claims(label, marks, {}, {"dense", "tiny"} | ({"ring"} if tallest > 64 else set()), False, sp)
-    o, e = start_pair(rc, data, st, nproc, oracle_tiles=nthreads)
+    o, e = pair(rc, data, st, nproc, tiles=nthreads)
     o.step(1)
     e.step(1)
     check_visible(label, o, marks, atm1)

@@ -8,53 +8,15 @@ max-norm of 1e-12 after one step, growing with the step count as stated per test
 import numpy as np
 import pytest
 
-from regcm_amd.config import CONFIGS, QX_STATE_FIELDS, STATE_FIELDS
+from regcm_amd.config import CONFIGS, STATE_FIELDS
 from regcm_amd import icbc
+from tests.support import case, engine, oracle, pair, relerr, state_names, variant_id, with_species
 
 pytestmark = pytest.mark.gpu
 
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-         "DSTOR", "HSTOR", "PSC", "PTEN", "TTEN", "QVTEN", "QCTEN", "OMEGA", "QDOT", "XKC", "PHI"} | \
-    set(QX_STATE_FIELDS)
-
-
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
-def with_species(rc, state):
-    """ipptls = 2: the state with patchy qi, qr, qs layers (icbc.hydrometeor_state)."""
-    if rc.nqx <= 2:
-        return state
-    st = dict(state)
-    st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-    return st
-
-
-def state_fields(rc):
-    return list(STATE_FIELDS) + (QX_STATE_FIELDS if rc.nqx > 2 else [])
-
-
-def make_pair(rc, data, nproc_j=1, nproc_i=1):
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o = OracleCore(rc, data["split"])
-    e = DynCore(rc, data["split"], nproc_j=nproc_j, nproc_i=nproc_i)
-    st = with_species(rc, data["state"])
-    o.put_state(st)
-    e.put_state(st)
-    o.bdyval()
-    e.bdyval()
-    return o, e
-
-
 def test_init_bdyval_exact(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data)
     for name in STATE_FIELDS:
         assert relerr(e.get(name), o.get(name), rc, name) == 0.0, name
     assert e.get_time() == o.get_time()
@@ -62,7 +24,7 @@ def test_init_bdyval_exact(c1_data):
 
 def test_one_tend_intermediates(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data)
     e.set_diagnostics(True)
     o.tend()
     e.tend()
@@ -77,7 +39,7 @@ def test_one_tend_intermediates(c1_data):
 
 def test_one_step_state(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data)
     o.step(1)
     e.step(1)
     for name in STATE_FIELDS:
@@ -87,7 +49,7 @@ def test_one_step_state(c1_data):
 
 def test_twenty_steps_graph_replay(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data)
     o.step(20)
     e.step(20)
     for name in STATE_FIELDS:
@@ -100,12 +62,7 @@ def test_twenty_steps_graph_replay(c1_data):
 
 def test_tend_bdyval_equals_step(c1_data):
     rc, data = c1_data
-    from regcm_amd.dycore import DynCore
-    e1 = DynCore(rc, data["split"])
-    e2 = DynCore(rc, data["split"])
-    for e in (e1, e2):
-        e.put_state(data["state"])
-        e.bdyval()
+    e1, e2 = engine(rc, data), engine(rc, data)
     for _ in range(6):                  # the drop-in sequence: graph per call, both parities
         e1.tend()
         e1.bdyval()
@@ -119,15 +76,12 @@ def test_cfl_violation_stops_within_lag(c1_data):
     """A state that goes NaN stops rcmdyn_step within FLAG_LAG steps of the failing step
     (checked on the host from per-step flag snapshots, no per-step stream sync), reports the
     step the oracle fails at, and clears the flag once reported (Main/mod_tendency.F90:702)."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore, EngineError
+    from regcm_amd.dycore import EngineError
     rc, data = c1_data
     st = {k: v.copy() for k, v in data["state"].items()}
     for name in ("ATM1_T", "ATM2_T"):
         st[name][5, 20:24, 20:24] = np.nan
-    o = OracleCore(rc, data["split"])
-    o.put_state(st)
-    o.bdyval()
+    o = oracle(rc, data, st)
     fail = None
     for n in range(1, 20):
         try:
@@ -136,9 +90,7 @@ def test_cfl_violation_stops_within_lag(c1_data):
             fail = n
             break
     assert fail is not None
-    e = DynCore(rc, data["split"])
-    e.put_state(st)
-    e.bdyval()
+    e = engine(rc, data, st)
     with pytest.raises(EngineError, match=rf"CFL VIOLATION \(step {fail}\)"):
         e.step(100)
     assert e.get_time()[0] <= fail + 3             # FLAG_LAG = 2 steps in flight at most
@@ -152,14 +104,12 @@ def test_get_reports_failed_step(c1_data):
     """rcmdyn_get never hands out fields of a failed run: a step that went NaN inside the
     2-step report lag of rcmdyn_tend is reported by the next get (the reference's fatal stops
     before any output, Main/mod_tendency.F90:702)."""
-    from regcm_amd.dycore import DynCore, EngineError
+    from regcm_amd.dycore import EngineError
     rc, data = c1_data
     st = {k: v.copy() for k, v in data["state"].items()}
     for name in ("ATM1_T", "ATM2_T"):
         st[name][5, 20:24, 20:24] = np.nan
-    e = DynCore(rc, data["split"])
-    e.put_state(st)
-    e.bdyval()
+    e = engine(rc, data, st)
     with pytest.raises(EngineError, match="CFL VIOLATION"):
         for _ in range(6):
             e.tend()
@@ -172,12 +122,8 @@ def test_decomposition_invariance(c1_data, nproc):
     """Tiles exchanging halos reproduce the single-tile result bit-for-bit; tiles
     narrower than the split-step halo (1 x 7) take the per-sub-step exchange path."""
     rc, data = c1_data
-    from regcm_amd.dycore import DynCore
-    ref = DynCore(rc, data["split"])
-    til = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
+    ref, til = engine(rc, data), engine(rc, data, nproc=nproc)
     for e in (ref, til):
-        e.put_state(data["state"])
-        e.bdyval()
         e.step(6)
     for name in STATE_FIELDS:
         assert np.array_equal(ref.get(name), til.get(name)), name
@@ -187,14 +133,9 @@ def test_decomposition_invariance(c1_data, nproc):
 def test_decomposition_invariance_c3(nproc):
     """The headline domain on the set_nproc tilings of 2/4/8 GPUs (local tiles): bit-identical
     to one tile, including the partial blocks the ghost-ring kernels run on 96 x 48 tiles."""
-    from regcm_amd.dycore import DynCore
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
-    ref = DynCore(rc, data["split"])
-    til = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
+    rc, data, _ = case("C3")
+    ref, til = engine(rc, data), engine(rc, data, nproc=nproc)
     for e in (ref, til):
-        e.put_state(data["state"])
-        e.bdyval()
         e.step(5)
     for name in STATE_FIELDS:
         assert np.array_equal(ref.get(name), til.get(name)), name
@@ -208,16 +149,11 @@ def test_overlap_parts_bit_identical(monkeypatch, mode):
     part 2 follows the join.  C3 on 1 x 2 tiles (192 x 96: k_momentum / k_scalars have part-1
     blocks) is bit-identical to one tile, through rcmdyn_step, through the drop-in
     tend + bdyval pair (k_columns split only) and with the split off (RCMDYN_NO_OVERLAP)."""
-    from regcm_amd.dycore import DynCore
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
-    ref = DynCore(rc, data["split"])
+    rc, data, _ = case("C3")
+    ref = engine(rc, data)
     if mode == "serial":
         monkeypatch.setenv("RCMDYN_NO_OVERLAP", "1")
-    til = DynCore(rc, data["split"], nproc_j=1, nproc_i=2)
-    for e in (ref, til):
-        e.put_state(data["state"])
-        e.bdyval()
+    til = engine(rc, data, nproc=(1, 2))
     ref.step(5)
     if mode == "dropin":
         for _ in range(5):
@@ -237,23 +173,17 @@ def test_overlap_shifted_blocks_bit_identical(nproc):
     k_momentum / k_scalars in parts 1 and 2 start at the origin that puts one 64-wide column
     wholly inside the part-1 rectangle (rcmdyn_overlap_shares: 62 / 56 / 44 % of their points
     beside the exchange, none with the default origin).  Bit-identical to one tile."""
-    from regcm_amd.dycore import DynCore
-    rc = CONFIGS["C3"]
-    data = icbc.generate(rc)
-    ref = DynCore(rc, data["split"])
-    til = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
+    rc, data, _ = case("C3")
+    ref, til = engine(rc, data), engine(rc, data, nproc=nproc)
     for e in (ref, til):
-        e.put_state(data["state"])
-        e.bdyval()
         e.step(5)
     for name in STATE_FIELDS:
         assert np.array_equal(ref.get(name), til.get(name)), name
 
 
 def test_c2_ten_steps():
-    rc = CONFIGS["C2"]
-    data = icbc.generate(rc)
-    o, e = make_pair(rc, data)
+    rc, data, _ = case("C2")
+    o, e = pair(rc, data)
     o.step(10)
     e.step(10)
     for name in STATE_FIELDS:
@@ -282,12 +212,7 @@ def test_diagnostics_switch_is_transparent(c1_data):
 def test_kernel_times_hook(c1_data):
     """rcmdyn_kernel_times runs real (eager) steps and reports every kernel of the step."""
     rc, data = c1_data
-    from regcm_amd.dycore import DynCore
-    e1 = DynCore(rc, data["split"])
-    e2 = DynCore(rc, data["split"])
-    for e in (e1, e2):
-        e.put_state(data["state"])
-        e.bdyval()
+    e1, e2 = engine(rc, data), engine(rc, data)
     kt = e1.kernel_times(3)
     e2.step(3)
     for name in STATE_FIELDS:
@@ -335,7 +260,7 @@ def test_qfilter_fusion_equals_qfilter(c1_data, monkeypatch, variant, nproc):
         e.bdyval()
         e.step(5)
     assert fused.get_time() == sep.get_time()
-    for name in state_fields(rcv) + (["ATM1_TKE", "ATM2_TKE"] if rcv.ibltyp == 2 else []):
+    for name in state_names(rcv, tke=True):
         assert np.array_equal(fused.get(name), sep.get(name)), name
     assert np.array_equal(fused.reductions(), sep.reductions())
 
@@ -367,7 +292,7 @@ def test_fused_bdyval_equals_separate(c1_data, monkeypatch, variant, nproc):
         e.bdyval()
         e.step(5)
     assert fused.get_time() == sep.get_time()
-    for name in state_fields(rcv) + (["ATM1_TKE", "ATM2_TKE"] if rcv.ibltyp == 2 else []):
+    for name in state_names(rcv, tke=True):
         assert np.array_equal(fused.get(name), sep.get(name)), name
     assert np.array_equal(fused.reductions(), sep.reductions())
 
@@ -545,52 +470,41 @@ VARIANTS = [{"iboudy": 4}, {"iboudy": 3}, {"iboudy": 2}, {"iboudy": 1}, {"ipgf":
 DECOMP_VARIANTS = [v for v in VARIANTS if v.get("idiffu") != 3 and "ipptls" not in v]
 
 
-def _variant_id(v):
-    return ",".join(f"{k}={x}" for k, x in v.items())
-
-
-@pytest.mark.parametrize("variant", VARIANTS, ids=_variant_id)
+@pytest.mark.parametrize("variant", VARIANTS, ids=variant_id)
 def test_variant_parity(c1_data, variant):
     """Option variants match the oracle: 1 step < 1e-12, 3 steps < 1e-11.  Over 20 steps the
     engine-oracle difference must stay inside the oracle's own sensitivity to a 1e-14
     perturbation of the initial state (iboudy = 4's inflow/outflow switches flip on
     near-zero boundary winds, so ulp-level differences grow by branch flips, not by error)."""
     import dataclasses
-    from oracle.oracle import OracleCore
     rc, data = c1_data
     rcv = dataclasses.replace(rc, **variant)
-    o, e = make_pair(rcv, data)
+    o, e = pair(rcv, data, with_species(rcv, data["state"]))
     for nsteps, tol in ((1, 1e-12), (2, 1e-11)):
         o.step(nsteps)
         e.step(nsteps)
-        for name in state_fields(rcv):
+        for name in state_names(rcv):
             err = relerr(e.get(name), o.get(name), rcv, name)
             assert err < tol, (name, err, nsteps)
     o.step(17)
     e.step(17)
     st = {k: v.copy() for k, v in with_species(rcv, data["state"]).items()}
     st["ATM1_T"] = st["ATM1_T"] * (1.0 + 1e-14)
-    p = OracleCore(rcv, data["split"])
-    p.put_state(st)
-    p.bdyval()
+    p = oracle(rcv, data, st)
     p.step(20)
-    for name in state_fields(rcv):
+    for name in state_names(rcv):
         err = relerr(e.get(name), o.get(name), rcv, name)
         spread = relerr(p.get(name), o.get(name), rcv, name)
         assert err <= max(1e-9, 100.0 * spread), (name, err, spread)
 
 
-@pytest.mark.parametrize("variant", DECOMP_VARIANTS, ids=_variant_id)
+@pytest.mark.parametrize("variant", DECOMP_VARIANTS, ids=variant_id)
 def test_variant_decomposition(c1_data, variant):
     import dataclasses
-    from regcm_amd.dycore import DynCore
     rc, data = c1_data
     rcv = dataclasses.replace(rc, **variant)
-    ref = DynCore(rcv, data["split"])
-    til = DynCore(rcv, data["split"], nproc_j=2, nproc_i=2)
+    ref, til = engine(rcv, data), engine(rcv, data, nproc=(2, 2))
     for e in (ref, til):
-        e.put_state(data["state"])
-        e.bdyval()
         e.step(6)
     for name in STATE_FIELDS:
         assert np.array_equal(ref.get(name), til.get(name)), name
@@ -604,20 +518,14 @@ def test_idiffu3_tiles_match_oracle_tiles(c1_data, monkeypatch, nthreads, transp
     1 step < 1e-12, 3 steps < 1e-11; the column terms reach the neighbour's ring through their
     own exchange (also over RCCL), and the result differs from one tile."""
     import dataclasses
-    from oracle.oracle import OracleParallel
     from regcm_amd.config import set_nproc
-    from regcm_amd.dycore import DynCore
     rc, data = c1_data
     rcv = dataclasses.replace(rc, idiffu=3)
     cj, ci = set_nproc(nthreads, rc.jx, rc.iy)
     if transport == "rccl":
         monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
-    o = OracleParallel(rcv, data["split"], nthreads=nthreads)
-    e = DynCore(rcv, data["split"], nproc_j=cj, nproc_i=ci)
-    one = DynCore(rcv, data["split"])
-    for x in (o, e, one):
-        x.put_state(data["state"])
-        x.bdyval()
+    o, e = pair(rcv, data, nproc=(cj, ci), tiles=nthreads)
+    one = engine(rcv, data)
     for nsteps, tol in ((1, 1e-12), (2, 1e-11)):
         o.step(nsteps)
         e.step(nsteps)
@@ -642,12 +550,7 @@ def test_bdyval_qc_tall_tile(iy):
     rng = np.random.default_rng(11)
     for name in ("ATM1_QC", "ATM2_QC"):
         st[name] = rng.uniform(1e-6, 1e-4, size=st[name].shape) * st["PSA"][0][None]
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o, e = OracleCore(rc, data["split"]), DynCore(rc, data["split"])
-    for c in (o, e):
-        c.put_state(st)
-        c.bdyval()
+    o, e = pair(rc, data, st)
     for name in STATE_FIELDS:
         assert np.array_equal(e.get(name)[..., : rc.iy - 1, : rc.jx - 1],
                               o.get(name)[..., : rc.iy - 1, : rc.jx - 1]), name
@@ -668,12 +571,7 @@ def test_sladvection_departure_check(c1_data):
     st = {k: v.copy() for k, v in data["state"].items()}
     for name in ("ATM1_U", "ATM2_U"):
         st[name] = st[name] * 60.0               # ~600 m/s: u dt > dx at 60 km, 150 s
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o, e = OracleCore(rcv, data["split"]), DynCore(rcv, data["split"])
-    for c in (o, e):
-        c.put_state(st)
-        c.bdyval()
+    o, e = pair(rcv, data, st)
     with pytest.raises(FloatingPointError):
         o.tend()
     with pytest.raises(EngineError, match="SLADVECTION"):

@@ -12,69 +12,19 @@ libm ulps).  State after steps with physics tendencies: the same bounds as witho
 import numpy as np
 import pytest
 
-from regcm_amd.config import (ATMS_FIELDS, CONFIGS, NH_PHY_FIELDS, NH_STATE_FIELDS, PHY_FIELDS,
-                              STATE_FIELDS, field_levels)
-from regcm_amd import icbc
+from regcm_amd.config import ATMS_FIELDS, NH_STATE_FIELDS, STATE_FIELDS
+from tests.support import NH_FIELDS, case, engine, pair, physics_tendencies, relerr
 
 pytestmark = pytest.mark.gpu
 
 TRANSCENDENTAL = {"ATMS_TH3D", "ATMS_TP3D", "ATMS_ZQ", "ATMS_ZA", "ATMS_DZQ"}
 HYDRO_ONLY = {"ATMS_ZQ", "ATMS_ZA", "ATMS_DZQ"}
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB",
-         "DSTOR", "HSTOR", "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"}
-
-
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
-def physics_tendencies(rc, nh, seed=7):
-    """Synthetic pc_physic tendencies, coupled with p* (~90 cb) like aten: heating of a few
-    K/day, moistening/condensation of ~1e-3 kg/kg/day, momentum drag of a few m/s/day."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    scale = {"TPHY": 5e-3, "QVPHY": 1e-6, "QCPHY": 1e-7, "UPHY": 5e-3, "VPHY": 5e-3,
-             "PPPHY": 5e-2, "WPHY": 1e-4}
-    out = {}
-    for name in PHY_FIELDS + (NH_PHY_FIELDS if nh else []):
-        nk = field_levels(name, rc.kz, rc.nsplit)
-        x = rng.standard_normal((nk, rc.iy, rc.jx))
-        # moisture sources are non-negative: a negative forecast would trigger the
-        # negative-moisture fix, whose in-tile sweep (:382-393) makes the reference itself
-        # decomposition-dependent where such points meet a tile edge
-        out[name] = scale[name] * (np.abs(x) if name in ("QVPHY", "QCPHY") else x)
-    return out
-
-
-def make_pair(rc, data, nproc=(1, 1)):
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o = OracleCore(rc, data["split"])
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    for c in (o, e):
-        c.put_state(data["state"])
-        c.bdyval()
-    return o, e
-
-
-@pytest.fixture(scope="module")
-def nh_data():
-    rc = CONFIGS["N1"]
-    return rc, icbc.generate_nh(rc)
 
 
 def test_pre_post_equals_tend(c1_data):
     """pre_physics + post_physics with no physics is the fused tend, bit for bit."""
-    from regcm_amd.dycore import DynCore
     rc, data = c1_data
-    a = DynCore(rc, data["split"])
-    b = DynCore(rc, data["split"])
-    for c in (a, b):
-        c.put_state(data["state"])
-        c.bdyval()
+    a, b = engine(rc, data), engine(rc, data)
     for _ in range(3):
         a.tend()
         a.bdyval()
@@ -114,7 +64,7 @@ def sync_oracle(o, e, names, rc):
 
 def test_slice_export_parity(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
+    o, e = pair(rc, data)
     e.step(1)                 # leave the start-up steps (dt switch, filtered levels)
     e.tend()
     sync_oracle(o, e, STATE_FIELDS, rc)
@@ -125,8 +75,8 @@ def test_slice_export_parity(c1_data):
 
 def test_physics_tendencies_parity(c1_data):
     rc, data = c1_data
-    o, e = make_pair(rc, data)
-    phy = physics_tendencies(rc, False)
+    o, e = pair(rc, data)
+    phy = physics_tendencies(rc)
     for name, arr in phy.items():
         o.put(name, arr)
         e.put(name, arr)
@@ -138,7 +88,7 @@ def test_physics_tendencies_parity(c1_data):
         e.bdyval()
     e.step(2)                 # graph replay recaptured with the physics buffers
     o.step(2)
-    ref = make_pair(rc, data)[1]
+    ref = engine(rc, data)
     ref.step(5)
     for name in STATE_FIELDS:
         err = relerr(e.get(name), o.get(name), rc, name)
@@ -150,9 +100,8 @@ def test_physics_tendencies_parity(c1_data):
 @pytest.mark.parametrize("nproc", [(2, 2), (1, 3)])
 def test_seam_decomposition_invariance(c1_data, nproc):
     rc, data = c1_data
-    _, a = make_pair(rc, data)
-    _, b = make_pair(rc, data, nproc)
-    phy = physics_tendencies(rc, False, seed=11)
+    a, b = engine(rc, data), engine(rc, data, nproc=nproc)
+    phy = physics_tendencies(rc, seed=11)
     # no qc source: a cloud field under 4th-order diffusion produces negative forecasts, and
     # the negative-moisture fix sweeps within a tile (:382-393), so like the reference the
     # result would depend on the decomposition wherever such a point meets a tile edge
@@ -172,16 +121,16 @@ def test_seam_decomposition_invariance(c1_data, nproc):
         assert np.array_equal(a.get(name), b.get(name)), name
 
 
-def test_nh_physics_and_slices(nh_data):
-    rc, data = nh_data
-    o, e = make_pair(rc, data)
-    phy = physics_tendencies(rc, True)
+def test_nh_physics_and_slices():
+    rc, data, _ = case("N1")
+    o, e = pair(rc, data)
+    phy = physics_tendencies(rc)
     for name, arr in phy.items():
         o.put(name, arr)
         e.put(name, arr)
     o.step(2)
     e.step(2)
-    for name in STATE_FIELDS[:12] + NH_STATE_FIELDS:
+    for name in NH_FIELDS:
         err = relerr(e.get(name), o.get(name), rc, name)
         assert err < 1e-10, (name, err)
     e.tend()
@@ -192,7 +141,7 @@ def test_nh_physics_and_slices(nh_data):
     e.tend_post_physics()
     o.bdyval()
     e.bdyval()
-    for name in STATE_FIELDS[:12] + NH_STATE_FIELDS:
+    for name in NH_FIELDS:
         err = relerr(e.get(name), o.get(name), rc, name)
         assert err < 1e-11, (name, err)
 

@@ -13,22 +13,10 @@ counts.
 import numpy as np
 import pytest
 
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, STATE_FIELDS
-from regcm_amd import icbc
+from regcm_amd.config import STATE_FIELDS
+from tests.support import NH_FIELDS, case, engine, pair
 
 pytestmark = pytest.mark.gpu
-
-NH_FIELDS = ["ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T",
-             "ATM2_QV", "ATM2_QC", "PSA", "PSB"] + NH_STATE_FIELDS
-
-
-def _engine(rc, data, nproc_j=1, nproc_i=1):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc_j, nproc_i=nproc_i)
-    e.put_state(data["state"])
-    e.bdyval()
-    return e
-
 
 def test_runtime_info():
     from regcm_amd.dycore import runtime_info
@@ -40,11 +28,11 @@ def test_runtime_info():
 @pytest.mark.parametrize("mode", ["graph", "eager", "dropin"])
 def test_rccl_transport_hydrostatic(c1_data, monkeypatch, mode):
     rc, data = c1_data
-    one = _engine(rc, data)
+    one = engine(rc, data)
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
     if mode == "eager":
         monkeypatch.setenv("RCMDYN_NO_GRAPH", "1")
-    dec = _engine(rc, data, 2, 2)
+    dec = engine(rc, data, nproc=(2, 2))
     one.step(6)
     if mode == "dropin":
         for _ in range(6):
@@ -64,10 +52,10 @@ def test_rccl_shared_channel(c1_data, monkeypatch):
     """Both streams on the job's one communicator (RCMDYN_RCCL_CHAN2=one, the only mode), the
     second stream's exchange ordered after the first's.  Bit-identical to one tile."""
     rc, data = c1_data
-    one = _engine(rc, data)
+    one = engine(rc, data)
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
     monkeypatch.setenv("RCMDYN_RCCL_CHAN2", "one")
-    dec = _engine(rc, data, 2, 2)
+    dec = engine(rc, data, nproc=(2, 2))
     one.step(6)
     dec.step(6)
     for name in STATE_FIELDS:
@@ -75,11 +63,10 @@ def test_rccl_shared_channel(c1_data, monkeypatch):
 
 
 def test_rccl_transport_nonhydrostatic(monkeypatch):
-    rc = CONFIGS["N1"]
-    data = icbc.generate_nh(rc)
-    one = _engine(rc, data)
+    rc, data, _ = case("N1")
+    one = engine(rc, data)
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
-    dec = _engine(rc, data, 2, 2)
+    dec = engine(rc, data, nproc=(2, 2))
     for e in (one, dec):
         e.step(5)                       # eager steps 1-2 (day alarm: RCCL all-reduce), then graphs
     for name in NH_FIELDS:
@@ -90,12 +77,8 @@ def test_rccl_transport_nonhydrostatic(monkeypatch):
 
 def test_reductions_report(c1_data):
     """ptntot/pt2tot of the last step match the oracle's sums (Main/mod_tendency.F90:1449-1459)."""
-    from oracle.oracle import OracleCore
     rc, data = c1_data
-    e = _engine(rc, data)
-    o = OracleCore(rc, data["split"])
-    o.put_state(data["state"])
-    o.bdyval()
+    o, e = pair(rc, data)
     e.step(3)
     o.step(3)
     r = e.reductions()
@@ -114,10 +97,7 @@ def test_rccl_job_wide_cfl_stop(c1_data, monkeypatch):
     for name in ("ATM1_T", "ATM2_T"):
         st[name][5, 20:24, 20:24] = np.nan
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=2, nproc_i=2)
-    e.put_state(st)
-    e.bdyval()
+    e = engine(rc, data, st, (2, 2))
     with pytest.raises(EngineError, match=r"CFL VIOLATION \(job, by step (8|16)\)"):
         e.step(100)
     assert e.get_time()[0] <= 24

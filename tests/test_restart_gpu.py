@@ -12,30 +12,22 @@ import numpy as np
 import pytest
 
 from regcm_amd.config import STATE_FIELDS
+from tests.support import engine
 
 pytestmark = pytest.mark.gpu
-
-
-def fresh(rc, data, nproc=(1, 1)):
-    from regcm_amd.dycore import DynCore
-    e = DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    e.put_state(data["state"])
-    return e
 
 
 @pytest.mark.parametrize("nproc", [(1, 1), (2, 2)])
 def test_restart_bit_identical(c1_data, nproc):
     rc, data = c1_data
-    ref = fresh(rc, data)
-    ref.bdyval()
+    ref = engine(rc, data)
     ref.step(7)
-    run = fresh(rc, data)
-    run.bdyval()
+    run = engine(rc, data)
     run.step(4)
     sav = {name: run.get(name) for name in STATE_FIELDS}
     clock = run.get_time()
     run.close()
-    rst = fresh(rc, data, nproc)       # statics and boundary data, as init reads them again
+    rst = engine(rc, data, nproc=nproc, bdyval=False)    # statics and boundary data, as init reads them again
     for name, a in sav.items():
         rst.put(name, a)
     rst.set_time(*clock)

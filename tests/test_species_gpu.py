@@ -13,65 +13,30 @@ import numpy as np
 import pytest
 
 from regcm_amd import icbc
-from regcm_amd.config import CONFIGS, QX_ATMS_FIELDS, QX_STATE_FIELDS, QX_PHY_FIELDS, STATE_FIELDS
+from regcm_amd.config import QX_ATMS_FIELDS, QX_STATE_FIELDS, QX_PHY_FIELDS, STATE_FIELDS
+from tests.support import NH_FIELDS, case, engine, oracle, pair, relerr, variant_id
 
 pytestmark = pytest.mark.gpu
 
 ALL = list(STATE_FIELDS) + QX_STATE_FIELDS
-CROSS = {"ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSA", "PSB", "DSTOR", "HSTOR"} | \
-    set(QX_STATE_FIELDS)
-
-
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
-def species_state(rc, data):
-    st = {k: v.copy() for k, v in data["state"].items()}
-    st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))
-    return st
-
-
-def start(cls, rc, data, st, nproc=(1, 1), extra=None):
-    if cls.__name__ == "DynCore":
-        c = cls(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-    else:
-        c = cls(rc, data["split"])
-    c.put_state(st)
-    for name, a in (extra or {}).items():
-        c.put(name, a)
-    c.bdyval()
-    return c
 
 
 @pytest.fixture(scope="module")
-def qx_c1(c1_data):
-    rc, data = c1_data
-    rcq = dataclasses.replace(rc, ipptls=2)
-    return rcq, data, species_state(rcq, data)
+def qx_c1():
+    return case("C1", ipptls=2)
 
 
 VARIANTS = [{}, {"isladvec": 1}, {"idiffu": 2}, {"idiffu": 3}, {"iboudy": 4}, {"iboudy": 3},
             {"upstream_mode": 0}]
 
 
-def _vid(v):
-    return ",".join(f"{k}={x}" for k, x in v.items()) or "default"
-
-
-@pytest.mark.parametrize("variant", VARIANTS, ids=_vid)
+@pytest.mark.parametrize("variant", VARIANTS, ids=variant_id)
 def test_species_parity(qx_c1, variant):
     """ipptls = 2 against the oracle: the species bit-identical after one step (their chain has
     no transcendental; qdot, the mass fluxes and xkc are exact), every field < 1e-11 after 3."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
     rcv = dataclasses.replace(rc, **variant)
-    o, e = start(OracleCore, rcv, data, st), start(DynCore, rcv, data, st)
+    o, e = pair(rcv, data, st)
     o.step(1)
     e.step(1)
     # the interior bit-identical (the boundary lines take p* of the split corrections, which
@@ -93,14 +58,13 @@ def test_species_parity(qx_c1, variant):
 def test_species_change_the_step(qx_c1, c1_data):
     """The species are advected and their load reaches the geopotential: qi moves, and the
     temperature of an ipptls = 2 run differs from ipptls = 1 with the same qv, qc."""
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
-    e = start(DynCore, rc, data, st)
+    e = engine(rc, data, st)
     e.step(3)
     assert not np.array_equal(e.get("ATM1_QI"), st["ATM1_QI"])
     rc1 = c1_data[0]
     st1 = {k: v for k, v in st.items() if k not in QX_STATE_FIELDS}
-    e1 = start(DynCore, rc1, data, st1)
+    e1 = engine(rc1, data, st1)
     e1.step(3)
     assert not np.array_equal(e.get("ATM1_U"), e1.get("ATM1_U"))
 
@@ -108,11 +72,9 @@ def test_species_change_the_step(qx_c1, c1_data):
 def test_species_negative_fix(qx_c1):
     """The patchy cloud edges make negative species forecasts, some with negative sweep
     predecessors (the serial sweep); the fix is bit-identical to the oracle's serial loop."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
     from tests.test_parity_gpu import _dependent_negatives
     rc, data, st = qx_c1
-    o, e = start(OracleCore, rc, data, st), start(DynCore, rc, data, st)
+    o, e = pair(rc, data, st)
     o.tend()
     e.tend()
     dt = o.get_time()[1]
@@ -137,15 +99,10 @@ def test_species_tiles_match_oracle_tiles(qx_c1, monkeypatch, nthreads):
     depends on the decomposition, and so does the engine, tile for tile.  1 x 7 tiles are
     narrower than the split step's halo (its per-sub-step exchanges and the exchange of atmc%qx
     run as the reference's).  Species interior bit-identical after one step; < 1e-11 after 3."""
-    from oracle.oracle import OracleParallel
     from regcm_amd.config import set_nproc
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
     cj, ci = set_nproc(nthreads, rc.jx, rc.iy)
-    o = OracleParallel(rc, data["split"], nthreads=nthreads)
-    o.put_state(st)
-    o.bdyval()
-    e = start(DynCore, rc, data, st, (cj, ci))
+    o, e = pair(rc, data, st, (cj, ci), tiles=nthreads)
     o.step(1)
     e.step(1)
     for name in QX_STATE_FIELDS:
@@ -163,16 +120,12 @@ def test_species_tiles_match_oracle_tiles(qx_c1, monkeypatch, nthreads):
 def test_qc_tiles_match_oracle_tiles(c1_data, nthreads):
     """nqx = 2 with cloud water: the qc chain on decomposed tiles against the oracle's tiles
     (the fix's decomposition dependence above applies to qc as well)."""
-    from oracle.oracle import OracleParallel
     from regcm_amd.config import set_nproc
-    from regcm_amd.dycore import DynCore
     rc, data = c1_data
-    st = species_state(rc, data)
+    st = dict(data["state"])
+    st.update(icbc.hydrometeor_state(rc, st, nqx=rc.nqx))     # nqx = 2: patchy qc only
     cj, ci = set_nproc(nthreads, rc.jx, rc.iy)
-    o = OracleParallel(rc, data["split"], nthreads=nthreads)
-    o.put_state(st)
-    o.bdyval()
-    e = start(DynCore, rc, data, st, (cj, ci))
+    o, e = pair(rc, data, st, (cj, ci), tiles=nthreads)
     o.step(1)
     e.step(1)
     a, b = e.get("ATM1_QC")[:, 1:rc.iy - 2, 1:rc.jx - 2], o.get("ATM1_QC")[:, 1:rc.iy - 2, 1:rc.jx - 2]
@@ -188,11 +141,10 @@ def test_qc_tiles_match_oracle_tiles(c1_data, nthreads):
 def test_species_rccl_transport(qx_c1, monkeypatch, nproc):
     """The same tiles with their halos sent over RCCL (one-rank self send/receive) are
     bit-identical to the device-copy exchange."""
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
-    ref = start(DynCore, rc, data, st, nproc)
+    ref = engine(rc, data, st, nproc)
     monkeypatch.setenv("RCMDYN_FORCE_RCCL", "1")
-    til = start(DynCore, rc, data, st, nproc)
+    til = engine(rc, data, st, nproc)
     for e in (ref, til):
         e.step(4)
     for name in ALL:
@@ -204,11 +156,10 @@ def test_species_rccl_transport(qx_c1, monkeypatch, nproc):
 def test_species_step_forms(qx_c1, monkeypatch, env):
     """The step forms (qfuse, the fused bdyval, graph replay) and the drop-in call sequence agree
     bit for bit with species."""
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
-    ref = start(DynCore, rc, data, st)
+    ref = engine(rc, data, st)
     monkeypatch.setenv(env, "1")
-    alt = start(DynCore, rc, data, st)
+    alt = engine(rc, data, st)
     ref.step(5)
     for _ in range(5):
         alt.tend()
@@ -229,13 +180,9 @@ def test_negfix_wavefront_equals_row_sweep(name, monkeypatch):
     choice): some plane has more than 16 marked rows, and where the rows fill more than one
     wavefront (C3) every 64-row boundary holds a dependent negative with a negative predecessor
     on the row below it, so the ring between the wavefronts carries values that matter."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
     from tests.test_negfix_gpu import Marks, forecasts
-    rc = dataclasses.replace(CONFIGS[name], ipptls=2)
-    data = icbc.generate(CONFIGS[name])
-    st = species_state(rc, data)
-    o = start(OracleCore, rc, data, st)
+    rc, data, st = case(name, ipptls=2)
+    o = oracle(rc, data, st)
     sp = ["QC", "QI", "QR", "QS"]
     a2 = {nm: o.get(f"ATM2_{nm}") for nm in sp}
     o.tend()
@@ -253,7 +200,7 @@ def test_negfix_wavefront_equals_row_sweep(name, monkeypatch):
     runs = []
     for mode in ("0", "1"):
         monkeypatch.setenv("RCMDYN_NEGFIX_MODE", mode)
-        e = start(DynCore, rc, data, st)
+        e = engine(rc, data, st)
         e.step(4)
         runs.append(e)
     for name_ in ALL:
@@ -263,12 +210,10 @@ def test_negfix_wavefront_equals_row_sweep(name, monkeypatch):
 def test_species_physics_seam(qx_c1):
     """qxphy of qi, qr, qs enter the sums as the reference adds them (:332-335), against the
     oracle; pre + post physics is the whole tend."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
     rng = np.random.default_rng(11)
     phy = {n: rng.normal(0.0, 1e-9, (rc.kz, rc.iy, rc.jx)) * st["PSA"][0][None] for n in QX_PHY_FIELDS}
-    o, e = start(OracleCore, rc, data, st, extra=phy), start(DynCore, rc, data, st, extra=phy)
+    o, e = pair(rc, data, st, extra=phy)
     o.step(1)
     e.tend_pre_physics()
     e.tend_post_physics()
@@ -292,7 +237,7 @@ def test_species_restart(qx_c1):
     """A restart from the species' SAV fields (get / put) continues bit-identically."""
     from regcm_amd.dycore import DynCore
     rc, data, st = qx_c1
-    ref = start(DynCore, rc, data, st)
+    ref = engine(rc, data, st)
     ref.step(3)
     sav = {n: ref.get(n) for n in ALL}
     t = ref.get_time()
@@ -326,55 +271,40 @@ def test_species_fields_refused_for_nqx2(c1_data):
 # the fix and filter_raw_4d in place; the total load enters the water loading of w
 # (:1662-1671).  Tolerances as tests/test_nh_gpu.py (the NH step is transcendental almost
 # everywhere: 1e-11 after one step, 1e-10 after three).
-NH_ALL = ["ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T", "ATM2_QV", "ATM2_QC",
-          "PSA", "PSB", "ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"] + QX_STATE_FIELDS
-NH_CROSS = CROSS | {"ATM1_PP", "ATM2_PP", "ATM1_W", "ATM2_W"}
-
-
-def nh_relerr(a, b, rc, name):
-    if name in NH_CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
+NH_ALL = NH_FIELDS + QX_STATE_FIELDS
 
 
 @pytest.fixture(scope="module")
 def qx_n1():
-    rc = dataclasses.replace(CONFIGS["N1"], ipptls=2)
-    data = icbc.generate_nh(rc)
-    return rc, data, species_state(rc, data)
+    return case("N1", ipptls=2)
 
 
 NH_VARIANTS = [{}, {"isladvec": 1}, {"idiffu": 2}, {"idiffu": 3}, {"iboudy": 4}]
 
 
-@pytest.mark.parametrize("variant", NH_VARIANTS, ids=_vid)
+@pytest.mark.parametrize("variant", NH_VARIANTS, ids=variant_id)
 def test_nh_species_parity(qx_n1, variant):
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_n1
     rcv = dataclasses.replace(rc, **variant)
-    o, e = start(OracleCore, rcv, data, st), start(DynCore, rcv, data, st)
+    o, e = pair(rcv, data, st)
     for nsteps, tol in ((1, 1e-11), (2, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         for name in NH_ALL:
-            err = nh_relerr(e.get(name), o.get(name), rcv, name)
+            err = relerr(e.get(name), o.get(name), rcv, name)
             assert err < tol, (name, err, nsteps)
 
 
 def test_nh_species_change_the_step(qx_n1):
     """The species' load reaches w through the water loading: an ipptls = 2 run differs from
     ipptls = 1 with the same qv, qc."""
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_n1
-    e = start(DynCore, rc, data, st)
+    e = engine(rc, data, st)
     e.step(2)
     assert not np.array_equal(e.get("ATM1_QR"), st["ATM1_QR"])
     rc1 = dataclasses.replace(rc, ipptls=1)
     st1 = {k: v for k, v in st.items() if k not in QX_STATE_FIELDS}
-    e1 = start(DynCore, rc1, data, st1)
+    e1 = engine(rc1, data, st1)
     e1.step(2)
     assert not np.array_equal(e.get("ATM1_W"), e1.get("ATM1_W"))
 
@@ -383,20 +313,15 @@ def test_nh_species_change_the_step(qx_n1):
 def test_nh_species_tiles_match_oracle_tiles(qx_n1, nthreads):
     """The NH core decomposed, against the oracle's same tiles (the fix's decomposition
     dependence as test_species_tiles_match_oracle_tiles)."""
-    from oracle.oracle import OracleParallel
     from regcm_amd.config import set_nproc
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_n1
     cj, ci = set_nproc(nthreads, rc.jx, rc.iy)
-    o = OracleParallel(rc, data["split"], nthreads=nthreads)
-    o.put_state(st)
-    o.bdyval()
-    e = start(DynCore, rc, data, st, (cj, ci))
+    o, e = pair(rc, data, st, (cj, ci), tiles=nthreads)
     for nsteps, tol in ((1, 1e-11), (2, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         for name in NH_ALL:
-            err = nh_relerr(e.get(name), o.get(name), rc, name)
+            err = relerr(e.get(name), o.get(name), rc, name)
             assert err < tol, (name, err, nsteps)
 
 
@@ -404,11 +329,10 @@ def test_nh_species_tiles_match_oracle_tiles(qx_n1, nthreads):
 def test_nh_species_step_forms(qx_n1, monkeypatch, env):
     """2 x 2 tiles: graph replay, the overlapped exchanges and the RCCL transport against the
     drop-in call sequence with none of them, bit for bit."""
-    from regcm_amd.dycore import DynCore
     rc, data, st = qx_n1
-    ref = start(DynCore, rc, data, st, (2, 2))
+    ref = engine(rc, data, st, (2, 2))
     monkeypatch.setenv(env, "1")
-    alt = start(DynCore, rc, data, st, (2, 2))
+    alt = engine(rc, data, st, (2, 2))
     ref.step(4)
     if env == "RCMDYN_NO_GRAPH":
         for _ in range(4):
@@ -422,18 +346,12 @@ def test_nh_species_step_forms(qx_n1, monkeypatch, env):
 
 
 @pytest.mark.parametrize("core", ["hydrostatic", "nh"])
-def test_species_smooth_decomposition_bit_identical(c1_data, core):
+def test_species_smooth_decomposition_bit_identical(core):
     """With smooth hydrometeor layers (no cloud edges, so no negative forecast reaches the fix
     at a tile edge) a 2 x 2 decomposition with nqx = 5 is bit-identical to one tile, as the
     reference's decompositions are; with cloud edges the fix itself depends on the tiles
     (test_species_tiles_match_oracle_tiles)."""
-    from regcm_amd.dycore import DynCore
-    if core == "nh":
-        rc = dataclasses.replace(CONFIGS["N1"], ipptls=2)
-        data = icbc.generate_nh(rc)
-    else:
-        rc = dataclasses.replace(c1_data[0], ipptls=2)
-        data = c1_data[1]
+    rc, data, _ = case("N1" if core == "nh" else "C1", ipptls=2)
     st = dict(data["state"])
     hsig = (rc.sigma[1:] + rc.sigma[:-1]) * 0.5
     ps = st["PSA"][0]
@@ -442,8 +360,8 @@ def test_species_smooth_decomposition_bit_identical(c1_data, core):
         layer = peak * (0.2 + np.exp(-0.5 * ((hsig - s0) / w) ** 2))    # positive everywhere
         st[f"ATM1_{nm}"] = layer[:, None, None] * ps[None]
         st[f"ATM2_{nm}"] = 0.98 * st[f"ATM1_{nm}"]
-    one = start(DynCore, rc, data, st)
-    til = start(DynCore, rc, data, st, (2, 2))
+    one = engine(rc, data, st)
+    til = engine(rc, data, st, (2, 2))
     one.step(4)
     til.step(4)
     names = (NH_ALL if core == "nh" else ALL)

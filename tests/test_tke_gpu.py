@@ -15,63 +15,36 @@ import numpy as np
 import pytest
 
 from regcm_amd import icbc
-from regcm_amd.config import CONFIGS, NH_STATE_FIELDS, STATE_FIELDS, TKE_STATE_FIELDS
+from regcm_amd.config import NH_STATE_FIELDS, STATE_FIELDS, TKE_STATE_FIELDS
+from tests.support import case, engine, oracle, pair, relerr, variant_id
 
 pytestmark = pytest.mark.gpu
 
-CROSS = {"ATM1_TKE", "ATM2_TKE"}
 
-
-def relerr(a, b, rc, name):
-    if name in CROSS:
-        a = a[:, : rc.iy - 1, : rc.jx - 1]
-        b = b[:, : rc.iy - 1, : rc.jx - 1]
-    den = max(np.max(np.abs(b)), 1e-300)
-    return float(np.max(np.abs(a - b)) / den)
-
-
-def start(c, rc, data, tke=True):
-    c.put_state(data["state"])
-    if tke:
-        for name, a in icbc.tke_state(rc).items():
-            c.put(name, a)
-    c.bdyval()
-    return c
-
-
+# (rc, data, state): the state holds the TKE after the generated fields, so it is put after them
 @pytest.fixture(scope="module")
-def tke_c1(c1_data):
-    rc, data = c1_data
-    return dataclasses.replace(rc, ibltyp=2), data
+def tke_c1():
+    return case("C1", ibltyp=2)
 
 
 @pytest.fixture(scope="module")
 def tke_n1():
-    rc = dataclasses.replace(CONFIGS["N1"], ibltyp=2)
-    return rc, icbc.generate_nh(rc)
-
-
-def pair(rc, data, nproc=(1, 1)):
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    o = start(OracleCore(rc, data["split"]), rc, data)
-    e = start(DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1]), rc, data)
-    return o, e
+    return case("N1", ibltyp=2)
 
 
 def test_tke_init_bdyval_exact(tke_c1):
-    rc, data = tke_c1
-    o, e = pair(rc, data)
+    rc, data, st = tke_c1
+    o, e = pair(rc, data, st)
     for name in TKE_STATE_FIELDS:
         assert np.array_equal(e.get(name), o.get(name)), name
 
 
 @pytest.mark.parametrize("variant", [{}, {"idiffu": 2}, {"idiffu": 3}, {"iboudy": 4}, {"iboudy": 3}, {"upstream_mode": 0}],
-                         ids=lambda v: ",".join(f"{k}={x}" for k, x in v.items()) or "default")
+                         ids=variant_id)
 def test_tke_parity(tke_c1, variant):
-    rc, data = tke_c1
+    rc, data, st = tke_c1
     rc = dataclasses.replace(rc, **variant)
-    o, e = pair(rc, data)
+    o, e = pair(rc, data, st)
     for nsteps, tol in ((1, 1e-12), (2, 1e-11)):
         o.step(nsteps)
         e.step(nsteps)
@@ -84,11 +57,10 @@ def test_tke_parity(tke_c1, variant):
 
 
 def test_tke_leaves_the_state_alone(tke_c1, c1_data):
-    from regcm_amd.dycore import DynCore
-    rc, data = tke_c1
+    rc, data, st = tke_c1
     rc0, _ = c1_data
-    a = start(DynCore(rc, data["split"]), rc, data)
-    b = start(DynCore(rc0, data["split"]), rc0, data, tke=False)
+    a = engine(rc, data, st)
+    b = engine(rc0, data)
     a.step(4)
     b.step(4)
     for name in STATE_FIELDS:
@@ -97,10 +69,9 @@ def test_tke_leaves_the_state_alone(tke_c1, c1_data):
 
 @pytest.mark.parametrize("nproc", [(2, 2), (1, 3)])
 def test_tke_decomposition_invariance(tke_c1, nproc):
-    from regcm_amd.dycore import DynCore
-    rc, data = tke_c1
-    a = start(DynCore(rc, data["split"]), rc, data)
-    b = start(DynCore(rc, data["split"], nproc_j=nproc[0], nproc_i=nproc[1]), rc, data)
+    rc, data, st = tke_c1
+    a = engine(rc, data, st)
+    b = engine(rc, data, st, nproc)
     a.step(5)
     b.step(5)
     for name in TKE_STATE_FIELDS + STATE_FIELDS:
@@ -109,8 +80,8 @@ def test_tke_decomposition_invariance(tke_c1, nproc):
 
 def test_tke_physics_tendency(tke_c1):
     """The UW scheme's tendency (TKEPHY) enters tketen after the dyn part (:530-531)."""
-    rc, data = tke_c1
-    o, e = pair(rc, data)
+    rc, data, st = tke_c1
+    o, e = pair(rc, data, st)
     rng = np.random.Generator(np.random.PCG64(3))
     phy = 1e-4 * rng.standard_normal((rc.kz + 1, rc.iy, rc.jx))
     for c in (o, e):
@@ -122,17 +93,16 @@ def test_tke_physics_tendency(tke_c1):
 
 
 def test_nh_tke_parity(tke_n1):
-    rc, data = tke_n1
-    o, e = pair(rc, data)
+    rc, data, st = tke_n1
+    o, e = pair(rc, data, st)
     for nsteps, tol in ((1, 1e-11), (2, 1e-10)):
         o.step(nsteps)
         e.step(nsteps)
         for name in TKE_STATE_FIELDS:
             err = relerr(e.get(name), o.get(name), rc, name)
             assert err < tol, (name, err, nsteps)
-    from regcm_amd.dycore import DynCore
-    til = start(DynCore(rc, data["split"], nproc_j=2, nproc_i=2), rc, data)
-    ref = start(DynCore(rc, data["split"]), rc, data)
+    til = engine(rc, data, st, (2, 2))
+    ref = engine(rc, data, st)
     til.step(4)
     ref.step(4)
     for name in TKE_STATE_FIELDS + NH_STATE_FIELDS:
@@ -143,12 +113,9 @@ def test_nh_tke_parity(tke_n1):
 def test_tke_idiffu3_tiles_match_oracle_tiles(tke_c1, tke_n1, core):
     """idiffu = 3 with the TKE (diffu_x3df of atm2 tke with nuk on each tile's column j = jci2,
     Main/mod_diffusion.F90:602-651) on 2 x 2 tiles against the oracle run as the same tiles."""
-    from oracle.oracle import OracleParallel
-    from regcm_amd.dycore import DynCore
-    rc, data = tke_c1 if core == "hydrostatic" else tke_n1
+    rc, data, st = tke_c1 if core == "hydrostatic" else tke_n1
     rc = dataclasses.replace(rc, idiffu=3)
-    o = start(OracleParallel(rc, data["split"], nthreads=4), rc, data)
-    e = start(DynCore(rc, data["split"], nproc_j=2, nproc_i=2), rc, data)
+    o, e = pair(rc, data, st, (2, 2), tiles=4)
     tol = 1e-11 if core == "hydrostatic" else 1e-10
     o.step(2)
     e.step(2)
@@ -163,7 +130,7 @@ def test_tke_errors(c1_data, tke_c1):
     e = DynCore(rc, data["split"])
     with pytest.raises(EngineError, match="ibltyp=2"):
         e.put("ATM1_TKE", np.zeros((rc.kz + 1, rc.iy, rc.jx)))
-    rc2, _ = tke_c1
+    rc2 = tke_c1[0]
     e2 = DynCore(rc2, data["split"])
     with pytest.raises(EngineError, match="no TKE tendency"):
         e2.get("TKEPHY")
@@ -173,10 +140,10 @@ def test_tke_restart_bit_identical(tke_c1):
     """SAV restart with the UW TKE (mod_savefile writes atm1/atm2 tke for ibltyp = 2): the
     continued run equals the uninterrupted one bit for bit, also on another decomposition."""
     from regcm_amd.dycore import DynCore
-    rc, data = tke_c1
-    ref = start(DynCore(rc, data["split"]), rc, data)
+    rc, data, st = tke_c1
+    ref = engine(rc, data, st)
     ref.step(6)
-    run = start(DynCore(rc, data["split"]), rc, data)
+    run = engine(rc, data, st)
     run.step(3)
     names = STATE_FIELDS + TKE_STATE_FIELDS
     sav = {n: run.get(n) for n in names}
@@ -207,42 +174,28 @@ def test_uw_vertical_flux_parity(tke_c1, tke_n1, core):
     overshoot test at kpbl compares |f(kpb-2) + slope dh - f(kpb)| with |f(kpb-1) - f(kpb)|,
     which are the same number whenever the min/max picks the upper layer's gradient, so an
     ulp of input difference (the log/pow of the PGF reach qdot) decides that branch."""
-    from oracle.oracle import OracleCore
-    from regcm_amd.dycore import DynCore
-    rc, data = tke_c1 if core == "hydrostatic" else tke_n1
+    rc, data, _ = tke_c1 if core == "hydrostatic" else tke_n1
     rcu, st, kpbl = _uw(rc, data)
     kpbl2 = np.roll(kpbl, 3, axis=-1)
-
-    def start(cls, state):
-        c = cls(rcu, data["split"])
-        c.put_state(state)
-        for name, a in icbc.tke_state(rcu).items():
-            c.put(name, a)
-        c.put("KPBL", kpbl)
-        c.bdyval()
-        return c
-    o, e = start(OracleCore, st), start(DynCore, st)
+    extra = dict(icbc.tke_state(rcu), KPBL=kpbl)
+    o, e = pair(rcu, data, st, extra=extra)
     stp = dict(st)
     stp["ATM1_T"] = st["ATM1_T"] * (1.0 + 1e-14)
-    p = start(OracleCore, stp)
+    p = oracle(rcu, data, stp, extra=extra)
     for n, c in enumerate((o, e, p)):
         c.step(1)
         if n < 2:
             for name in STATE_FIELDS:
-                err = relerr(e.get(name), o.get(name), rcu, name) if n == 1 else 0.0
+                err = relerr(e.get(name), o.get(name), rcu, name, crop=False) if n == 1 else 0.0
                 assert err < 1e-11, (name, err)
     for c in (o, e, p):
         c.put("KPBL", kpbl2)
         c.step(3)
     for name in STATE_FIELDS:
-        err = relerr(e.get(name), o.get(name), rcu, name)
-        spread = relerr(p.get(name), o.get(name), rcu, name)
+        err = relerr(e.get(name), o.get(name), rcu, name, crop=False)
+        spread = relerr(p.get(name), o.get(name), rcu, name, crop=False)
         assert err <= max(1e-10, 100.0 * spread), (name, err, spread)
-    base = DynCore(rc, data["split"])
-    base.put_state(st)
-    for name, a in icbc.tke_state(rc).items():
-        base.put(name, a)
-    base.bdyval()
+    base = engine(rc, data, st, extra=icbc.tke_state(rc))
     base.step(4)
     assert not np.array_equal(base.get("ATM1_QC"), e.get("ATM1_QC"))
 
@@ -250,17 +203,12 @@ def test_uw_vertical_flux_parity(tke_c1, tke_n1, core):
 def test_uw_decomposition_and_refusal(tke_c1):
     """iuwvadv = 1 is bit-identical on 2 x 2 tiles; a kpbl above kz is refused at the put
     ('kpbl is greater than kz', Main/mod_advection.F90:923-925)."""
-    from regcm_amd.dycore import DynCore, EngineError
-    rc, data = tke_c1
+    from regcm_amd.dycore import EngineError
+    rc, data, _ = tke_c1
     rcu, st, kpbl = _uw(rc, data)
     runs = []
     for nproc in ((1, 1), (2, 2)):
-        e = DynCore(rcu, data["split"], nproc_j=nproc[0], nproc_i=nproc[1])
-        e.put_state(st)
-        for name, a in icbc.tke_state(rcu).items():
-            e.put(name, a)
-        e.put("KPBL", kpbl)
-        e.bdyval()
+        e = engine(rcu, data, st, nproc, extra=dict(icbc.tke_state(rcu), KPBL=kpbl))
         e.step(4)
         runs.append(e)
     for name in STATE_FIELDS:
