@@ -34,6 +34,7 @@
 #include "tke.hpp"
 #include "fieldtab.hpp"
 #include "massck.hpp"
+#include "optset.hpp"
 
 using namespace rcm;
 
@@ -177,12 +178,14 @@ void setup_boundaries(const Geom& g, int jx, int iy, int nsp, bool ldot, std::ve
 }
 
 // Launch with an optional HIP event pair around the kernel (rcmdyn_kernel_times).
-#define KLAUNCH(kern, ...)                                  \
+#define KLAUNCH(kern, ...) KLAUNCH_AS(#kern, kern, __VA_ARGS__)
+// the same under a given name: the instances of one kernel (optset.hpp) report one name
+#define KLAUNCH_AS(name, kern, ...)                         \
   do {                                                      \
     if (dry) break;                                         \
     hipEvent_t e0_ = prof ? prof->begin(stream) : nullptr;  \
     hipLaunchKernelGGL(kern, __VA_ARGS__);                  \
-    if (prof) prof->end(stream, #kern, e0_);                \
+    if (prof) prof->end(stream, name, e0_);                 \
   } while (0)
 // a stream-path HIP call that a plan-only engine (rcmdyn_exchange_plan) skips
 #define DHIPCHK(x)           \
@@ -277,6 +280,9 @@ struct Switches {
   // decomposed domain; RCMDYN_NO_OVERLAP=1: the atm1/p* part first, then the atm2 part beside
   // k_columns only
   bool no_overlap = false;
+  // RCMDYN_NO_OPTSET (present): the generic instances of k_momentum, k_scalars and k_update
+  // everywhere, also where the default-set ones would fit (optset.hpp)
+  bool no_optset = false;
   // RCMDYN_FORCE_RCCL=1: the halo messages between tiles held by this engine travel as RCCL
   // sends/receives to itself (one-rank communicator), not as device copies
   bool force_rccl = false;
@@ -300,6 +306,7 @@ struct Switches {
     s.lazy_tend = !present("RCMDYN_NO_LAZY_TEND");
     s.no_qfuse = nonzero("RCMDYN_NO_QFUSE");
     s.no_overlap = nonzero("RCMDYN_NO_OVERLAP");
+    s.no_optset = optset_disabled_by_env();
     s.force_rccl = present("RCMDYN_FORCE_RCCL");
     s.negfix_mode = number("RCMDYN_NEGFIX_MODE", 0);
     s.inject_launch_failure = number("RCMDYN_INJECT_LAUNCH_FAILURE", 0);
@@ -748,6 +755,9 @@ struct rcmdyn_engine {
     const K ks[] = {{(const void*)k_update, SBT, "k_update"},
                     {(const void*)k_momentum, MBT, "k_momentum"},
                     {(const void*)k_scalars, SBT, "k_scalars"},
+                    {(const void*)k_update_gen, SBT, "k_update_gen"},
+                    {(const void*)k_momentum_gen, MBT, "k_momentum_gen"},
+                    {(const void*)k_scalars_gen, SBT, "k_scalars_gen"},
                     {(const void*)k_update_bud, SBT, "k_update_bud"},
                     {(const void*)k_scalars_bud, SBT, "k_scalars_bud"},
                     {(const void*)k_qx_tend, QBT, "k_qx_tend"}};
@@ -1894,6 +1904,20 @@ struct rcmdyn_engine {
     return f;
   }
 
+  // the instance of k_momentum / k_scalars / k_update a launch with the argument
+  // block f takes (optset.hpp): from the configuration and the pointers the launch passes
+  OptInstance opt_instance(const Fields& f) const {
+    OptQuery q{};
+    q.iboudy = cfg.iboudy; q.idiffu = cfg.idiffu; q.ipgf = cfg.ipgf; q.isladvec = cfg.isladvec;
+    q.ibltyp = cfg.ibltyp; q.iuwvadv = cfg.iuwvadv; q.nqx_extra = hc.nsp;
+    q.budget = budget; q.no_optset = sw.no_optset;
+    q.tten = f.tten; q.uten = f.uten; q.vten = f.vten; q.qvten = f.qvten; q.qcten = f.qcten;
+    q.omega = f.omega; q.xkcs = f.xkcs;
+    q.tphy = f.tphy; q.qvphy = f.qvphy; q.qcphy = f.qcphy; q.uphy = f.uphy; q.vphy = f.vphy;
+    q.kpbl = f.kpbl;
+    return optset_instance(q);
+  }
+
   // dynamic LDS of the two-phase column kernels: 4 x kz x 64 doubles
   size_t col_lds() const { return sizeof(double) * 4 * COLW * (size_t)cfg.kz; }
 
@@ -2345,23 +2369,32 @@ struct rcmdyn_engine {
       const int mnx = (mj2 - mo + MBJ) / MBJ, mny = (mi2 - g.idi1 + MBI) / MBI;
       const int snx = (g.jcx2() - so + SBJ) / SBJ, sny = (g.icx2() - g.icx1() + SBI) / SBI;
       const int xcd = (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW);
+      const dim3 grid(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz);
+      const Fields fm = fields(t, pm), fs = fields(t, ps);
       if (budget)
-        KLAUNCH(k_update_bud, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc,
-                ds, fields(t, pm), fields(t, ps), mnx, mny, snx, sny, xcd, budget_args(t));
+        KLAUNCH(k_update_bud, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd, budget_args(t));
+      else if (opt_instance(fm) == OPT_DEFAULT && opt_instance(fs) == OPT_DEFAULT)
+        KLAUNCH(k_update, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd);
       else
-        KLAUNCH(k_update, dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc, ds,
-                fields(t, pm), fields(t, ps), mnx, mny, snx, sny, xcd);
+        KLAUNCH_AS("k_update", k_update_gen, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd);
       return;
     }
-    if (pm >= 0)
+    const bool def = opt_instance(fields(t)) == OPT_DEFAULT;
+    if (pm >= 0 && def)
       KLAUNCH(k_momentum, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz), dim3(MBT), 0,
               stream, g, dc, ds, fields(t, pm));
+    else if (pm >= 0)
+      KLAUNCH_AS("k_momentum", k_momentum_gen, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz),
+                 dim3(MBT), 0, stream, g, dc, ds, fields(t, pm));
     if (ps >= 0 && budget)
       KLAUNCH(k_scalars_bud, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
               dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t));
-    else if (ps >= 0)
+    else if (ps >= 0 && def)
       KLAUNCH(k_scalars, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
               dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
+    else if (ps >= 0)
+      KLAUNCH_AS("k_scalars", k_scalars_gen, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
+                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
   }
 
   void tend_post(Corr corr, bool post_inner) {

@@ -61,8 +61,9 @@ __global__ void k_surface_pressures(Geom g, Fields f) {
 }
 
 // the nudging coefficients of band line ib at level k (relax, pointops.hpp)
+template <class O>
 __device__ __forceinline__ void nudge_coef(const Consts* c, int ib, int k, double& xf, double& xg) {
-  if (c->iboudy == 1) { xf = c->fcx[ib]; xg = c->gcx[ib]; }
+  if (O::iboudy(c) == 1) { xf = c->fcx[ib]; xg = c->gcx[ib]; }
   else { xf = c->hefc[ib][k]; xg = c->hegc[ib][k]; }
 }
 
@@ -336,7 +337,7 @@ __global__ __launch_bounds__(COLT, COL_LB) void k_columns(Geom g, const Consts* 
         pt = c->wgtx[ibc] * pt + (d_one - c->wgtx[ibc]) * pbt0;
       } else if (ci && rgc > 0) {
         double xf, xg;
-        nudge_coef(c, ibc, kz, xf, xg);
+        nudge_coef<OptGeneric>(c, ibc, kz, xf, xg);
         pt = relax(pt, xf, xg, fg1[0], fg1[1], fg1[2], fg1[3], fg1[4]);
       }
       ST(f.ptenn, o2, pt);
@@ -547,7 +548,9 @@ struct MomLDS {
   } sX;
   double sTV[TH0][TW0], sQ0[TH0][TW0], sQ1[TH0][TW0], sPH[TH0][TW0], sPS[TH0][TW0], sXK[TH0][TW0];
 };
-// one k_momentum block (bx, by, bz) with its LDS (k_momentum, or the momentum blocks of k_update)
+// one k_momentum block (bx, by, bz) with its LDS (k_momentum, or the momentum blocks of k_update);
+// O: the option policy (pointops.hpp)
+template <class O>
 __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __restrict__ c,
                                                const StepState* __restrict__ s, const Fields& f, MomLDS& L,
                                                int bx, int by, int bz) {
@@ -630,7 +633,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
     if (t < TW1 * TH1) {
       const bool ok = aok[n];
       double ud = ok ? au[n] * ar[n] : 0.0, vd = ok ? av[n] * ar[n] : 0.0;
-      if ((c->iboudy == 3 || c->iboudy == 4) && ok) {
+      if ((O::iboudy(c) == 3 || O::iboudy(c) == 4) && ok) {
         const int jg = J0 - 1 + jj, ig = I0 - 1 + ii;
         if (g.gjeq(jg, 1) || g.gjeq(jg, g.gjx) || ig == 1 || ig == g.giy) {
           const double2 bb = udvd_bdy(g, f, jg, ig, kof);
@@ -764,7 +767,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
   // nudgeuv (iboudy 1/5); the sponge of iboudy = 4 (spongeuv, Main/mod_bdycod.F90:2735-2813)
   // acts on the still-zero total tendency, so it enters as the first summand below
   double spu = d_zero, spv = d_zero;
-  if (rgd > 0 && c->iboudy == 4) {
+  if (rgd > 0 && O::iboudy(c) == 4) {
     const int ib = f.ibdt[o2 >> 3];
     spu = c->wgtd[ib] * d_zero + (d_one - c->wgtd[ib]) * LD(f.ubt, o3);
     spv = c->wgtd[ib] * d_zero + (d_one - c->wgtd[ib]) * LD(f.vbt, o3);
@@ -772,7 +775,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
     const double xt = s->xbctime + dt;
     double xf, xg;
     const int ib = f.ibdt[o2 >> 3];
-    if (c->iboudy == 1) { xf = c->fcx[ib]; xg = c->gcx[ib]; } else { xf = c->hefc[ib][k]; xg = c->hegc[ib][k]; }
+    nudge_coef<O>(c, ib, k, xf, xg);
 #define FGU(dj, di) bdy_minus_state(LD(f.ub0, O3(dj, di)), LD(f.ubt, O3(dj, di)), LD(f.a2u, O3(dj, di)), xt)
 #define FGV(dj, di) bdy_minus_state(LD(f.vb0, O3(dj, di)), LD(f.vbt, O3(dj, di)), LD(f.a2v, O3(dj, di)), xt)
     ut = relax(ut, xf, xg, FGU(0, 0), FGU(-1, 0), FGU(1, 0), FGU(0, -1), FGU(0, 1));
@@ -781,7 +784,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
 #undef FGV
   }
   // diffu_d (idiffu = 1); xkd from calc_coeff (Main/mod_diffusion.F90:237-248)
-  if (c->idiffu == 3) {                     // the column term of k_diffu6
+  if (O::idiffu(c) == 3) {                  // the column term of k_diffu6
     if (j == g.jdi2 || (!g.bl && j == g.jde1 - 1)) {
       ut = ut + LD(f.d6u, o3);
       vt = vt + LD(f.d6v, o3);
@@ -790,7 +793,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
     double xkd = d_rfour * (sXK[a0][b0] + sXK[a0 - 1][b0 - 1] + sXK[a0 - 1][b0] + sXK[a0][b0 - 1]);
     xkd = xkd * c->rdxsq * pdotb;
 #define UM(S, dj, di) S[a2 + (di)][b2 + (dj)]
-    if (c->idiffu == 2) {                   // 9-point scheme on jdi x idi, :386-411
+    if (O::idiffu(c) == 2) {                // 9-point scheme on jdi x idi, :386-411
       ut = ut + xkd * (o4_c1 * (UM(sUM, 1, 0) + UM(sUM, -1, 0) + UM(sUM, 0, 1) + UM(sUM, 0, -1)) +
                        o4_c2 * (UM(sUM, 1, 1) + UM(sUM, -1, -1) + UM(sUM, -1, 1) + UM(sUM, 1, -1)) +
                        o4_c3 * (UM(sUM, 0, 0)));
@@ -810,7 +813,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
                    z4_c2 * (UM(sUM, 0, 0)));                                                          \
   vt = vt + xkd * (z4_c1 * (UM(sVM, 1, 0) + UM(sVM, -1, 0) + UM(sVM, 0, 1) + UM(sVM, 0, -1)) +        \
                    z4_c2 * (UM(sVM, 0, 0)));
-    if (c->idiffu == 1) {
+    if (O::idiffu(c) == 1) {
       if (g.gjeq(j, 2)) { LAPD(); }
       if (g.gjeq(j, g.gjx - 1)) { LAPD(); }
       if (i == 2) { LAPD(); }
@@ -822,7 +825,7 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
   // pressure gradient force, part 1 (ipgf = 0) and part 2 (geopotential gradient)
   {
     double rtbar = d_rfour * (sTV[a0 - 1][b0 - 1] + sTV[a0][b0 - 1] + sTV[a0 - 1][b0] + sTV[a0][b0]);
-    if (c->ipgf == 1)                       // reference-atmosphere temperature, :1945-1946
+    if (O::ipgf(c) == 1)                    // reference-atmosphere temperature, :1945-1946
       rtbar = rtbar - T00PG * rcm_powpos((c->hsigma[k] * pdota + c->ptop) / P00PG, c->pgfaa1);
     rtbar = c->rgas * rtbar * pdota;
     const double den = c->dx * mfd;
@@ -836,9 +839,9 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
   }
   // totals uten + udyn + uphy (Main/mod_tendency.F90:404-411), forecast, RA filter
   // (pc_physic of the coupling seam, loaded here to keep registers free: absent = 0)
-  ut = (spu + ut) + (f.uphy ? LD(f.uphy, o3) : d_zero);
-  vt = (spv + vt) + (f.vphy ? LD(f.vphy, o3) : d_zero);
-  if (f.uten) { ST(f.uten, o3, ut); ST(f.vten, o3, vt); }
+  ut = (spu + ut) + (O::has(f.uphy) ? LD(f.uphy, o3) : d_zero);
+  vt = (spv + vt) + (O::has(f.vphy) ? LD(f.vphy, o3) : d_zero);
+  if (O::has(f.uten)) { ST(f.uten, o3, ut); ST(f.vten, o3, vt); }
   const double g1 = c->gnu1;
   const double u2 = u2c, v2 = v2c;
   const double cu = u2 + dt * ut, cv = v2 + dt * vt;
@@ -850,10 +853,16 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
   ST(f.b1v, o3, cv);
   PT_PRINT(2);
 }
+// the default-set instance (optset.hpp) and the generic one
 __global__ __launch_bounds__(MBT, MO_LB) void k_momentum(Geom g, const Consts* __restrict__ c,
                                                      const StepState* __restrict__ s, Fields f) {
   __shared__ MomLDS L;
-  momentum_block(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+  momentum_block<OptDefault>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+}
+__global__ __launch_bounds__(MBT, MO_LB) void k_momentum_gen(Geom g, const Consts* __restrict__ c,
+                                                         const StepState* __restrict__ s, Fields f) {
+  __shared__ MomLDS L;
+  momentum_block<OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -948,7 +957,7 @@ struct ScaLDS {
 // accumulator (ten2diag, :2123-2175) at the tile's own interior points.  Hydrostatic qv has no
 // adiabatic term (its difference is 0 exactly: qdiag%adi is left alone); iboudy = 4 adds the
 // sponge value itself (pc_total, no ten0); iboudy 0, 2, 3 never write the bdy term.
-template <bool BUD>
+template <bool BUD, class O>
 __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __restrict__ c,
                                               const StepState* __restrict__ s, const Fields& f, ScaLDS& L,
                                               int bx, int by, int bz, const Budget& b) {
@@ -1076,14 +1085,14 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   if (!g.gci(j, i)) {
     ST(f.cqv, o3, qv2);
     ST(f.cqc, o3, qc2);
-    if (f.xkcs) ST(f.xkcs, o3, xkc);
+    if (O::has(f.xkcs)) ST(f.xkcs, o3, xkc);
     return;
   }
   const double dt = s->dt;
   const int b1 = tj + 1, a1 = ti + 1, b2 = tj + 2, a2 = ti + 2;
   // budget: acc = acc + (after - before) * rw at an owned interior point
   const bool bown = BUD && in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
-  const bool bbdy = c->iboudy == 1 || c->iboudy == 4 || c->iboudy == 5;
+  const bool bbdy = O::iboudy(c) == 1 || O::iboudy(c) == 4 || O::iboudy(c) == 5;
   auto bud = [&](double* acc, double after, double before) {
     if (bown) ST(acc, o3, LD(acc, o3) + (after - before) * b.rw);
   };
@@ -1095,12 +1104,12 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   const double vavg2 = DT(sVMC, 1, 1) + DT(sVMC, 0, 1);
   const double ps = H1T(sPS, 0, 0);
   const double xkcs = xkc * c->rdxsq * pb;
-  if (f.xkcs) ST(f.xkcs, o3, xkcs);
+  if (O::has(f.xkcs)) ST(f.xkcs, o3, xkcs);
   // diffu_x from a halo-2 LDS tile (Main/mod_diffusion.F90:673-735, 881-891); idiffu = 3: the
   // column term of k_diffu6, on j = jci2 and on the ring column that is the left neighbour's
   auto diffu = [&](double ften, const double (&S)[SH2][SW2], const double* d6) {
-    if (c->idiffu == 3) return (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) ? ften + LD(d6, o3) : ften;
-    return diffu_x(g, c, j, i, ften, xkcs, [&](int dj, int di) { return S[a2 + di][b2 + dj]; });
+    if (O::idiffu(c) == 3) return (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) ? ften + LD(d6, o3) : ften;
+    return diffu_x<O>(g, c, j, i, ften, xkcs, [&](int dj, int di) { return S[a2 + di][b2 + dj]; });
   };
   // ================= temperature
   {
@@ -1132,7 +1141,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       const double x = su * (H1T(sPS, 1, 0) - H1T(sPS, -1, 0)) + sv * (H1T(sPS, 0, 1) - H1T(sPS, 0, -1));
       om = d_half * (q1 + q0) * ps + c->hsigma[k] * (ptn + x * dummy);
     }
-    if (f.omega) ST(f.omega, o3, om);
+    if (O::has(f.omega)) ST(f.omega, o3, om);
     // adiabatic (hydrostatic), cpmf = cpd*(1+0.8 qv)
     {
       const double qv = H1T(sXQV, 0, 0);
@@ -1143,27 +1152,27 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     if constexpr (BUD) { bud(b.t[2], td, t0); t0 = td; }
     // nudge3d (iboudy 1/5) or the sponge3d summand (iboudy 4, see k_momentum)
     double spt = d_zero;
-    if (rgc > 0 && c->iboudy == 4) {
+    if (rgc > 0 && O::iboudy(c) == 4) {
       const int ib = f.ibcr[o2 >> 3];
       spt = c->wgtx[ib] * d_zero + (d_one - c->wgtx[ib]) * LD(f.tbt, o3);
     } else if (rgc > 0) {
       const double xtb = s->xbctime + dt;
       double xf, xg;
-      nudge_coef(c, f.ibcr[o2 >> 3], k, xf, xg);
+      nudge_coef<O>(c, f.ibcr[o2 >> 3], k, xf, xg);
 #define FGT(dj, di) bdy_minus_state(LD(f.tb0, O3(dj, di)), LD(f.tbt, O3(dj, di)), LD(f.a2t, O3(dj, di)), xtb)
       td = relax(td, xf, xg, FGT(0, 0), FGT(-1, 0), FGT(1, 0), FGT(0, -1), FGT(0, 1));
 #undef FGT
     }
     if constexpr (BUD) {
-      if (bbdy) bud(b.t[3], c->iboudy == 4 ? spt : td, c->iboudy == 4 ? d_zero : t0);
+      if (bbdy) bud(b.t[3], O::iboudy(c) == 4 ? spt : td, O::iboudy(c) == 4 ? d_zero : t0);
       t0 = td;
     }
     td = diffu(td, sTB, f.d6t);
     if constexpr (BUD) bud(b.t[4], td, t0);
     // tten + tdyn + tphy (:285-288), then the SUBEX condensation term (:332-341, stubbed)
     // (pc_physic of the coupling seam, loaded here to keep registers free: absent = 0)
-    const double tt = ((spt + td) + (f.tphy ? LD(f.tphy, o3) : d_zero)) + d_zero;
-    if (f.tten) ST(f.tten, o3, tt);
+    const double tt = ((spt + td) + (O::has(f.tphy) ? LD(f.tphy, o3) : d_zero)) + d_zero;
+    if (O::has(f.tten)) ST(f.tten, o3, tt);
     const double ct = t2 + dt * tt;
     const double d = c->gnu1 * (ct + t2 - d_two * t1);
     ST(f.b2t, o3, t1 + d);
@@ -1171,7 +1180,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   // ================= qv
   // hadvqv, or the semi-Lagrangian start of qxdyn from k_sladv (isladvec = 1, :1361-1363)
-  double tq = c->isladvec ? LD(f.slqv, o3)
+  double tq = O::isladvec(c) ? LD(f.slqv, o3)
                           : d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXQV, 0, 0),
                                                H1T(sXQV, -1, 0), H1T(sXQV, 1, 0), H1T(sXQV, 0, -1),
                                                H1T(sXQV, 0, 1), 2);
@@ -1191,29 +1200,29 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   if constexpr (BUD) { bud(b.q[1], tq, tq0); tq0 = tq; }
   double spq = d_zero;
-  if (rgc > 0 && c->iboudy == 4) {
+  if (rgc > 0 && O::iboudy(c) == 4) {
     const int ib = f.ibcr[o2 >> 3];
     spq = c->wgtx[ib] * d_zero + (d_one - c->wgtx[ib]) * LD(f.qbt, o3);
   } else if (rgc > 0) {
     const double xtb = s->xbctime + dt;
     const double nfac = 1.0e3, rfac = d_one / nfac;
     double xf, xg;
-    nudge_coef(c, f.ibcr[o2 >> 3], k, xf, xg);
+    nudge_coef<O>(c, f.ibcr[o2 >> 3], k, xf, xg);
 #define FGQ(dj, di) bdy_minus_state(LD(f.qb0, O3(dj, di)), LD(f.qbt, O3(dj, di)), LD(f.a2qv, O3(dj, di)), xtb, nfac)
     const double f0 = FGQ(0, 0), f1 = FGQ(-1, 0), f2 = FGQ(1, 0), f3 = FGQ(0, -1), f4 = FGQ(0, 1);
 #undef FGQ
     tq = tq + rfac * (xf * f0 - xg * (f1 + f2 + f3 + f4 - d_four * f0));
   }
   if constexpr (BUD) {
-    if (bbdy) bud(b.q[3], c->iboudy == 4 ? spq : tq, c->iboudy == 4 ? d_zero : tq0);
+    if (bbdy) bud(b.q[3], O::iboudy(c) == 4 ? spq : tq, O::iboudy(c) == 4 ? d_zero : tq0);
     tq0 = tq;
   }
   tq = diffu(tq, sQVB, f.d6qv);
   if constexpr (BUD) bud(b.q[4], tq, tq0);
   // the qv sums and forecast (and with qfuse its RAW filter) before the qc chain, so the qv
   // operands are dead while it runs
-  tq = ((spq + tq) + (f.qvphy ? LD(f.qvphy, o3) : d_zero)) + d_zero;
-  if (f.qvten) ST(f.qvten, o3, tq);
+  tq = ((spq + tq) + (O::has(f.qvphy) ? LD(f.qvphy, o3) : d_zero)) + d_zero;
+  if (O::has(f.qvten)) ST(f.qvten, o3, tq);
   const bool qown = f.qfuse && in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
   {
     const double fcqv = qv2 + dt * tq;
@@ -1222,11 +1231,11 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   // ================= qc
   // hadvqx, or the semi-Lagrangian start of qxdyn (:1378-1380)
-  double tc = c->isladvec ? LD(f.slqc, o3)
+  double tc = O::isladvec(c) ? LD(f.slqc, o3)
                           : d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXQC, 0, 0),
                                                H1T(sXQC, -1, 0), H1T(sXQC, 1, 0), H1T(sXQC, 0, -1),
                                                H1T(sXQC, 0, 1), 0);
-  if (f.kpbl) {
+  if (O::has(f.kpbl)) {
     // vadv4d ind = 3 (iuwvadv = 1): no positivity threshold, the PBL-top rule at kpbl
     const int kpb = (int)LD(f.kpbl, o2);
     auto fk = [&](int kk) { return LD(f.a1qc, o2 + (uint32_t)(kk - 1) * L8); };
@@ -1251,8 +1260,8 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   tc = diffu(tc, sQCB, f.d6qc);
 #undef DT
 #undef H1T
-  tc = ((d_zero + tc) + (f.qcphy ? LD(f.qcphy, o3) : d_zero)) + d_zero;
-  if (f.qcten) ST(f.qcten, o3, tc);
+  tc = ((d_zero + tc) + (O::has(f.qcphy) ? LD(f.qcphy, o3) : d_zero)) + d_zero;
+  if (O::has(f.qcten)) ST(f.qcten, o3, tc);
   {
     const double fcqc = qc2 + dt * tc;
     ST(f.cqc, o3, fcqc);
@@ -1260,15 +1269,21 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   PT_PRINT(3);
 }
+// the default-set instance (optset.hpp), the generic one and the budget one (generic)
 __global__ __launch_bounds__(SBT, SC_LB) void k_scalars(Geom g, const Consts* __restrict__ c,
                                                     const StepState* __restrict__ s, Fields f) {
   __shared__ ScaLDS L;
-  scalars_block<false>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
+  scalars_block<false, OptDefault>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_gen(Geom g, const Consts* __restrict__ c,
+                                                        const StepState* __restrict__ s, Fields f) {
+  __shared__ ScaLDS L;
+  scalars_block<false, OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
 }
 __global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts* __restrict__ c,
                                                         const StepState* __restrict__ s, Fields f, Budget b) {
   __shared__ ScaLDS L;
-  scalars_block<true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b);
+  scalars_block<true, OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b);
 }
 
 // k_momentum and k_scalars in one launch: blockIdx.z < kz a scalars block of level z + 1, else
@@ -1278,9 +1293,12 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts
 // longer scalars blocks dispatched first the momentum blocks fill it (C3, alternating on one
 // box: 203.5-212.1 us/step against 211.2-222.9 with the momentum blocks first, 222.3-224.1
 // interleaved by level, 218.8-223.6 as two launches).
-__global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __restrict__ c,
-                                                   const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                   int mnx, int mny, int snx, int sny, int xcd) {
+// Three instances of the one body: the default set (k_update, optset.hpp), the generic one
+// (k_update_gen) and the budget one (k_update_bud, generic).
+template <bool BUD, class O>
+__device__ __forceinline__ void update_block(const Geom& g, const Consts* __restrict__ c,
+                                             const StepState* __restrict__ s, const Fields& fm, const Fields& fs,
+                                             int mnx, int mny, int snx, int sny, int xcd, const Budget& b) {
   __shared__ union { MomLDS m; ScaLDS s; } L;
   const int kz = c->kz, bz = (int)blockIdx.z;
   int bx = (int)blockIdx.x, by = (int)blockIdx.y;
@@ -1288,25 +1306,25 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __r
   const bool mom = bz >= kz;
   const int lz = mom ? bz - kz : bz;
   if (mom) {
-    if (bx < mnx && by < mny) momentum_block(g, c, s, fm, L.m, bx, by, lz);
+    if (bx < mnx && by < mny) momentum_block<O>(g, c, s, fm, L.m, bx, by, lz);
   } else if (bx < snx && by < sny) {
-    scalars_block<false>(g, c, s, fs, L.s, bx, by, lz, Budget{});
+    scalars_block<BUD, O>(g, c, s, fs, L.s, bx, by, lz, b);
   }
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __restrict__ c,
+                                                   const StepState* __restrict__ s, Fields fm, Fields fs,
+                                                   int mnx, int mny, int snx, int sny, int xcd) {
+  update_block<false, OptDefault>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{});
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_update_gen(Geom g, const Consts* __restrict__ c,
+                                                       const StepState* __restrict__ s, Fields fm, Fields fs,
+                                                       int mnx, int mny, int snx, int sny, int xcd) {
+  update_block<false, OptGeneric>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{});
 }
 __global__ __launch_bounds__(SBT, SC_LB) void k_update_bud(Geom g, const Consts* __restrict__ c,
                                                        const StepState* __restrict__ s, Fields fm, Fields fs,
                                                        int mnx, int mny, int snx, int sny, int xcd, Budget b) {
-  __shared__ union { MomLDS m; ScaLDS s; } L;
-  const int kz = c->kz, bz = (int)blockIdx.z;
-  int bx = (int)blockIdx.x, by = (int)blockIdx.y;
-  if (xcd) xcd_tile2d(bx, by);
-  const bool mom = bz >= kz;
-  const int lz = mom ? bz - kz : bz;
-  if (mom) {
-    if (bx < mnx && by < mny) momentum_block(g, c, s, fm, L.m, bx, by, lz);
-  } else if (bx < snx && by < sny) {
-    scalars_block<true>(g, c, s, fs, L.s, bx, by, lz, b);
-  }
+  update_block<true, OptGeneric>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b);
 }
 
 // ---------------------------------------------------------------------------------------

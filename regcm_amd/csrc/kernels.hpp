@@ -194,12 +194,19 @@ __global__ void k_surface_pressures(Geom g, Fields f);
 template <bool QX>
 __global__ void k_columns(Geom g, const Consts* __restrict__ c, StepState* s, Fields f, int nxb, int ncol);
 __global__ void k_sladv(Geom g, const Consts* __restrict__ c, StepState* s, Fields f, QxArgs q);
+// k_momentum, k_scalars, k_update: the instance compiled for the default option set
+// (optset.hpp); *_gen: the generic instance of the same body, any option.  The engine reports
+// either under the plain name.
 __global__ void k_momentum(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
+__global__ void k_momentum_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
 __global__ void k_diffu6(Geom g, const Consts* __restrict__ c, Fields f, QxArgs q);
 __global__ void k_scalars(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
+__global__ void k_scalars_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
 __global__ void k_update(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm, Fields fs,
                          int mnx, int mny, int snx, int sny, int xcd);
-// the budget instances of the two (the scalars blocks also accumulate the tendency budget)
+__global__ void k_update_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
+                             Fields fs, int mnx, int mny, int snx, int sny, int xcd);
+// the budget instances of the two (the scalars blocks also accumulate the tendency budget; generic)
 __global__ void k_scalars_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
                               Budget b);
 __global__ void k_update_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,

@@ -4,8 +4,33 @@
 // Every body keeps the reference's floating-point operation order (-ffp-contract=off).
 #pragma once
 #include "devcommon.hpp"
+#include "optset.hpp"
 
 namespace rcm {
+
+// How a kernel reads a model option: every read of iboudy, idiffu, ipgf, isladvec and every
+// test of an optional pointer of Fields (the exports tten .. xkcs, the seam's physics
+// tendencies, kpbl) in the hydrostatic tendency kernels goes through a policy.  OptGeneric
+// reads Consts and tests the pointer (any option, the code as it always was); OptDefault
+// returns the constants of the default set and ignores its argument, so the compiler drops the
+// code, pointers and registers of the alternatives.  The host picks the instance per launch
+// (optset.hpp).  The non-hydrostatic kernels and the hydrometeors use OptGeneric.
+struct OptGeneric {
+  static __device__ __forceinline__ int iboudy(const Consts* c) { return c->iboudy; }
+  static __device__ __forceinline__ int idiffu(const Consts* c) { return c->idiffu; }
+  static __device__ __forceinline__ int ipgf(const Consts* c) { return c->ipgf; }
+  static __device__ __forceinline__ int isladvec(const Consts* c) { return c->isladvec; }
+  template <class T>
+  static __device__ __forceinline__ bool has(const T* p) { return p != nullptr; }
+};
+struct OptDefault {
+  static __device__ __forceinline__ int iboudy(const Consts*) { return OPT_IBOUDY; }
+  static __device__ __forceinline__ int idiffu(const Consts*) { return OPT_IDIFFU; }
+  static __device__ __forceinline__ int ipgf(const Consts*) { return OPT_IPGF; }
+  static __device__ __forceinline__ int isladvec(const Consts*) { return OPT_ISLADVEC; }
+  template <class T>
+  static __device__ __forceinline__ bool has(const T*) { return false; }
+};
 
 // boundary relaxation contribution (nudge*, Main/mod_bdycod.F90:4262-4263): f0 the boundary
 // data minus the state at the point, f1..f4 at its west, east, south and north neighbours
@@ -91,11 +116,11 @@ __device__ __forceinline__ void raw_filter(const Consts* c, int n, double v, dou
 // east, south, north).  f(dj, di) reads the decoupled field at (j + dj, i + di), xk is the
 // scaled coefficient.  The index tests are the global ones, so they hold on ghost-ring points
 // too (equal to the tile ranges on owned points, engine.hpp).  The idiffu = 3 column term
-// stays with the callers.
-template <class F>
+// stays with the callers.  O: the option policy (idiffu).
+template <class O = OptGeneric, class F>
 __device__ __forceinline__ double diffu_x(const Geom& g, const Consts* __restrict__ c, int j, int i, double ften,
                                           double xk, F f) {
-  if (c->idiffu == 2)
+  if (O::idiffu(c) == 2)
     return ften + d_one * xk *
                       (o4_c1 * (f(1, 0) + f(-1, 0) + f(0, 1) + f(0, -1)) +
                        o4_c2 * (f(1, 1) + f(-1, -1) + f(-1, 1) + f(1, -1)) + o4_c3 * f(0, 0));
