@@ -420,6 +420,43 @@ int rcmdyn_reset_budget(rcmdyn_t* h);
 int rcmdyn_set_massck(rcmdyn_t* h, int32_t on, int32_t cap);
 int rcmdyn_get_massck(rcmdyn_t* h, double* out, int32_t cap, int32_t* count, int64_t* lost);
 
+/* SUBEX large-scale condensation inside tend (the reference's `call condtq` for ipptls = 1,
+ * Main/mod_tendency.F90:336-349, Main/mod_micro_interface.F90:382-493, the idynamic /= 3 branch):
+ * off by default.  When on, every tend applies, after it summed the tendencies of t, qv, qc (and
+ * NH pp) and before the NH Rayleigh damping and the forecasts, the one-step condensation /
+ * evaporation adjustment with partial cloud cover at every interior cross point.  It reads the
+ * step's own totals, sfs%psc, atms%qsb3d of the step's start (formed at the point as mkslice
+ * does) and the host's rh0adj, and adds the coupled increments -psc*tmp2 (qv), +psc*tmp2 (qc),
+ * +psc*tmp2*wlh*rcpd (t) where |tmp2| > dlowval.  TTEN / QVTEN / QCTEN then include the term, as
+ * aten(pc_total) does after :345-349.  The operations and their order are the Fortran text's.
+ *
+ * rcmdyn_set_condtq: conf is subexparam's condensation efficiency (Main/mod_params.F90:326,
+ * default 1.0).  Refused for ipptls != 1 and for conf outside (0, 1], the switch staying as it
+ * was.  Waits for the device like rcmdyn_set_budget.
+ * rcmdyn_put_rh0adj: the adjusted relative-humidity threshold the host's cldfrac produces inside
+ * physical_parametrizations (Main/mod_micro_interface.F90:353-356), cross points, kz levels,
+ * layout and bounds as in rcmdyn_put.  A value outside [0, 0.99999] (the reference's clamp; 1 -
+ * rh0adj is a divisor) refuses the whole put.  The buffer persists like the *PHY ones; on the
+ * split path the host puts it between rcmdyn_tend_pre_physics and rcmdyn_tend_post_physics.  A
+ * decomposed job's host passes the values of the tile's ghost ring too, as for the *PHY fields;
+ * the frame columns of a band (rows in CRM mode) past either end of the period are filled from
+ * the wrapped index, as rcmdyn_put does.
+ * A tend with condtq on fails until, since the switch-on, one put has covered every level of
+ * every interior cross point of the engine's tiles and of their ghost rings (for one tile: jci1
+ * .. jci2, ici1 .. ici2, 1 .. kz); puts of smaller boxes update the buffer before and after it.
+ * rcmdyn_get_condtq: the held rh0adj, or the last tend's increments of t, qv, qc (coupled, as
+ * aten(.., pc_physic) holds them after condtq; the host feeds tdiag%lsc / qdiag%lsc from them,
+ * :351-354); the increments are written to dst on the interior cross points only.  Fails while
+ * the switch is off. */
+enum rcmdyn_condtq_term {
+  RCMDYN_CONDTQ_RH0ADJ = 0, RCMDYN_CONDTQ_T, RCMDYN_CONDTQ_QV, RCMDYN_CONDTQ_QC, RCMDYN_NCONDTQ
+};
+int rcmdyn_set_condtq(rcmdyn_t* h, int32_t on, double conf);
+int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

@@ -393,6 +393,16 @@ struct rcmdyn_engine {
     b.rw = bud_rw;
     return b;
   }
+  // SUBEX condensation inside tend (rcmdyn_set_condtq; condtq.hpp): the switch, subexparam's
+  // conf, and whether one put of the host covered rh0adj wherever condtq runs since the switch-on
+  bool condtq = false, rh0_put = false;
+  double ct_conf = 1.0;
+  Condtq condtq_args(const Tile& t) const { return Condtq{t.rh0adj, t.cti[0], t.cti[1], t.cti[2], ct_conf}; }
+  void condtq_ready(const char* who) const {
+    if (condtq && !rh0_put)
+      throw std::runtime_error(std::string(who) + ": condtq is on and no rh0adj was put since that covers the tiles' interior "
+                               "cross points and their rings on every level (rcmdyn_put_rh0adj)");
+  }
   // mass check of tend (rcmdyn_set_massck; massck.hip): the switch, the ring's capacity, the
   // tiles' slots with k_massck_final's table of them, the device log (its counter, then the
   // records) and the counter's value at the host's last read
@@ -1190,6 +1200,30 @@ struct rcmdyn_engine {
       "no slice fields yet (rcmdyn_tend_pre_physics)", "tendency diagnostics are off (rcmdyn_set_diagnostics)"};
   static_assert(fieldtab::DIAG == 5 && sizeof(WAITS_FOR) / sizeof(WAITS_FOR[0]) == 6, "one text per fieldtab::Lazy");
 
+  // The host box src (j fastest, then i, then k) into a tile's buffer d of nk levels: every frame
+  // point of the tile whose global index lies in the box, the ghost ring included, and the frame
+  // points past either end of a period from the wrapped index.  (rcmdyn_put, rcmdyn_put_rh0adj)
+  void scatter_box(const Tile& t, double* d, int nk, const double* src, int j1, int j2, int i1, int i2, int k1,
+                   int k2) {
+    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const Geom& g = t.g;
+    std::vector<double> h((size_t)nk * g.plane);
+    HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
+    for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
+      for (int i = g.i0; i <= g.i0 + g.ni - 1; i++) {
+        // CRM: the frame rows past either end of the period take the wrapped row
+        const int iw = !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i));
+        if (iw < i1 || iw > i2) continue;
+        for (int j = g.j0; j <= g.j0 + g.nj - 1; j++) {
+          // a band's frame columns past either end of the period take the wrapped column
+          const int jw = !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j));
+          if (jw < j1 || jw > j2) continue;
+          h[(size_t)(k - 1) * g.plane + g.ix(j, i)] = src[((size_t)(k - k1) * ni + (iw - i1)) * nj + (jw - j1)];
+        }
+      }
+    HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  }
+
   void put(int f, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
     settle();
     const fieldtab::Row* r = fieldtab::row(f);
@@ -1205,27 +1239,11 @@ struct rcmdyn_engine {
     }
     if (!have(r->lazy)) enable(r->lazy);
     HIPCHK(hipStreamSynchronize(stream));
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
     const int nk = field_levels(f);
     for (auto& t : tiles) {
       double* d = field_ptr(t, f);
       if (!d) throw std::runtime_error("rcmdyn_put: unknown field");
-      const Geom& g = t.g;
-      std::vector<double> h((size_t)nk * g.plane);
-      HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-        for (int i = g.i0; i <= g.i0 + g.ni - 1; i++) {
-          // CRM: the frame rows past either end of the period take the wrapped row
-          const int iw = !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i));
-          if (iw < i1 || iw > i2) continue;
-          for (int j = g.j0; j <= g.j0 + g.nj - 1; j++) {
-            // a band's frame columns past either end of the period take the wrapped column
-            const int jw = !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j));
-            if (jw < j1 || jw > j2) continue;
-            h[(size_t)(k - 1) * g.plane + g.ix(j, i)] = src[((size_t)(k - k1) * ni + (iw - i1)) * nj + (jw - j1)];
-          }
-        }
-      HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+      scatter_box(t, d, nk, src, j1, j2, i1, i2, k1, k2);
     }
     ghosts_stale = true;
     switch (r->after) {
@@ -1404,6 +1422,84 @@ struct rcmdyn_engine {
     HIPCHK(hipStreamSynchronize(stream));
     for (auto& t : tiles)
       for (double* d : t.bud) HIPCHK(hipMemset(d, 0, t.g.plane * (size_t)cfg.kz * sizeof(double)));
+  }
+
+  // SUBEX condensation (condtq, Main/mod_micro_interface.F90:382-493) inside tend: the switch,
+  // the host's rh0adj and the read of the last tend's increments.  rh0adj and the three
+  // increment arrays are allocated at the first switch-on; the switch selects other kernel
+  // instances and conf is a kernel argument, so the captured graphs are dropped when either
+  // changes.  A put of rh0adj writes the buffer the graphs already point to.
+  void set_condtq(int on, double conf) {
+    if (on) {
+      if (cfg.ipptls != 1)
+        throw std::runtime_error("rcmdyn_set_condtq: condtq belongs to ipptls = 1 (SUBEX); the reference does not call it otherwise");
+      if (!(conf > 0.0) || !(conf <= 1.0))
+        throw std::runtime_error("rcmdyn_set_condtq: conf must be in (0, 1]");
+    }
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    const bool b = on != 0;
+    if (b == condtq && (!b || conf == ct_conf)) return;
+    if (b && !tiles.empty() && !tiles[0].rh0adj)
+      for (auto& t : tiles) {
+        t.rh0adj = dalloc(t, t.g.plane * (size_t)cfg.kz);
+        for (double*& d : t.cti) d = dalloc(t, t.g.plane * (size_t)cfg.kz);
+      }
+    invalidate_graphs();
+    if (b && !condtq) rh0_put = false;
+    condtq = b;
+    if (b) ct_conf = conf;
+  }
+  void put_rh0adj(const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+    if (!condtq) throw std::runtime_error("rcmdyn_put_rh0adj: condtq is off (rcmdyn_set_condtq)");
+    const size_t n = (size_t)std::max(0, j2 - j1 + 1) * std::max(0, i2 - i1 + 1) * std::max(0, k2 - k1 + 1);
+    for (size_t q = 0; q < n; q++)
+      if (!(src[q] >= 0.0) || !(src[q] <= 0.99999))
+        throw std::runtime_error("rcmdyn_put_rh0adj: rh0adj must lie in [0, 0.99999]");
+    settle();                                        // a pending lazy tend reads the previous values
+    HIPCHK(hipStreamSynchronize(stream));
+    // as rcmdyn_put scatters a *PHY field: the ghost ring and the wrapped columns of a band (rows
+    // in CRM mode) included, since the hydrostatic step computes the forecasts of the ring as
+    // their owners do
+    for (auto& t : tiles) scatter_box(t, t.rh0adj, cfg.kz, src, j1, j2, i1, i2, k1, k2);
+    // tend waits for a put that covers every point condtq runs at, on every level: the interior
+    // cross points (gci) of each tile and of its ring, the wrapped ones by their wrapped index.
+    // None then reads the zeros of the allocation or the values of an earlier switch-on.  Smaller
+    // boxes update the buffer before and after that put.
+    bool all = k1 <= 1 && k2 >= cfg.kz;
+    for (const auto& t : tiles) {
+      const Geom& g = t.g;
+      for (int i = g.icx1(); all && i <= g.icx2(); i++) {
+        const int iw = !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i));
+        for (int j = g.jcx1(); all && j <= g.jcx2(); j++) {
+          const int jw = !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j));
+          if (g.gci(j, i) && (jw < j1 || jw > j2 || iw < i1 || iw > i2)) all = false;
+        }
+      }
+    }
+    if (all) rh0_put = true;
+  }
+  void get_condtq(int term, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    settle();
+    if (!condtq) throw std::runtime_error("rcmdyn_get_condtq: condtq is off (rcmdyn_set_condtq)");
+    if (term < 0 || term >= RCMDYN_NCONDTQ) throw std::runtime_error("rcmdyn_get_condtq: unknown term");
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const int nk = cfg.kz;
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      std::vector<double> h((size_t)nk * g.plane);
+      HIPCHK(hipMemcpy(h.data(), term == RCMDYN_CONDTQ_RH0ADJ ? t.rh0adj : t.cti[term - RCMDYN_CONDTQ_T], h.size() * 8,
+                       hipMemcpyDeviceToHost));
+      // the increments live on the tile's interior cross points (the ring's are its neighbours')
+      const bool inc = term != RCMDYN_CONDTQ_RH0ADJ;
+      const int ja = inc ? g.jci1 : g.jde1, jb = inc ? g.jci2 : g.jde2, ia = inc ? g.ici1 : g.ide1, ib = inc ? g.ici2 : g.ide2;
+      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
+        for (int i = std::max(i1, ia); i <= std::min(i2, ib); i++)
+          for (int j = std::max(j1, ja); j <= std::min(j2, jb); j++)
+            dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+    }
   }
 
   // Mass check of tend (Main/mod_massck.F90:190-306): the switch, the launches tend issues after
@@ -1910,7 +2006,7 @@ struct rcmdyn_engine {
     OptQuery q{};
     q.iboudy = cfg.iboudy; q.idiffu = cfg.idiffu; q.ipgf = cfg.ipgf; q.isladvec = cfg.isladvec;
     q.ibltyp = cfg.ibltyp; q.iuwvadv = cfg.iuwvadv; q.nqx_extra = hc.nsp;
-    q.budget = budget; q.no_optset = sw.no_optset;
+    q.budget = budget; q.no_optset = sw.no_optset; q.condtq = condtq;
     q.tten = f.tten; q.uten = f.uten; q.vten = f.vten; q.qvten = f.qvten; q.qcten = f.qcten;
     q.omega = f.omega; q.xkcs = f.xkcs;
     q.tphy = f.tphy; q.qvphy = f.qvphy; q.qcphy = f.qcphy; q.uphy = f.uphy; q.vphy = f.vphy;
@@ -2208,6 +2304,12 @@ struct rcmdyn_engine {
       // the chains of qi, qr, qs after it on the same stream
       KLAUNCH(k_nh_qx_tend, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0, stream, g, dc, ds, f,
               qx_args(t));
+    } else if (condtq && budget) {
+      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+              (int)diag, istep, budget_args(t), condtq_args(t));
+    } else if (condtq) {
+      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
+              (int)diag, istep, condtq_args(t));
     } else if (budget) {
       KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
               (int)diag, istep, budget_args(t));
@@ -2371,7 +2473,13 @@ struct rcmdyn_engine {
       const int xcd = (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW);
       const dim3 grid(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz);
       const Fields fm = fields(t, pm), fs = fields(t, ps);
-      if (budget)
+      if (condtq && budget)
+        KLAUNCH_AS("k_update_bud", k_update_bud_ct, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny,
+                   xcd, budget_args(t), condtq_args(t));
+      else if (condtq)
+        KLAUNCH_AS("k_update", k_update_ct, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd,
+                   condtq_args(t));
+      else if (budget)
         KLAUNCH(k_update_bud, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd, budget_args(t));
       else if (opt_instance(fm) == OPT_DEFAULT && opt_instance(fs) == OPT_DEFAULT)
         KLAUNCH(k_update, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd);
@@ -2386,7 +2494,13 @@ struct rcmdyn_engine {
     else if (pm >= 0)
       KLAUNCH_AS("k_momentum", k_momentum_gen, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz),
                  dim3(MBT), 0, stream, g, dc, ds, fields(t, pm));
-    if (ps >= 0 && budget)
+    if (ps >= 0 && condtq && budget)
+      KLAUNCH_AS("k_scalars_bud", k_scalars_bud_ct, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
+                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t), condtq_args(t));
+    else if (ps >= 0 && condtq)
+      KLAUNCH_AS("k_scalars", k_scalars_ct, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
+                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), condtq_args(t));
+    else if (ps >= 0 && budget)
       KLAUNCH(k_scalars_bud, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
               dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t));
     else if (ps >= 0 && def)
@@ -2685,6 +2799,7 @@ struct rcmdyn_engine {
   void replayed_bdyval() { hs.xbctime = hs.xbctime + cfg.dtsec; }
 
   void step(int n) {
+    condtq_ready("rcmdyn_step");
     prepare();
     settle();
     hipEvent_t e0, e1;
@@ -2722,6 +2837,7 @@ struct rcmdyn_engine {
   // the drop-in call sequence of RCM_run (Main/mod_regcm_interface.F90:189,208): each call
   // replays its own captured graph and returns without synchronising the stream
   void tend_call() {
+    condtq_ready("rcmdyn_tend");
     begin_tend();
     const int par = gpar();
     const Corr corr = drop_in_corr();
@@ -2751,6 +2867,7 @@ struct rcmdyn_engine {
   // the host's physics; the corrections go with the next rcmdyn_bdyval as after rcmdyn_tend
   void tend_pre_physics() { begin_tend(); tend(Corr::Launch, TEND_PRE, true); }
   void tend_post_physics() {
+    condtq_ready("rcmdyn_tend_post_physics");
     begin_tend();
     const Corr corr = drop_in_corr();
     tend(corr, TEND_POST);
@@ -2835,6 +2952,7 @@ struct rcmdyn_engine {
   }
 
   void kernel_times(int nsteps, int cap, char* names, int32_t* launches, double* avg, int32_t* count) {
+    condtq_ready("rcmdyn_kernel_times");
     prepare();
     settle();
     KernelProf kp;
@@ -3180,6 +3298,20 @@ int rcmdyn_set_massck(rcmdyn_t* h, int32_t on, int32_t cap) {
 
 int rcmdyn_get_massck(rcmdyn_t* h, double* out, int32_t cap, int32_t* count, int64_t* lost) {
   return guard(h, [&] { h->get_massck(out, cap, count, lost); });
+}
+
+int rcmdyn_set_condtq(rcmdyn_t* h, int32_t on, double conf) {
+  return guard(h, [&] { h->set_condtq(on, conf); });
+}
+
+int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
+                      int32_t k2) {
+  return guard(h, [&] { h->put_rh0adj(src, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                      int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_condtq(term, dst, j1, j2, i1, i2, k1, k2); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

@@ -218,6 +218,9 @@ struct Tile {
   // tendency budget of t and qv (rcmdyn_set_budget; allocated on its first use): tdiag then
   // qdiag %adh, adv, adi, bdy, dif, in rcmdyn_budget_term order
   double *bud[RCMDYN_NBUDGET] = {};
+  // SUBEX condensation (rcmdyn_set_condtq; allocated at its first switch-on): the host's rh0adj
+  // and the last tend's coupled increments of t, qv, qc
+  double *rh0adj = nullptr, *cti[3] = {};
   // boundary slices (Main/mod_bdycod.F90:58-61): [k][frame index]
   double *sl[16];
   // wide frame of the fused split step on a decomposed domain (2-D inputs, ghost depth SPH)

@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <vector>
 #include "fastmath.hpp"
+#include "condtq.hpp"
 #include "devcommon.hpp"
 #include "qxcommon.hpp"
 
@@ -957,10 +958,15 @@ struct ScaLDS {
 // accumulator (ten2diag, :2123-2175) at the tile's own interior points.  Hydrostatic qv has no
 // adiabatic term (its difference is 0 exactly: qdiag%adi is left alone); iboudy = 4 adds the
 // sponge value itself (pc_total, no ten0); iboudy 0, 2, 3 never write the bdy term.
-template <bool BUD, class O>
+// CT: the condtq instance (rcmdyn_set_condtq).  The three totals of the point meet in this
+// thread, so it holds tt and tq back until tc is known, adds condtq's increments
+// (Main/mod_tendency.F90:336-349), and only then stores the tendency exports and forms the
+// forecasts (:368-380) with their filters.
+template <bool BUD, class O, bool CT = false>
 __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __restrict__ c,
                                               const StepState* __restrict__ s, const Fields& f, ScaLDS& L,
-                                              int bx, int by, int bz, const Budget& b) {
+                                              int bx, int by, int bz, const Budget& b,
+                                              const Condtq& ctq = Condtq{}) {
   auto& sUMC = L.sUMC; auto& sVMC = L.sVMC; auto& sUD = L.sUD; auto& sVD = L.sVD; auto& sUB = L.sUB;
   auto& sVB = L.sVB; auto& sPS = L.sPS; auto& sXT = L.sXT; auto& sXQV = L.sXQV; auto& sXQC = L.sXQC;
   auto& sTB = L.sTB; auto& sQVB = L.sQVB; auto& sQCB = L.sQCB;
@@ -1112,6 +1118,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     return diffu_x<O>(g, c, j, i, ften, xkcs, [&](int dj, int di) { return S[a2 + di][b2 + dj]; });
   };
   // ================= temperature
+  double tth = d_zero;                  // CT: the total of t, held until the qc total is known
   {
     double td = d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, H1T(sXT, 0, 0), H1T(sXT, -1, 0),
                                    H1T(sXT, 1, 0), H1T(sXT, 0, -1), H1T(sXT, 0, 1), 1);
@@ -1169,14 +1176,21 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     }
     td = diffu(td, sTB, f.d6t);
     if constexpr (BUD) bud(b.t[4], td, t0);
-    // tten + tdyn + tphy (:285-288), then the SUBEX condensation term (:332-341, stubbed)
+    // tten + tdyn + tphy (:285-288); + d_zero where the SUBEX condensation term enters (:345-349:
+    // zero with condtq off, the CT instance adds its increment after the qc chain)
     // (pc_physic of the coupling seam, loaded here to keep registers free: absent = 0)
     const double tt = ((spt + td) + (O::has(f.tphy) ? LD(f.tphy, o3) : d_zero)) + d_zero;
-    if (O::has(f.tten)) ST(f.tten, o3, tt);
-    const double ct = t2 + dt * tt;
-    const double d = c->gnu1 * (ct + t2 - d_two * t1);
-    ST(f.b2t, o3, t1 + d);
-    ST(f.b1t, o3, ct);
+    if constexpr (CT) {
+      tth = tt;
+    } else {
+      // (the CT instance restates this export, forecast and filter, and those of qv and qc
+      // below, after its increments at the end of the qc chain: change both copies together)
+      if (O::has(f.tten)) ST(f.tten, o3, tt);
+      const double ct = t2 + dt * tt;
+      const double d = c->gnu1 * (ct + t2 - d_two * t1);
+      ST(f.b2t, o3, t1 + d);
+      ST(f.b1t, o3, ct);
+    }
   }
   // ================= qv
   // hadvqv, or the semi-Lagrangian start of qxdyn from k_sladv (isladvec = 1, :1361-1363)
@@ -1222,9 +1236,11 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   // the qv sums and forecast (and with qfuse its RAW filter) before the qc chain, so the qv
   // operands are dead while it runs
   tq = ((spq + tq) + (O::has(f.qvphy) ? LD(f.qvphy, o3) : d_zero)) + d_zero;
-  if (O::has(f.qvten)) ST(f.qvten, o3, tq);
+  if constexpr (!CT) {
+    if (O::has(f.qvten)) ST(f.qvten, o3, tq);
+  }
   const bool qown = f.qfuse && in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
-  {
+  if constexpr (!CT) {
     const double fcqv = qv2 + dt * tq;
     ST(f.cqv, o3, fcqv);
     if (qown) scalars_qraw(c, f, 0, fcqv, o2, o3, ps, pb);
@@ -1261,8 +1277,37 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
 #undef DT
 #undef H1T
   tc = ((d_zero + tc) + (O::has(f.qcphy) ? LD(f.qcphy, o3) : d_zero)) + d_zero;
-  if (O::has(f.qcten)) ST(f.qcten, o3, tc);
-  {
+  if constexpr (CT) {
+    // condtq (Main/mod_micro_interface.F90:382-493) on the three totals: pres from the new p*
+    // (:413), qs = atms%qsb3d of the step's start as mkslice forms it (k_slice)
+    const double psc = LD(f.psc, o2), ptop = c->ptop;
+    const double pres = (c->hsigma[k] * psc + ptop) * d_1000;
+    const double qs = pfwsat(t2 * LD(f.rpsb, o2), (c->hsigma[k] * pb + ptop) * d_1000, cq::EP2);
+    double tmp2, wwlh, it, iqv, iqc;
+    condtq_point(t2, qv2, qc2, tth, tq, tc, psc, pres, qs, LD(ctq.rh0adj, o3), dt, ctq.conf, tmp2, wwlh);
+    condtq_increments(psc, tmp2, wwlh, it, iqv, iqc);
+    ST(ctq.it, o3, it); ST(ctq.iqv, o3, iqv); ST(ctq.iqc, o3, iqc);
+    // the totals with the condensation term (:345-349), then the forecasts and their filters
+    // (the `else` copies of t, qv and qc above and below, restated: change them together)
+    const double tt = tth + it;
+    tq = tq + iqv;
+    tc = tc + iqc;
+    if (O::has(f.tten)) ST(f.tten, o3, tt);
+    if (O::has(f.qvten)) ST(f.qvten, o3, tq);
+    if (O::has(f.qcten)) ST(f.qcten, o3, tc);
+    const double ct = t2 + dt * tt;
+    const double d = c->gnu1 * (ct + t2 - d_two * t1);
+    ST(f.b2t, o3, t1 + d);
+    ST(f.b1t, o3, ct);
+    const double fcqv = qv2 + dt * tq, fcqc = qc2 + dt * tc;
+    ST(f.cqv, o3, fcqv);
+    ST(f.cqc, o3, fcqc);
+    if (qown) {
+      scalars_qraw(c, f, 0, fcqv, o2, o3, ps, pb);
+      scalars_qraw(c, f, 1, fcqc, o2, o3, ps, pb);
+    }
+  } else {
+    if (O::has(f.qcten)) ST(f.qcten, o3, tc);
     const double fcqc = qc2 + dt * tc;
     ST(f.cqc, o3, fcqc);
     if (qown) scalars_qraw(c, f, 1, fcqc, o2, o3, ps, pb);
@@ -1285,6 +1330,18 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts
   __shared__ ScaLDS L;
   scalars_block<true, OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b);
 }
+// the condtq instances (generic), without and with the budget
+__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_ct(Geom g, const Consts* __restrict__ c,
+                                                       const StepState* __restrict__ s, Fields f, Condtq q) {
+  __shared__ ScaLDS L;
+  scalars_block<false, OptGeneric, true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{}, q);
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud_ct(Geom g, const Consts* __restrict__ c,
+                                                           const StepState* __restrict__ s, Fields f, Budget b,
+                                                           Condtq q) {
+  __shared__ ScaLDS L;
+  scalars_block<true, OptGeneric, true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b, q);
+}
 
 // k_momentum and k_scalars in one launch: blockIdx.z < kz a scalars block of level z + 1, else
 // a momentum block of level z - kz + 1 (x/y: the larger of the two grids; a block past its own
@@ -1295,10 +1352,11 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts
 // interleaved by level, 218.8-223.6 as two launches).
 // Three instances of the one body: the default set (k_update, optset.hpp), the generic one
 // (k_update_gen) and the budget one (k_update_bud, generic).
-template <bool BUD, class O>
+template <bool BUD, class O, bool CT = false>
 __device__ __forceinline__ void update_block(const Geom& g, const Consts* __restrict__ c,
                                              const StepState* __restrict__ s, const Fields& fm, const Fields& fs,
-                                             int mnx, int mny, int snx, int sny, int xcd, const Budget& b) {
+                                             int mnx, int mny, int snx, int sny, int xcd, const Budget& b,
+                                             const Condtq& ctq = Condtq{}) {
   __shared__ union { MomLDS m; ScaLDS s; } L;
   const int kz = c->kz, bz = (int)blockIdx.z;
   int bx = (int)blockIdx.x, by = (int)blockIdx.y;
@@ -1308,7 +1366,8 @@ __device__ __forceinline__ void update_block(const Geom& g, const Consts* __rest
   if (mom) {
     if (bx < mnx && by < mny) momentum_block<O>(g, c, s, fm, L.m, bx, by, lz);
   } else if (bx < snx && by < sny) {
-    scalars_block<BUD, O>(g, c, s, fs, L.s, bx, by, lz, b);
+    if constexpr (CT) scalars_block<BUD, O, true>(g, c, s, fs, L.s, bx, by, lz, b, ctq);
+    else scalars_block<BUD, O>(g, c, s, fs, L.s, bx, by, lz, b);
   }
 }
 __global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __restrict__ c,
@@ -1325,6 +1384,17 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_update_bud(Geom g, const Consts*
                                                        const StepState* __restrict__ s, Fields fm, Fields fs,
                                                        int mnx, int mny, int snx, int sny, int xcd, Budget b) {
   update_block<true, OptGeneric>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b);
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_update_ct(Geom g, const Consts* __restrict__ c,
+                                                      const StepState* __restrict__ s, Fields fm, Fields fs,
+                                                      int mnx, int mny, int snx, int sny, int xcd, Condtq q) {
+  update_block<false, OptGeneric, true>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{}, q);
+}
+__global__ __launch_bounds__(SBT, SC_LB) void k_update_bud_ct(Geom g, const Consts* __restrict__ c,
+                                                          const StepState* __restrict__ s, Fields fm, Fields fs,
+                                                          int mnx, int mny, int snx, int sny, int xcd, Budget b,
+                                                          Condtq q) {
+  update_block<true, OptGeneric, true>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b, q);
 }
 
 // ---------------------------------------------------------------------------------------

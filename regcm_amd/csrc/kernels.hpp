@@ -155,6 +155,17 @@ struct Budget {
   double rw;
 };
 
+// SUBEX condensation (condtq, rcmdyn_set_condtq; condtq.hpp): the host's rh0adj, the three frame
+// arrays that hold the last tend's coupled increments of t, qv, qc (aten pc_physic after condtq),
+// and subexparam's conf.  An argument of its own of the condtq instances of the tendency kernels
+// (k_scalars_ct.., k_nh_tend_c with a Condtq argument); the other instances take none and hold no
+// code for it.
+struct Condtq {
+  const double* rh0adj;
+  double *it, *iqv, *iqc;
+  double conf;
+};
+
 // nqx = 5: the hydrometeors beyond qc (qi, qr, qs) for the current (a*) and next (b*) time-level
 // buffers (species.hip; the non-hydrostatic core updates a* in place and leaves b* null)
 struct QxArgs {
@@ -211,6 +222,15 @@ __global__ void k_scalars_bud(Geom g, const Consts* __restrict__ c, const StepSt
                               Budget b);
 __global__ void k_update_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
                              Fields fs, int mnx, int mny, int snx, int sny, int xcd, Budget b);
+// the condtq instances (generic; *_bud_ct: with the budget as well)
+__global__ void k_scalars_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
+                             Condtq q);
+__global__ void k_scalars_bud_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
+                                 Budget b, Condtq q);
+__global__ void k_update_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
+                            Fields fs, int mnx, int mny, int snx, int sny, int xcd, Condtq q);
+__global__ void k_update_bud_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
+                                Fields fs, int mnx, int mny, int snx, int sny, int xcd, Budget b, Condtq q);
 __global__ void k_qfilter(Geom g, const Consts* __restrict__ c, Fields f);
 // the serial fix passes resolve the chain (qxcommon.hpp), k_negfix_post / k_qx_post apply the
 // filters of the points they fixed

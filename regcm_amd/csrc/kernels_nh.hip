@@ -13,10 +13,12 @@
 // formed where it is read instead of being stored.  The state is updated in place (the
 // reference's own semantics); the intermediates that remain live in HBM (NHFields).  DESIGN.md
 // section 4.2 lists the kernels with their roofline position.
+#include <type_traits>
 #include "engine.hpp"
 #include "kernels_nh.hpp"
 #include "kernels.hpp"
 #include "fastmath.hpp"
+#include "condtq.hpp"
 #include "devcommon.hpp"
 #include "qxcommon.hpp"
 
@@ -358,12 +360,21 @@ constexpr int TC_NF = 5;
 // instance has the signature and the code it had without the budget (an empty pack, not a shared
 // __device__ body: called from two kernels, the body was scheduled differently in the default one
 // under this file's device scheduler, 3 376 -> 3 390 VALU instructions and 128 -> 130 VGPRs).
+// B may also end with Condtq (rcmdyn_set_condtq): the condtq instance holds the totals of t, qv
+// and pp back until the total of qc is known, adds condtq's increments (Main/mod_tendency.F90:
+// 336-349; condtq.hpp) before the Rayleigh damping of t and qv (:356-364), and then stores the
+// exports and forms the forecasts.
 __device__ __forceinline__ const Budget& budget_arg(const Budget& b) { return b; }
+__device__ __forceinline__ const Budget& budget_arg(const Budget& b, const Condtq&) { return b; }
+__device__ __forceinline__ const Condtq& condtq_arg(const Condtq& q) { return q; }
+__device__ __forceinline__ const Condtq& condtq_arg(const Budget&, const Condtq& q) { return q; }
+template <class T, class... B>
+constexpr bool pack_has = (std::is_same<T, B>::value || ...);
 template <bool QX, class... B>
 __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* __restrict__ c,
                                                    const StepState* __restrict__ s, NHFields f, int wdiag,
                                                    int istep, B... b) {
-  constexpr bool BUD = sizeof...(B) != 0;
+  constexpr bool BUD = pack_has<Budget, B...>, CT = pack_has<Condtq, B...>;
   // the horizontal stencil operands of this level for the 32 x 8 block and a 2-point halo,
   // staged in LDS once: the diffusion fields (13-point).  Staging the advected fields or the
   // relaxation differences as well measured slower at C5 (3.36 ms diffusion only, 3.66 ms
@@ -558,6 +569,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   avg(k, u1, u2, v1, v2);
   const double cr = F3(f.cr, j, i, k);
   // ================= pp: hadv3d ind 0, vadv3d ind = 0 (nk = kz), adiabatic, boundary, diffusion
+  double pth = d_zero, tth = d_zero, qvh = d_zero;    // CT: the totals of pp, t, qv before condtq
   {
     double pd = d_zero + hadx(f.a1pp, 0, u1, u2, v1, v2, 0);
     auto pflux = [&](int kk) {
@@ -571,6 +583,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     if (nudge) RELAX5(pd, f.ppb0, f.ppbt, f.a2pp);
     pd = c->idiffu == 3 ? diff6_add(g, pd, f.d6pp, g.jci2, j, i, k) : diffx_l(g, c, pd, sT[3], xkc, j, i, ti, tj);
     double pt = pt0 + pd + PHY(ppphy);
+    if constexpr (CT) pth = pt;
     if (c->ifrayd == 1 && k <= c->rayndamp)       // raydamp3 (CRM: raydamp3f toward 0, :468-470),
       pt = pt + nh_tau(c, F3(f.z0, j, i, k), F3(f.z0, j, i, 1)) *  // decoupling, acoustic-step scaling
                     ((c->crm ? d_zero : F3(f.ppb0, j, i, k) + xt * F3(f.ppbt, j, i, k)) - F3(f.a2pp, j, i, k));
@@ -613,12 +626,16 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     td = c->idiffu == 3 ? diff6_add(g, td, f.d6t, g.jci2, j, i, k) : diffx_l(g, c, td, sT[0], xkc, j, i, ti, tj);
     if constexpr (BUD) bud(0, 4, td, tb);
     double tt = tt0 + td + PHY(tphy);
-    tt = tt + 0.0;
-    if (ray) tt = tt + tau * ((F3(f.tb0, j, i, k) + xt * F3(f.tbt, j, i, k)) - F3(f.a2t, j, i, k));
-    if (wdiag) F3(f.tten, j, i, k) = tt;
-    const double o2 = F3(f.a2t, j, i, k), ctv = o2 + dt * tt;
-    if (f.tfuse) ra_t(c, F3(f.a1t, j, i, k), o2, ctv, F3(f.b1t, j, i, k), F3(f.b2t, j, i, k));
-    else F3(f.ct, j, i, k) = ctv;
+    if constexpr (CT) {
+      tth = tt;
+    } else {
+      tt = tt + 0.0;
+      if (ray) tt = tt + tau * ((F3(f.tb0, j, i, k) + xt * F3(f.tbt, j, i, k)) - F3(f.a2t, j, i, k));
+      if (wdiag) F3(f.tten, j, i, k) = tt;
+      const double o2 = F3(f.a2t, j, i, k), ctv = o2 + dt * tt;
+      if (f.tfuse) ra_t(c, F3(f.a1t, j, i, k), o2, ctv, F3(f.b1t, j, i, k), F3(f.b2t, j, i, k));
+      else F3(f.ct, j, i, k) = ctv;
+    }
   }
   // ================= qv: hadvqv (or the semi-Lagrangian start), vadvqv, adiabatic, boundary,
   // diffusion, forecast
@@ -656,14 +673,20 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     qd = c->idiffu == 3 ? diff6_add(g, qd, f.d6qv, g.jci2, j, i, k) : diffx_l(g, c, qd, sT[1], xkc, j, i, ti, tj);
     if constexpr (BUD) bud(1, 4, qd, qb);
     double qv = qt0 + qd + PHY(qvphy);
-    qv = qv + 0.0;
-    if (ray) qv = qv + tau * ((F3(f.qb0, j, i, k) + xt * F3(f.qbt, j, i, k)) - F3(f.a2qv, j, i, k));
-    if (wdiag) F3(f.qvten, j, i, k) = qv;
-    const double o2 = F3(f.a2qv, j, i, k), cq = o2 + dt * qv;
-    F3(f.cqv, j, i, k) = cq;
-    if (f.tfuse && !(cq < d_zero))      // a negative forecast: filtered after its fix
-      raw_qv(c, F3(f.a1qv, j, i, k), o2, cq, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
-    if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2);
+    if constexpr (CT) {
+      qvh = qv;
+    } else {
+      // (the CT branch of the qc chain below restates this damping, export, forecast, filter and
+      // neglist entry, and those of t, after its increments: change both copies together)
+      qv = qv + 0.0;
+      if (ray) qv = qv + tau * ((F3(f.qb0, j, i, k) + xt * F3(f.qbt, j, i, k)) - F3(f.a2qv, j, i, k));
+      if (wdiag) F3(f.qvten, j, i, k) = qv;
+      const double o2 = F3(f.a2qv, j, i, k), cq = o2 + dt * qv;
+      F3(f.cqv, j, i, k) = cq;
+      if (f.tfuse && !(cq < d_zero))      // a negative forecast: filtered after its fix
+        raw_qv(c, F3(f.a1qv, j, i, k), o2, cq, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
+      if (cq < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2);
+    }
   }
   // ================= qc: hadvqx (or the semi-Lagrangian start), vadv4d ind = 1, adiabatic,
   // diffusion, forecast
@@ -685,7 +708,40 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
     cd = cd + xqcat(k) * cr;
     cd = c->idiffu == 3 ? diff6_add(g, cd, f.d6qc, g.jci2, j, i, k) : diffx_l(g, c, cd, sT[2], xkc, j, i, ti, tj);
     double qc = d_zero + cd + PHY(qcphy);
-    qc = qc + 0.0;
+    if constexpr (CT) {
+      // condtq (Main/mod_micro_interface.F90:382-493) on the totals of this point: p* of the NH
+      // core is atm0's (sfs%psc points to sfs%psa, Main/mod_atm_interface.F90:890), pres from the
+      // total of pp before its Rayleigh damping (:415-416), qs = atms%qsb3d of the step's start
+      // as mkslice forms it (k_slice: pb3d with its k = 1 floor)
+      const Condtq& q = condtq_arg(b...);
+      const double t2 = F3(f.a2t, j, i, k), qv2 = F3(f.a2qv, j, i, k), qc2 = F3(f.a2qc, j, i, k);
+      const double rpb = F2(f.rpsb, j, i);
+      const double pres = F3(f.pr0, j, i, k) + (F3(f.a2pp, j, i, k) + dt * pth) / ps;
+      double pb = F3(f.pr0, j, i, k) + F3(f.a2pp, j, i, k) * rpb;
+      if (k == 1) pb = dmax(pb, c->ptop * d_1000 + 1.0);
+      const double qs = pfwsat(t2 * rpb, pb, cq::EP2);
+      double tmp2, wwlh, it, iqv, iqc;
+      condtq_point(t2, qv2, qc2, tth, qvh, qc, ps, pres, qs, F3(q.rh0adj, j, i, k), dt, q.conf, tmp2, wwlh);
+      condtq_increments(ps, tmp2, wwlh, it, iqv, iqc);
+      F3(q.it, j, i, k) = it; F3(q.iqv, j, i, k) = iqv; F3(q.iqc, j, i, k) = iqc;
+      // the totals with the condensation term (:345-349), the Rayleigh damping of t and qv
+      // (:356-364), the exports, the forecasts and their filters (the non-CT copies in the t and
+      // qv chains above, restated: change them together)
+      double tt = tth + it, qv = qvh + iqv;
+      qc = qc + iqc;
+      if (ray) tt = tt + tau * ((F3(f.tb0, j, i, k) + xt * F3(f.tbt, j, i, k)) - t2);
+      if (ray) qv = qv + tau * ((F3(f.qb0, j, i, k) + xt * F3(f.qbt, j, i, k)) - qv2);
+      if (wdiag) { F3(f.tten, j, i, k) = tt; F3(f.qvten, j, i, k) = qv; }
+      const double ctv = t2 + dt * tt, cv = qv2 + dt * qv;
+      if (f.tfuse) ra_t(c, F3(f.a1t, j, i, k), t2, ctv, F3(f.b1t, j, i, k), F3(f.b2t, j, i, k));
+      else F3(f.ct, j, i, k) = ctv;
+      F3(f.cqv, j, i, k) = cv;
+      if (f.tfuse && !(cv < d_zero))
+        raw_qv(c, F3(f.a1qv, j, i, k), qv2, cv, ps, pbs, F3(f.b1qv, j, i, k), F3(f.b2qv, j, i, k));
+      if (cv < d_zero) f.neglist[atomicAdd(f.negcnt, 1)] = (unsigned)(((long)(k - 1) * g.plane + g.ix(j, i)) * 2);
+    } else {
+      qc = qc + 0.0;
+    }
     if (wdiag) F3(f.qcten, j, i, k) = qc;
     const double o2 = F3(f.a2qc, j, i, k), cq = o2 + dt * qc;
     F3(f.cqc, j, i, k) = cq;
@@ -705,6 +761,12 @@ template __global__ void k_nh_tend_c<false, Budget>(Geom, const Consts* __restri
                                                      NHFields, int, int, Budget);
 template __global__ void k_nh_tend_c<true, Budget>(Geom, const Consts* __restrict__, const StepState* __restrict__,
                                                     NHFields, int, int, Budget);
+// the condtq instances (ipptls = 1: nqx = 2 only)
+template __global__ void k_nh_tend_c<false, Condtq>(Geom, const Consts* __restrict__, const StepState* __restrict__,
+                                                     NHFields, int, int, Condtq);
+template __global__ void k_nh_tend_c<false, Budget, Condtq>(Geom, const Consts* __restrict__,
+                                                             const StepState* __restrict__, NHFields, int, int, Budget,
+                                                             Condtq);
 #endif
 #if NH_OTHER_KERNELS
 

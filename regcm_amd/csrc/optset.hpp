@@ -30,13 +30,14 @@ struct OptQuery {
   const void *tten, *uten, *vten, *qvten, *qcten, *omega, *xkcs;   // exports
   const void *tphy, *qvphy, *qcphy, *uphy, *vphy;                   // physics tendencies of the seam
   const void* kpbl;
+  bool condtq;                          // the condtq instances stay generic (rcmdyn_set_condtq)
 };
 
 // RCMDYN_NO_OPTSET (present = the generic instances everywhere; Switches::read, engine.hip)
 inline bool optset_disabled_by_env() { return std::getenv("RCMDYN_NO_OPTSET") != nullptr; }
 
 inline OptInstance optset_instance(const OptQuery& q) {
-  if (q.no_optset || q.budget) return OPT_GENERIC;
+  if (q.no_optset || q.budget || q.condtq) return OPT_GENERIC;
   if (q.iboudy != OPT_IBOUDY || q.idiffu != OPT_IDIFFU || q.ipgf != OPT_IPGF || q.isladvec != OPT_ISLADVEC)
     return OPT_GENERIC;
   if (q.ibltyp == 2 || q.nqx_extra > 0) return OPT_GENERIC;

@@ -7,31 +7,14 @@
 // One thread per owned column walks the levels; every product and clamp is the reference's
 // expression in its order (-ffp-contract=off), the powers/logs use the device libm.
 #include "slice.hpp"
+#include "condtq.hpp"      // pfwsat (Share/pfesat.inc, Share/pfwsat.inc), shared with condtq
 
 namespace rcm {
 
 namespace {
 
 constexpr double P00 = 1.0e5;                 // Share/mod_constants.F90:229
-constexpr double TZERO = 273.15;              // :197
 constexpr double EGRAV_S = 9.80665;           // :85
-
-// pfesat / pfwsat, Share/pfesat.inc, Share/pfwsat.inc (Flatau et al. 1992 polynomials)
-__device__ double pfwsat(double t, double p, double ep2) {
-  double tl = t - TZERO;
-  if (tl > 100.0) tl = 100.0;
-  if (tl < -75.0) tl = -75.0;
-  const double td = tl;
-  double esat;
-  if (td >= 0.0)
-    esat = 6.11213476 + td * (0.444007856 + td * (0.143064234e-01 + td * (0.264461437e-03 + td * (0.305903558e-05 +
-           td * (0.196237241e-07 + td * (0.892344772e-10 + td * (-0.373208410e-12 + td * 0.209339997e-15)))))));
-  else
-    esat = 6.11123516 + td * (0.503109514 + td * (0.188369801e-01 + td * (0.420547422e-03 + td * (0.614396778e-05 +
-           td * (0.602780717e-07 + td * (0.387940929e-09 + td * (0.149436277e-11 + td * 0.262655803e-14)))))));
-  const double es = esat * 100.0;
-  return ep2 * (es / (p - es));
-}
 
 __device__ __forceinline__ double omega_hydro(const Geom& g, const Consts* c, const SliceArgs& a, int j, int i, int k) {
   // Main/mod_tendency.F90:1195-1214 (ud/vd = atm1 * (1/psdota), decouple :880-906)

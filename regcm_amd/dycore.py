@@ -33,6 +33,7 @@ EXPORTED = [
     "rcmdyn_exchange_plan", "rcmdyn_overlap_shares",
     "rcmdyn_set_budget", "rcmdyn_get_budget", "rcmdyn_reset_budget",
     "rcmdyn_set_massck", "rcmdyn_get_massck",
+    "rcmdyn_set_condtq", "rcmdyn_put_rh0adj", "rcmdyn_get_condtq",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
@@ -40,6 +41,8 @@ BUDGET_TERMS = ["T_ADH", "T_ADV", "T_ADI", "T_BDY", "T_DIF", "Q_ADH", "Q_ADV", "
 IQV = 1    # the reference's index of water vapour (Main/mpplib/mod_runparams.F90:38)
 # one record of the mass check (rcmdyn_get_massck), in order
 MASSCK_COLUMNS = ("lcount", "dt", "drymass", "dryadv", "qmass", "qadv")
+# enum rcmdyn_condtq_term, in order: the held rh0adj, the last tend's condensation increments
+CONDTQ_TERMS = ["RH0ADJ", "T", "QV", "QC"]
 
 
 class EngineError(RuntimeError):
@@ -90,6 +93,9 @@ def lib():
     L.rcmdyn_reset_budget.argtypes = [P]
     L.rcmdyn_set_massck.argtypes = [P, i32, i32]
     L.rcmdyn_get_massck.argtypes = [P, dp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64)]
+    L.rcmdyn_set_condtq.argtypes = [P, i32, ctypes.c_double]
+    L.rcmdyn_put_rh0adj.argtypes = [P, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_condtq.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -301,6 +307,30 @@ class DynCore:
         self._check(lib().rcmdyn_get_massck(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cap,
                                             ctypes.byref(n), ctypes.byref(lost)))
         return out[:n.value].copy(), int(lost.value)
+
+    def set_condtq(self, on: bool = True, conf: float = 1.0):
+        """The SUBEX condensation (condtq, ipptls = 1) inside tend; conf is subexparam's
+        condensation efficiency, in (0, 1].  Every later tend needs an rh0adj (put_rh0adj)."""
+        self._check(lib().rcmdyn_set_condtq(self.h, 1 if on else 0, conf))
+
+    def put_rh0adj(self, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+        """cldfrac's adjusted humidity threshold, a (kz, ni, nj) array of values in [0, 0.99999]
+        starting at the global indices (j1, i1, k1).  tend waits for one put since the switch-on
+        that covers the interior cross points of the tiles and their rings on every level."""
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        nk, ni, nj = a.shape
+        self._check(lib().rcmdyn_put_rh0adj(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+
+    def get_condtq(self, term) -> np.ndarray:
+        """One term by name (CONDTQ_TERMS) or number as a (kz, iy, jx) array: the held rh0adj, or
+        the last tend's coupled condensation increment of t, qv or qc (zero outside the interior
+        cross points)."""
+        n = CONDTQ_TERMS.index(term) if isinstance(term, str) else int(term)
+        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
+        self._check(lib().rcmdyn_get_condtq(self.h, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
+        return out
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

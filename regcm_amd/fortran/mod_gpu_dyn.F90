@@ -53,6 +53,11 @@ module mod_gpu_dyn
     bud_q_adh = 5, bud_q_adv = 6, bud_q_adi = 7, bud_q_bdy = 8, bud_q_dif = 9, &
     rcmdyn_nbudget = 10
 
+  ! terms of rcmdyn_get_condtq (enum rcmdyn_condtq_term): the held rh0adj, the last tend's coupled
+  ! condensation increments of t, qv, qc (aten(.., pc_physic) after condtq: tdiag%lsc, qdiag%lsc)
+  integer(c_int32_t), parameter, public :: &
+    condtq_rh0adj = 0, condtq_t = 1, condtq_qv = 2, condtq_qc = 3, rcmdyn_ncondtq = 4
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -268,6 +273,32 @@ module mod_gpu_dyn
       integer(c_int32_t), intent(out) :: count
       integer(c_int64_t), intent(out) :: lost
     end function
+    ! the SUBEX condensation (condtq, ipptls = 1) inside tend on (1) or off (0, the default); conf
+    ! is subexparam's condensation efficiency, in (0, 1]
+    integer(c_int) function rcmdyn_set_condtq(h, on, conf) bind(c, name='rcmdyn_set_condtq')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on
+      real(c_double), value :: conf
+    end function
+    ! cldfrac's rh0adj(j1:j2,i1:i2,k1:k2), every value in [0, 0.99999]; on the split path between
+    ! rcmdyn_tend_pre_physics and rcmdyn_tend_post_physics.  tend waits for one put since the
+    ! switch-on that covers the tiles' interior cross points and their rings on every level
+    integer(c_int) function rcmdyn_put_rh0adj(h, src, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_put_rh0adj')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(in) :: src(*)
+      integer(c_int32_t), value :: j1, j2, i1, i2, k1, k2
+    end function
+    ! one term (condtq_rh0adj .. condtq_qc) into dst(j1:j2,i1:i2,k1:k2)
+    integer(c_int) function rcmdyn_get_condtq(h, term, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_condtq')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: term, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -288,6 +319,7 @@ module mod_gpu_dyn
   public :: rcmdyn_overlap_shares, rcmdyn_runtime_info, rcmdyn_last_step_ms, rcmdyn_set_diagnostics
   public :: rcmdyn_kernel_times, rcmdyn_set_budget, rcmdyn_get_budget, rcmdyn_reset_budget
   public :: rcmdyn_set_massck, rcmdyn_get_massck
+  public :: rcmdyn_set_condtq, rcmdyn_put_rh0adj, rcmdyn_get_condtq
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains
