@@ -35,6 +35,7 @@
 #include "fieldtab.hpp"
 #include "massck.hpp"
 #include "optset.hpp"
+#include "pointops.hpp"   // the policies OptDefault / OptGeneric the tendency kernels are instantiated on
 
 using namespace rcm;
 
@@ -398,6 +399,20 @@ struct rcmdyn_engine {
   bool condtq = false, rh0_put = false;
   double ct_conf = 1.0;
   Condtq condtq_args(const Tile& t) const { return Condtq{t.rh0adj, t.cti[0], t.cti[1], t.cti[2], ct_conf}; }
+  // The extra argument blocks of a tendency launch (kernels.hpp): fn(blocks...) with those that
+  // are switched on, Budget before Condtq.  fn is a generic lambda that issues the launch of the
+  // instance its arguments name, so a further switch is one more rung here for every kernel.
+  template <class F>
+  void with_extras(const Tile& t, F&& fn) const {
+    if (condtq && budget) fn(budget_args(t), condtq_args(t));
+    else if (condtq) fn(condtq_args(t));
+    else if (budget) fn(budget_args(t));
+    else fn();
+  }
+  // the name an instance reports to the kernel-time profile: every instance the kernel's plain
+  // name, the budget ones (with or without condtq) the name they always had
+  template <class... B>
+  static const char* tend_name(const char* plain, const char* bud) { return pack_has<Budget, B...> ? bud : plain; }
   void condtq_ready(const char* who) const {
     if (condtq && !rh0_put)
       throw std::runtime_error(std::string(who) + ": condtq is on and no rh0adj was put since that covers the tiles' interior "
@@ -762,14 +777,14 @@ struct rcmdyn_engine {
   // a block-size mismatch between a kernel and its launch fails here, not as unwritten points.
   void check_block_sizes() {
     struct K { const void* f; int threads; const char* name; };
-    const K ks[] = {{(const void*)k_update, SBT, "k_update"},
-                    {(const void*)k_momentum, MBT, "k_momentum"},
-                    {(const void*)k_scalars, SBT, "k_scalars"},
-                    {(const void*)k_update_gen, SBT, "k_update_gen"},
-                    {(const void*)k_momentum_gen, MBT, "k_momentum_gen"},
-                    {(const void*)k_scalars_gen, SBT, "k_scalars_gen"},
-                    {(const void*)k_update_bud, SBT, "k_update_bud"},
-                    {(const void*)k_scalars_bud, SBT, "k_scalars_bud"},
+    const K ks[] = {{(const void*)k_update<OptDefault>, SBT, "k_update<OptDefault>"},
+                    {(const void*)k_momentum<OptDefault>, MBT, "k_momentum<OptDefault>"},
+                    {(const void*)k_scalars<OptDefault>, SBT, "k_scalars<OptDefault>"},
+                    {(const void*)k_update<OptGeneric>, SBT, "k_update<OptGeneric>"},
+                    {(const void*)k_momentum<OptGeneric>, MBT, "k_momentum<OptGeneric>"},
+                    {(const void*)k_scalars<OptGeneric>, SBT, "k_scalars<OptGeneric>"},
+                    {(const void*)k_update<OptGeneric, Budget>, SBT, "k_update<OptGeneric, Budget>"},
+                    {(const void*)k_scalars<OptGeneric, Budget>, SBT, "k_scalars<OptGeneric, Budget>"},
                     {(const void*)k_qx_tend, QBT, "k_qx_tend"}};
     for (const K& k : ks) {
       hipFuncAttributes a{};
@@ -1200,6 +1215,11 @@ struct rcmdyn_engine {
       "no slice fields yet (rcmdyn_tend_pre_physics)", "tendency diagnostics are off (rcmdyn_set_diagnostics)"};
   static_assert(fieldtab::DIAG == 5 && sizeof(WAITS_FOR) / sizeof(WAITS_FOR[0]) == 6, "one text per fieldtab::Lazy");
 
+  // the global index a frame point past either end of a period stands for: a band's columns
+  // (i_band) and the CRM's rows (i_crm) wrap, any other index is itself
+  int wrap_j(int j) const { return !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j)); }
+  int wrap_i(int i) const { return !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i)); }
+
   // The host box src (j fastest, then i, then k) into a tile's buffer d of nk levels: every frame
   // point of the tile whose global index lies in the box, the ghost ring included, and the frame
   // points past either end of a period from the wrapped index.  (rcmdyn_put, rcmdyn_put_rh0adj)
@@ -1211,17 +1231,28 @@ struct rcmdyn_engine {
     HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
     for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
       for (int i = g.i0; i <= g.i0 + g.ni - 1; i++) {
-        // CRM: the frame rows past either end of the period take the wrapped row
-        const int iw = !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i));
+        const int iw = wrap_i(i);
         if (iw < i1 || iw > i2) continue;
         for (int j = g.j0; j <= g.j0 + g.nj - 1; j++) {
-          // a band's frame columns past either end of the period take the wrapped column
-          const int jw = !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j));
+          const int jw = wrap_j(j);
           if (jw < j1 || jw > j2) continue;
           h[(size_t)(k - 1) * g.plane + g.ix(j, i)] = src[((size_t)(k - k1) * ni + (iw - i1)) * nj + (jw - j1)];
         }
       }
     HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  }
+  // The other way: a tile's buffer d of nk levels into the host box dst, the tile's points
+  // [ja, jb] x [ia, ib] that lie in the box.  (rcmdyn_get, rcmdyn_get_budget, rcmdyn_get_condtq)
+  void gather_box(const Tile& t, const double* d, int nk, double* dst, int j1, int j2, int i1, int i2, int k1,
+                  int k2, int ja, int jb, int ia, int ib) {
+    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const Geom& g = t.g;
+    std::vector<double> h((size_t)nk * g.plane);
+    HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
+    for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
+      for (int i = std::max(i1, ia); i <= std::min(i2, ib); i++)
+        for (int j = std::max(j1, ja); j <= std::min(j2, jb); j++)
+          dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
   }
 
   void put(int f, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
@@ -1363,18 +1394,11 @@ struct rcmdyn_engine {
     }
     HIPCHK(hipStreamSynchronize(stream));
     check_now();
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
     for (auto& t : tiles) {
       double* d = field_ptr(t, f);
       if (!d) throw std::runtime_error("rcmdyn_get: unknown field");
-      const int nk = field_levels(f);
       const Geom& g = t.g;
-      std::vector<double> h((size_t)nk * g.plane);
-      HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-        for (int i = std::max(i1, g.ide1); i <= std::min(i2, g.ide2); i++)
-          for (int j = std::max(j1, g.jde1); j <= std::min(j2, g.jde2); j++)
-            dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+      gather_box(t, d, field_levels(f), dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
     }
   }
 
@@ -1404,16 +1428,9 @@ struct rcmdyn_engine {
     if (term < 0 || term >= RCMDYN_NBUDGET) throw std::runtime_error("rcmdyn_get_budget: unknown budget term");
     HIPCHK(hipStreamSynchronize(stream));
     check_now();
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
-    const int nk = cfg.kz;
     for (auto& t : tiles) {
       const Geom& g = t.g;
-      std::vector<double> h((size_t)nk * g.plane);
-      HIPCHK(hipMemcpy(h.data(), t.bud[term], h.size() * 8, hipMemcpyDeviceToHost));
-      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-        for (int i = std::max(i1, g.ide1); i <= std::min(i2, g.ide2); i++)
-          for (int j = std::max(j1, g.jde1); j <= std::min(j2, g.jde2); j++)
-            dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+      gather_box(t, t.bud[term], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
     }
   }
   void reset_budget() {
@@ -1470,9 +1487,9 @@ struct rcmdyn_engine {
     for (const auto& t : tiles) {
       const Geom& g = t.g;
       for (int i = g.icx1(); all && i <= g.icx2(); i++) {
-        const int iw = !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i));
+        const int iw = wrap_i(i);
         for (int j = g.jcx1(); all && j <= g.jcx2(); j++) {
-          const int jw = !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j));
+          const int jw = wrap_j(j);
           if (g.gci(j, i) && (jw < j1 || jw > j2 || iw < i1 || iw > i2)) all = false;
         }
       }
@@ -1485,20 +1502,14 @@ struct rcmdyn_engine {
     if (term < 0 || term >= RCMDYN_NCONDTQ) throw std::runtime_error("rcmdyn_get_condtq: unknown term");
     HIPCHK(hipStreamSynchronize(stream));
     check_now();
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
-    const int nk = cfg.kz;
     for (auto& t : tiles) {
       const Geom& g = t.g;
-      std::vector<double> h((size_t)nk * g.plane);
-      HIPCHK(hipMemcpy(h.data(), term == RCMDYN_CONDTQ_RH0ADJ ? t.rh0adj : t.cti[term - RCMDYN_CONDTQ_T], h.size() * 8,
-                       hipMemcpyDeviceToHost));
       // the increments live on the tile's interior cross points (the ring's are its neighbours')
-      const bool inc = term != RCMDYN_CONDTQ_RH0ADJ;
-      const int ja = inc ? g.jci1 : g.jde1, jb = inc ? g.jci2 : g.jde2, ia = inc ? g.ici1 : g.ide1, ib = inc ? g.ici2 : g.ide2;
-      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-        for (int i = std::max(i1, ia); i <= std::min(i2, ib); i++)
-          for (int j = std::max(j1, ja); j <= std::min(j2, jb); j++)
-            dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+      if (term == RCMDYN_CONDTQ_RH0ADJ)
+        gather_box(t, t.rh0adj, cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
+      else
+        gather_box(t, t.cti[term - RCMDYN_CONDTQ_T], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jci1, g.jci2, g.ici1,
+                   g.ici2);
     }
   }
 
@@ -2293,29 +2304,24 @@ struct rcmdyn_engine {
   }
   void tend_c_launch(Tile& t, const NHFields& f, int istep) {
     const Geom& g = t.g;
-    const dim3 gc((g.nj + TC_J - 1) / TC_J, (g.ni + TC_I - 1) / TC_I, cfg.kz + 1);
+    const dim3 grid(cfg.kz + 1, (g.nj + TC_J - 1) / TC_J, (g.ni + TC_I - 1) / TC_I), blk(TC_J, TC_I);
     if (hc.nsp) {
-      if (budget)
-        KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-                (int)diag, istep, budget_args(t));
-      else
-        KLAUNCH(k_nh_tend_c<true>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-                (int)diag, istep);
+      // nqx = 5 belongs to ipptls = 2 and condtq to ipptls = 1 (set_condtq refuses the pair): the
+      // QX instances exist with and without Budget only
+      auto launch = [&](auto... x) {
+        constexpr auto kern = k_nh_tend_c<true, decltype(x)...>;
+        KLAUNCH_AS("k_nh_tend_c<true>", kern, grid, blk, 0, stream, g, dc, ds, f, (int)diag, istep, x...);
+      };
+      if (budget) launch(budget_args(t));
+      else launch();
       // the chains of qi, qr, qs after it on the same stream
       KLAUNCH(k_nh_qx_tend, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0, stream, g, dc, ds, f,
               qx_args(t));
-    } else if (condtq && budget) {
-      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-              (int)diag, istep, budget_args(t), condtq_args(t));
-    } else if (condtq) {
-      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-              (int)diag, istep, condtq_args(t));
-    } else if (budget) {
-      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-              (int)diag, istep, budget_args(t));
     } else {
-      KLAUNCH(k_nh_tend_c<false>, dim3(gc.z, gc.x, gc.y), dim3(TC_J, TC_I), 0, stream, g, dc, ds, f,
-              (int)diag, istep);
+      with_extras(t, [&](auto... x) {
+        constexpr auto kern = k_nh_tend_c<false, decltype(x)...>;
+        KLAUNCH_AS("k_nh_tend_c<false>", kern, grid, blk, 0, stream, g, dc, ds, f, (int)diag, istep, x...);
+      });
     }
   }
   // the forecasts exchanged after the tendency kernels (atmc%qx, :381)
@@ -2467,48 +2473,31 @@ struct rcmdyn_engine {
     const int pm = part == 0 ? 0 : (t.nint && t.mom_in ? part : (part == 1 ? -1 : 0));
     const int ps = part == 0 ? 0 : (t.nint && t.sca_in ? part : (part == 1 ? -1 : 0));
     const int mo = pm > 0 ? t.mj0 : g.jdi1, so = ps > 0 ? t.sj0 : g.jcx1();     // block-column origins
-    if (sw.fuse_update && pm >= 0 && ps >= 0) {
-      const int mnx = (mj2 - mo + MBJ) / MBJ, mny = (mi2 - g.idi1 + MBI) / MBI;
-      const int snx = (g.jcx2() - so + SBJ) / SBJ, sny = (g.icx2() - g.icx1() + SBI) / SBI;
-      const int xcd = (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW);
-      const dim3 grid(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz);
-      const Fields fm = fields(t, pm), fs = fields(t, ps);
-      if (condtq && budget)
-        KLAUNCH_AS("k_update_bud", k_update_bud_ct, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny,
-                   xcd, budget_args(t), condtq_args(t));
-      else if (condtq)
-        KLAUNCH_AS("k_update", k_update_ct, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd,
-                   condtq_args(t));
-      else if (budget)
-        KLAUNCH(k_update_bud, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd, budget_args(t));
-      else if (opt_instance(fm) == OPT_DEFAULT && opt_instance(fs) == OPT_DEFAULT)
-        KLAUNCH(k_update, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd);
-      else
-        KLAUNCH_AS("k_update", k_update_gen, grid, dim3(SBT), 0, stream, g, dc, ds, fm, fs, mnx, mny, snx, sny, xcd);
-      return;
-    }
-    const bool def = opt_instance(fields(t)) == OPT_DEFAULT;
-    if (pm >= 0 && def)
-      KLAUNCH(k_momentum, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz), dim3(MBT), 0,
-              stream, g, dc, ds, fields(t, pm));
-    else if (pm >= 0)
-      KLAUNCH_AS("k_momentum", k_momentum_gen, dim3((mj2 - mo + MBJ) / MBJ, (mi2 - g.idi1 + MBI) / MBI, cfg.kz),
-                 dim3(MBT), 0, stream, g, dc, ds, fields(t, pm));
-    if (ps >= 0 && condtq && budget)
-      KLAUNCH_AS("k_scalars_bud", k_scalars_bud_ct, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
-                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t), condtq_args(t));
-    else if (ps >= 0 && condtq)
-      KLAUNCH_AS("k_scalars", k_scalars_ct, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
-                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), condtq_args(t));
-    else if (ps >= 0 && budget)
-      KLAUNCH(k_scalars_bud, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
-              dim3(SBT), 0, stream, g, dc, ds, fields(t, ps), budget_args(t));
-    else if (ps >= 0 && def)
-      KLAUNCH(k_scalars, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
-              dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
-    else if (ps >= 0)
-      KLAUNCH_AS("k_scalars", k_scalars_gen, dim3((g.jcx2() - so + SBJ) / SBJ, (g.icx2() - g.icx1() + SBI) / SBI, cfg.kz),
-                 dim3(SBT), 0, stream, g, dc, ds, fields(t, ps));
+    const int mnx = (mj2 - mo + MBJ) / MBJ, mny = (mi2 - g.idi1 + MBI) / MBI;
+    const int snx = (g.jcx2() - so + SBJ) / SBJ, sny = (g.icx2() - g.icx1() + SBI) / SBI;
+    // o: the policy of the instances (an OptDefault or OptGeneric value), x: the extra blocks
+    auto launch = [&](auto o, auto... x) {
+      using O = decltype(o);
+      if (sw.fuse_update && pm >= 0 && ps >= 0) {
+        const int xcd = (int)((long)(g.jde2 - g.jde1 + 1) * (g.ide2 - g.ide1 + 1) < UPD_XCD_BELOW);
+        constexpr auto kern = k_update<O, decltype(x)...>;
+        KLAUNCH_AS(tend_name<decltype(x)...>("k_update", "k_update_bud"), kern,
+                   dim3(std::max(mnx, snx), std::max(mny, sny), 2 * cfg.kz), dim3(SBT), 0, stream, g, dc, ds,
+                   fields(t, pm), fields(t, ps), mnx, mny, snx, sny, xcd, x...);
+        return;
+      }
+      if (pm >= 0)
+        KLAUNCH_AS("k_momentum", k_momentum<O>, dim3(mnx, mny, cfg.kz), dim3(MBT), 0, stream, g, dc, ds,
+                   fields(t, pm));
+      if (ps >= 0) {
+        constexpr auto kern = k_scalars<O, decltype(x)...>;
+        KLAUNCH_AS(tend_name<decltype(x)...>("k_scalars", "k_scalars_bud"), kern, dim3(snx, sny, cfg.kz), dim3(SBT),
+                   0, stream, g, dc, ds, fields(t, ps), x...);
+      }
+    };
+    // the default-set instances take no extra block (optset_instance: generic with any of them)
+    if (opt_instance(fields(t)) == OPT_DEFAULT) launch(OptDefault{});
+    else with_extras(t, [&](auto... x) { launch(OptGeneric{}, x...); });
   }
 
   void tend_post(Corr corr, bool post_inner) {

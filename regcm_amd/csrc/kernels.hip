@@ -855,16 +855,14 @@ __device__ __forceinline__ void momentum_block(const Geom& g, const Consts* __re
   PT_PRINT(2);
 }
 // the default-set instance (optset.hpp) and the generic one
+template <class O>
 __global__ __launch_bounds__(MBT, MO_LB) void k_momentum(Geom g, const Consts* __restrict__ c,
                                                      const StepState* __restrict__ s, Fields f) {
   __shared__ MomLDS L;
-  momentum_block<OptDefault>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
+  momentum_block<O>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
 }
-__global__ __launch_bounds__(MBT, MO_LB) void k_momentum_gen(Geom g, const Consts* __restrict__ c,
-                                                         const StepState* __restrict__ s, Fields f) {
-  __shared__ MomLDS L;
-  momentum_block<OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
-}
+template __global__ void k_momentum<OptDefault>(Geom, const Consts* __restrict__, const StepState* __restrict__, Fields);
+template __global__ void k_momentum<OptGeneric>(Geom, const Consts* __restrict__, const StepState* __restrict__, Fields);
 
 // ---------------------------------------------------------------------------------------
 // K4. Scalars at the cross points jce x ice, one level per block of SBJ x SBI points:
@@ -962,11 +960,15 @@ struct ScaLDS {
 // thread, so it holds tt and tq back until tc is known, adds condtq's increments
 // (Main/mod_tendency.F90:336-349), and only then stores the tendency exports and forms the
 // forecasts (:368-380) with their filters.
-template <bool BUD, class O, bool CT = false>
+// xb: the kernel's extra argument blocks (kernels.hpp); a block that is not among them is a
+// value-initialised one here, which the instance never reads.
+template <class O, class... B>
 __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __restrict__ c,
                                               const StepState* __restrict__ s, const Fields& f, ScaLDS& L,
-                                              int bx, int by, int bz, const Budget& b,
-                                              const Condtq& ctq = Condtq{}) {
+                                              int bx, int by, int bz, const B&... xb) {
+  constexpr bool BUD = pack_has<Budget, B...>, CT = pack_has<Condtq, B...>;
+  const Budget b = pack_get<Budget>(xb...);
+  const Condtq ctq = pack_get<Condtq>(xb...);
   auto& sUMC = L.sUMC; auto& sVMC = L.sVMC; auto& sUD = L.sUD; auto& sVD = L.sVD; auto& sUB = L.sUB;
   auto& sVB = L.sVB; auto& sPS = L.sPS; auto& sXT = L.sXT; auto& sXQV = L.sXQV; auto& sXQC = L.sXQC;
   auto& sTB = L.sTB; auto& sQVB = L.sQVB; auto& sQCB = L.sQCB;
@@ -1314,34 +1316,20 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   }
   PT_PRINT(3);
 }
-// the default-set instance (optset.hpp), the generic one and the budget one (generic)
+// O: the default-set policy (optset.hpp) or the generic one; B: the extra blocks (generic only)
+template <class O, class... B>
 __global__ __launch_bounds__(SBT, SC_LB) void k_scalars(Geom g, const Consts* __restrict__ c,
-                                                    const StepState* __restrict__ s, Fields f) {
+                                                    const StepState* __restrict__ s, Fields f, B... b) {
   __shared__ ScaLDS L;
-  scalars_block<false, OptDefault>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
+  scalars_block<O>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b...);
 }
-__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_gen(Geom g, const Consts* __restrict__ c,
-                                                        const StepState* __restrict__ s, Fields f) {
-  __shared__ ScaLDS L;
-  scalars_block<false, OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{});
-}
-__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud(Geom g, const Consts* __restrict__ c,
-                                                        const StepState* __restrict__ s, Fields f, Budget b) {
-  __shared__ ScaLDS L;
-  scalars_block<true, OptGeneric>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b);
-}
-// the condtq instances (generic), without and with the budget
-__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_ct(Geom g, const Consts* __restrict__ c,
-                                                       const StepState* __restrict__ s, Fields f, Condtq q) {
-  __shared__ ScaLDS L;
-  scalars_block<false, OptGeneric, true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Budget{}, q);
-}
-__global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud_ct(Geom g, const Consts* __restrict__ c,
-                                                           const StepState* __restrict__ s, Fields f, Budget b,
-                                                           Condtq q) {
-  __shared__ ScaLDS L;
-  scalars_block<true, OptGeneric, true>(g, c, s, f, L, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, b, q);
-}
+#define SC_ARGS Geom, const Consts* __restrict__, const StepState* __restrict__, Fields
+template __global__ void k_scalars<OptDefault>(SC_ARGS);
+template __global__ void k_scalars<OptGeneric>(SC_ARGS);
+template __global__ void k_scalars<OptGeneric, Budget>(SC_ARGS, Budget);
+template __global__ void k_scalars<OptGeneric, Condtq>(SC_ARGS, Condtq);
+template __global__ void k_scalars<OptGeneric, Budget, Condtq>(SC_ARGS, Budget, Condtq);
+#undef SC_ARGS
 
 // k_momentum and k_scalars in one launch: blockIdx.z < kz a scalars block of level z + 1, else
 // a momentum block of level z - kz + 1 (x/y: the larger of the two grids; a block past its own
@@ -1350,13 +1338,11 @@ __global__ __launch_bounds__(SBT, SC_LB) void k_scalars_bud_ct(Geom g, const Con
 // longer scalars blocks dispatched first the momentum blocks fill it (C3, alternating on one
 // box: 203.5-212.1 us/step against 211.2-222.9 with the momentum blocks first, 222.3-224.1
 // interleaved by level, 218.8-223.6 as two launches).
-// Three instances of the one body: the default set (k_update, optset.hpp), the generic one
-// (k_update_gen) and the budget one (k_update_bud, generic).
-template <bool BUD, class O, bool CT = false>
+// The instances are k_scalars' (O and B as there).
+template <class O, class... B>
 __device__ __forceinline__ void update_block(const Geom& g, const Consts* __restrict__ c,
                                              const StepState* __restrict__ s, const Fields& fm, const Fields& fs,
-                                             int mnx, int mny, int snx, int sny, int xcd, const Budget& b,
-                                             const Condtq& ctq = Condtq{}) {
+                                             int mnx, int mny, int snx, int sny, int xcd, const B&... b) {
   __shared__ union { MomLDS m; ScaLDS s; } L;
   const int kz = c->kz, bz = (int)blockIdx.z;
   int bx = (int)blockIdx.x, by = (int)blockIdx.y;
@@ -1366,36 +1352,22 @@ __device__ __forceinline__ void update_block(const Geom& g, const Consts* __rest
   if (mom) {
     if (bx < mnx && by < mny) momentum_block<O>(g, c, s, fm, L.m, bx, by, lz);
   } else if (bx < snx && by < sny) {
-    if constexpr (CT) scalars_block<BUD, O, true>(g, c, s, fs, L.s, bx, by, lz, b, ctq);
-    else scalars_block<BUD, O>(g, c, s, fs, L.s, bx, by, lz, b);
+    scalars_block<O>(g, c, s, fs, L.s, bx, by, lz, b...);
   }
 }
+template <class O, class... B>
 __global__ __launch_bounds__(SBT, SC_LB) void k_update(Geom g, const Consts* __restrict__ c,
                                                    const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                   int mnx, int mny, int snx, int sny, int xcd) {
-  update_block<false, OptDefault>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{});
+                                                   int mnx, int mny, int snx, int sny, int xcd, B... b) {
+  update_block<O>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b...);
 }
-__global__ __launch_bounds__(SBT, SC_LB) void k_update_gen(Geom g, const Consts* __restrict__ c,
-                                                       const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                       int mnx, int mny, int snx, int sny, int xcd) {
-  update_block<false, OptGeneric>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{});
-}
-__global__ __launch_bounds__(SBT, SC_LB) void k_update_bud(Geom g, const Consts* __restrict__ c,
-                                                       const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                       int mnx, int mny, int snx, int sny, int xcd, Budget b) {
-  update_block<true, OptGeneric>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b);
-}
-__global__ __launch_bounds__(SBT, SC_LB) void k_update_ct(Geom g, const Consts* __restrict__ c,
-                                                      const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                      int mnx, int mny, int snx, int sny, int xcd, Condtq q) {
-  update_block<false, OptGeneric, true>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, Budget{}, q);
-}
-__global__ __launch_bounds__(SBT, SC_LB) void k_update_bud_ct(Geom g, const Consts* __restrict__ c,
-                                                          const StepState* __restrict__ s, Fields fm, Fields fs,
-                                                          int mnx, int mny, int snx, int sny, int xcd, Budget b,
-                                                          Condtq q) {
-  update_block<true, OptGeneric, true>(g, c, s, fm, fs, mnx, mny, snx, sny, xcd, b, q);
-}
+#define UP_ARGS Geom, const Consts* __restrict__, const StepState* __restrict__, Fields, Fields, int, int, int, int, int
+template __global__ void k_update<OptDefault>(UP_ARGS);
+template __global__ void k_update<OptGeneric>(UP_ARGS);
+template __global__ void k_update<OptGeneric, Budget>(UP_ARGS, Budget);
+template __global__ void k_update<OptGeneric, Condtq>(UP_ARGS, Condtq);
+template __global__ void k_update<OptGeneric, Budget, Condtq>(UP_ARGS, Budget, Condtq);
+#undef UP_ARGS
 
 // ---------------------------------------------------------------------------------------
 // K6. Negative-moisture fix + the RA filter of p* + the RAW filter of qv/qc, one pass

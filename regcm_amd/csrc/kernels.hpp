@@ -1,5 +1,6 @@
 // kernels.hpp -- device kernels of kernels.hip and the argument blocks they share.
 #pragma once
+#include <type_traits>
 #include "engine.hpp"
 
 namespace rcm {
@@ -145,10 +146,11 @@ struct Fields {
 
 // Tendency budget of t and qv (idiag = 1, rcmdyn_set_budget): the accumulators tdiag / qdiag
 // %adh, adv, adi, bdy, dif of ten2diag (Main/mod_tendency.F90:2123-2175), frame planes like tten,
-// and the host's alarm_out_atm%rw.  An argument of its own of the budget instances of the
-// tendency kernels (k_scalars_bud, k_update_bud, k_nh_tend_c_bud); the default instances take
-// none and hold no code for it.  Each term is the rounded difference of the running tendency
-// around its stage, acc = acc + (after - before) * rw, on the tile's own interior cross points.
+// and the host's alarm_out_atm%rw.  A trailing argument of its own of the budget instances of the
+// tendency kernels (k_scalars, k_update, k_nh_tend_c with Budget in their pack); the other
+// instances take none and hold no code for it.  Each term is the rounded difference of the
+// running tendency around its stage, acc = acc + (after - before) * rw, on the tile's own
+// interior cross points.
 constexpr int NBUDTERM = 5;          // adh, adv, adi, bdy, dif
 struct Budget {
   double *t[NBUDTERM], *q[NBUDTERM];
@@ -157,14 +159,27 @@ struct Budget {
 
 // SUBEX condensation (condtq, rcmdyn_set_condtq; condtq.hpp): the host's rh0adj, the three frame
 // arrays that hold the last tend's coupled increments of t, qv, qc (aten pc_physic after condtq),
-// and subexparam's conf.  An argument of its own of the condtq instances of the tendency kernels
-// (k_scalars_ct.., k_nh_tend_c with a Condtq argument); the other instances take none and hold no
-// code for it.
+// and subexparam's conf.  A trailing argument of its own of the condtq instances of the tendency
+// kernels (Condtq in their pack, after Budget); the other instances take none and hold no code
+// for it.
 struct Condtq {
   const double* rh0adj;
   double *it, *iqv, *iqc;
   double conf;
 };
+
+// The extra argument blocks of a tendency kernel are a trailing pack B... (empty, Budget, Condtq
+// or Budget, Condtq): pack_has tells an instance whether a block is among them, pack_get returns
+// it (a value-initialised one when it is not, for code that the instance does not hold)
+template <class T, class... B>
+constexpr bool pack_has = (std::is_same<T, B>::value || ...);
+template <class T>
+__host__ __device__ __forceinline__ T pack_get() { return T{}; }
+template <class T, class B0, class... B>
+__host__ __device__ __forceinline__ T pack_get(const B0& b0, const B&... b) {
+  if constexpr (std::is_same<T, B0>::value) return b0;
+  else return pack_get<T>(b...);
+}
 
 // nqx = 5: the hydrometeors beyond qc (qi, qr, qs) for the current (a*) and next (b*) time-level
 // buffers (species.hip; the non-hydrostatic core updates a* in place and leaves b* null)
@@ -205,32 +220,18 @@ __global__ void k_surface_pressures(Geom g, Fields f);
 template <bool QX>
 __global__ void k_columns(Geom g, const Consts* __restrict__ c, StepState* s, Fields f, int nxb, int ncol);
 __global__ void k_sladv(Geom g, const Consts* __restrict__ c, StepState* s, Fields f, QxArgs q);
-// k_momentum, k_scalars, k_update: the instance compiled for the default option set
-// (optset.hpp); *_gen: the generic instance of the same body, any option.  The engine reports
-// either under the plain name.
+// k_momentum, k_scalars, k_update: O the policy of the option reads (pointops.hpp; the engine
+// picks OptDefault or OptGeneric per launch, optset.hpp), B... the extra argument blocks above.
+// The instances are those kernels.hip instantiates: <OptDefault>, <OptGeneric>, and for the
+// latter two kernels <OptGeneric, Budget>, <OptGeneric, Condtq>, <OptGeneric, Budget, Condtq>.
+template <class O>
 __global__ void k_momentum(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
-__global__ void k_momentum_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
 __global__ void k_diffu6(Geom g, const Consts* __restrict__ c, Fields f, QxArgs q);
-__global__ void k_scalars(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
-__global__ void k_scalars_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f);
+template <class O, class... B>
+__global__ void k_scalars(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f, B... b);
+template <class O, class... B>
 __global__ void k_update(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm, Fields fs,
-                         int mnx, int mny, int snx, int sny, int xcd);
-__global__ void k_update_gen(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
-                             Fields fs, int mnx, int mny, int snx, int sny, int xcd);
-// the budget instances of the two (the scalars blocks also accumulate the tendency budget; generic)
-__global__ void k_scalars_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
-                              Budget b);
-__global__ void k_update_bud(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
-                             Fields fs, int mnx, int mny, int snx, int sny, int xcd, Budget b);
-// the condtq instances (generic; *_bud_ct: with the budget as well)
-__global__ void k_scalars_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
-                             Condtq q);
-__global__ void k_scalars_bud_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
-                                 Budget b, Condtq q);
-__global__ void k_update_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
-                            Fields fs, int mnx, int mny, int snx, int sny, int xcd, Condtq q);
-__global__ void k_update_bud_ct(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields fm,
-                                Fields fs, int mnx, int mny, int snx, int sny, int xcd, Budget b, Condtq q);
+                         int mnx, int mny, int snx, int sny, int xcd, B... b);
 __global__ void k_qfilter(Geom g, const Consts* __restrict__ c, Fields f);
 // the serial fix passes resolve the chain (qxcommon.hpp), k_negfix_post / k_qx_post apply the
 // filters of the points they fixed

@@ -364,12 +364,6 @@ constexpr int TC_NF = 5;
 // and pp back until the total of qc is known, adds condtq's increments (Main/mod_tendency.F90:
 // 336-349; condtq.hpp) before the Rayleigh damping of t and qv (:356-364), and then stores the
 // exports and forms the forecasts.
-__device__ __forceinline__ const Budget& budget_arg(const Budget& b) { return b; }
-__device__ __forceinline__ const Budget& budget_arg(const Budget& b, const Condtq&) { return b; }
-__device__ __forceinline__ const Condtq& condtq_arg(const Condtq& q) { return q; }
-__device__ __forceinline__ const Condtq& condtq_arg(const Budget&, const Condtq& q) { return q; }
-template <class T, class... B>
-constexpr bool pack_has = (std::is_same<T, B>::value || ...);
 template <bool QX, class... B>
 __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* __restrict__ c,
                                                    const StepState* __restrict__ s, NHFields f, int wdiag,
@@ -592,7 +586,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
   // budget: var 0 t, 1 qv; term 0 adh, 1 adv, 2 adi, 3 bdy, 4 dif
   auto bud = [&](int var, int term, double after, double before) {
     if constexpr (BUD) {
-      const Budget& bb = budget_arg(b...);
+      const Budget bb = pack_get<Budget>(b...);
       double* acc = var ? bb.q[term] : bb.t[term];
       F3(acc, j, i, k) = F3(acc, j, i, k) + (after - before) * bb.rw;
     }
@@ -713,7 +707,7 @@ __global__ __launch_bounds__(TCT, TC_W) void k_nh_tend_c(Geom g, const Consts* _
       // core is atm0's (sfs%psc points to sfs%psa, Main/mod_atm_interface.F90:890), pres from the
       // total of pp before its Rayleigh damping (:415-416), qs = atms%qsb3d of the step's start
       // as mkslice forms it (k_slice: pb3d with its k = 1 floor)
-      const Condtq& q = condtq_arg(b...);
+      const Condtq q = pack_get<Condtq>(b...);
       const double t2 = F3(f.a2t, j, i, k), qv2 = F3(f.a2qv, j, i, k), qc2 = F3(f.a2qc, j, i, k);
       const double rpb = F2(f.rpsb, j, i);
       const double pres = F3(f.pr0, j, i, k) + (F3(f.a2pp, j, i, k) + dt * pth) / ps;

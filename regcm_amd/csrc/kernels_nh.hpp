@@ -83,7 +83,7 @@ __global__ void k_nh_diffu6(Geom g, const Consts* __restrict__ c, NHFields f, Qx
 __global__ void k_nh_decouple(Geom g, const Consts* __restrict__ c, NHFields f);
 __global__ void k_nh_omega(Geom g, const Consts* __restrict__ c, NHFields f);
 __global__ void k_nh_coeff_raw(Geom g, const Consts* __restrict__ c, NHFields f);
-// B: empty (the default instance), or Budget (kernels.hpp): the budget instance of rcmdyn_set_budget
+// B: the extra argument blocks (kernels.hpp): empty, Budget, and for QX = false Condtq or Budget, Condtq
 template <bool QX, class... B>
 __global__ void k_nh_tend_c(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, NHFields f, int wdiag, int istep, B... b);
 __global__ void k_nh_tend_d(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, NHFields f, int istep);

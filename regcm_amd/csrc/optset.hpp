@@ -1,11 +1,11 @@
 // optset.hpp -- which instance of a hydrostatic tendency kernel a launch takes.  Host only, no
 // HIP: the engine includes it, and a stand-alone host program can (tests/test_optset_cpu.py).
 //
-// k_momentum, k_scalars and k_update exist twice (kernels.hip): the generic instance
-// reads every model option at run time (Consts, the optional pointers of Fields); the
-// default-set instance was compiled for the options of the configurations C1-C4 and holds no
-// code, pointer or register of any alternative (the policies OptGeneric / OptDefault,
-// pointops.hpp).  optset_instance() is evaluated where a launch is issued, on the configuration
+// k_momentum, k_scalars and k_update are templates on an option policy (kernels.hpp; the
+// policies OptGeneric / OptDefault, pointops.hpp): the generic instance reads every model option
+// at run time (Consts, the optional pointers of Fields); the default-set instance was compiled
+// for the options of the configurations C1-C4 and holds no code, pointer or register of any
+// alternative.  The instances with an extra argument block (Budget, Condtq) are generic.  optset_instance() is evaluated where a launch is issued, on the configuration
 // and the very pointers that launch passes, so a captured graph holds the instance that matches
 // its arguments; attaching the physics seam, the budget, an export or kpbl invalidates the
 // graphs (engine.hip) and the next capture selects again.

@@ -1,8 +1,9 @@
 """Cost of the SUBEX condensation inside tend (rcmdyn_set_condtq): graph-replayed ms/step of two
 engines from one state, one with condtq off and one with it on, timed in alternating blocks, then
-the per-kernel times of both (rcmdyn_kernel_times).  The switch selects the generic condtq
-instances of the tendency kernels (k_update / k_nh_tend_c), so their time "on" against "off" is
-that instance against the default-set one where the configuration takes it.  The step time also
+the per-kernel times of both (rcmdyn_kernel_times).  The switch selects the condtq instances of
+the tendency kernels (k_update<OptGeneric, Condtq> / k_nh_tend_c<false, Condtq>, reported under the
+kernels' plain names), so their time "on" against "off" is that instance against the default-set
+one (k_update<OptDefault>) where the configuration takes it.  The step time also
 holds what condtq does to the state: every evaporated cloud leaves qc forecasts of rounding noise
 of either sign, and the negative ones go through the negative-moisture fix, whose dependent
 points are resolved serially in the reference's sweep order (k_split_project / k_split_correct,

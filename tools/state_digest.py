@@ -1,7 +1,9 @@
 """One sha256 per named case over the raw bytes of the state and the tendency diagnostics after
 bdyval() and step(3) from the seeded state of regcm_amd/icbc.py: the bit-for-bit check of a
 kernel refactor.  Run it once under each engine library (RCMDYN_LIB) and compare the outputs
-line by line.
+line by line.  The cases with the tendency budget or condtq on (the instance switches of the
+tendency kernels, each alone and together, fused and as two launches, on a decomposed tile and
+in both cores) also hash the budget terms and the condensation increments.
 
     RCMDYN_LIB=varlib/var_parent.so python tools/state_digest.py > parent.txt
     RCMDYN_LIB=varlib/var_new.so    python tools/state_digest.py > new.txt
@@ -18,11 +20,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from regcm_amd import icbc  # noqa: E402
 from regcm_amd.config import (CONFIGS, NH_STATE_FIELDS, QX_STATE_FIELDS, STATE_FIELDS,  # noqa: E402
                               TKE_STATE_FIELDS)
-from regcm_amd.dycore import DynCore  # noqa: E402
+from regcm_amd.dycore import BUDGET_TERMS, DynCore  # noqa: E402
 
 TEND_DIAG = ["TTEN", "UTEN", "VTEN", "QVTEN", "QCTEN", "OMEGA", "XKC"]
 
-# (name, base config, RunConfig overrides, environment switches, local tiles)
+# (name, base config, RunConfig overrides, environment switches, local tiles[, instance switches])
 CASES = [("C1", "C1", {}, {}, (1, 1))]
 CASES += [(f"C1 {k}={v}", "C1", {k: v}, {}, (1, 1))
           for k, v in (("iboudy", 1), ("iboudy", 4), ("idiffu", 2), ("idiffu", 3), ("isladvec", 1),
@@ -47,9 +49,22 @@ CASES += [
     ("N1 2x2", "N1", {}, {}, (2, 2)),
     ("CRM", "CRM", {}, {}, (1, 1)),
 ]
+# the instance switches of the tendency kernels: every rung of the engine's selector
+NO_FUSE = {"RCMDYN_NO_FUSE_UPDATE": "1"}
+for sw in (("budget",), ("condtq",), ("budget", "condtq")):
+    CASES += [(f"C1 {'+'.join(sw)}", "C1", {}, {}, (1, 1), sw),
+              (f"C1 {'+'.join(sw)} NO_FUSE_UPDATE", "C1", {}, NO_FUSE, (1, 1), sw)]
+# (the tendency diagnostics make every case above generic: "nodiag" takes the default-set instances)
+CASES += [("C1 nodiag", "C1", {}, {}, (1, 1), ("nodiag",)),
+          ("C1 nodiag NO_FUSE_UPDATE", "C1", {}, NO_FUSE, (1, 1), ("nodiag",)),
+          ("C1 NO_OPTSET", "C1", {}, {"RCMDYN_NO_OPTSET": "1"}, (1, 1)),
+          ("C1 budget+condtq 2x2", "C1", {}, {}, (2, 2), ("budget", "condtq"))]
+CASES += [(f"N1 {'+'.join(sw)}", "N1", {}, {}, (1, 1), sw)
+          for sw in (("budget",), ("condtq",), ("budget", "condtq"))]
+CASES += [("N1 ipptls=2 budget", "N1", {"ipptls": 2}, {}, (1, 1), ("budget",))]
 
 
-def digest(base, over, env, tiles):
+def digest(base, over, env, tiles, switches=()):
     rc = dataclasses.replace(CONFIGS[base], **over)
     gen = icbc.generate_crm if rc.i_crm else icbc.generate_nh if rc.idynamic == 2 else icbc.generate
     data = gen(rc)
@@ -73,21 +88,34 @@ def digest(base, over, env, tiles):
         for k in env:
             del os.environ[k]
     e.put_state(st)
-    e.set_diagnostics(True)
+    e.set_diagnostics("nodiag" not in switches)
+    if "budget" in switches:
+        e.set_budget(True)
+    if "condtq" in switches:
+        e.set_condtq(True, 1.0)
+        e.put_rh0adj(np.random.Generator(np.random.PCG64(icbc.SEED)).uniform(0.0, 0.99999, (rc.kz, rc.iy, rc.jx)))
     e.bdyval()
     e.step(3)
     e.synchronize()
     h = hashlib.sha256()
-    for n in names + TEND_DIAG:
+    for n in names + (TEND_DIAG if "nodiag" not in switches else []):
         h.update(n.encode())
         h.update(np.ascontiguousarray(e.get(n)).tobytes())
+    if "budget" in switches:
+        for n in BUDGET_TERMS:
+            h.update(n.encode())
+            h.update(e.get_budget(n).tobytes())
+    if "condtq" in switches:
+        for n in ("T", "QV", "QC"):
+            h.update(n.encode())
+            h.update(e.get_condtq(n).tobytes())
     e.close()
     return h.hexdigest()
 
 
 def main():
-    for name, base, over, env, tiles in CASES:
-        print(f"{name:28s} {digest(base, over, env, tiles)}", flush=True)
+    for name, *case in CASES:
+        print(f"{name:28s} {digest(*case)}", flush=True)
 
 
 if __name__ == "__main__":
