@@ -141,10 +141,12 @@ typedef struct rcmdyn_config {
    * rows relax to the boundary data (Main/mod_atm_interface.F90:435-457).  A put fills a band
    * tile's frame columns past either end of the period from the wrapped columns.  Refused for
    * idynamic = 2 and for values other than 0 and 1.
-   * Options of the reference that this engine does not compute; a non-zero value is refused
-   * at rcmdyn_create ('not supported'): i_crm = 1 (cloud-resolving, periodic in j and i,
-   * Main/mpplib/mod_mppparam.F90:1063, 1132, 1224-1257); ichem = 1 (chemical tracers advected,
-   * diffused and nudged by tend, Main/mod_tendency.F90:164, 198, 275, 548, 873). */
+   * i_crm = 1 (cloud-resolving, periodic in j and i, Main/mpplib/mod_mppparam.F90:1063, 1132,
+   * 1224-1257): the non-hydrostatic core over the band only.
+   * ichem: this struct carries no tracer count, so a non-zero value is refused at rcmdyn_create;
+   * the chemical tracers that tend advects, diffuses, relaxes, forecasts, fixes and filters
+   * (Main/mod_tendency.F90:164, 198, 275, 548, 873) are declared after create with
+   * rcmdyn_set_tracers (below), with ichem = 0 here. */
   int32_t i_band, i_crm, ichem;
 } rcmdyn_config;
 
@@ -456,6 +458,55 @@ int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src,
                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
 int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst,
                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+
+/* Chemical and aerosol tracers (the reference's ichem = 1): the chi chain of tend and bdyval on
+ * the device.  tend decouples (atmx%chi = atm1%chi * rpsa, no floor), advects (hadvtr; vadv4d
+ * with itrvadv = 2, threshold mintr * ps, or 3 under ibltyp = 2 with iuwvadv = 1), relaxes
+ * (nudge_chiten, iboudy 1 or 5), diffuses (diffu_x on chib3d), sums with chiphy, forecasts,
+ * fixes negative values (0.1 * the mean of the nine |chi|, serially in the reference's order)
+ * and filters (RAW, gnu2, 0.53, zero floor) every tracer on the step's own mass fluxes, qdot and
+ * xkc (Main/mod_tendency.F90:548-586, 1027-1032, 1393-1412, 1502-1512, 1539-1543); bdyval runs
+ * chem_bdyval_coupled (Main/chemlib/mod_che_bdyco.F90:565-758).  Tracers are passive: no other
+ * field of the step reads them.  The chemistry itself (sources, deposition, the gas-phase
+ * mechanism, cumulus transport) stays the host's and enters as the pc_physic tendency TR_PHY.
+ *
+ * Fields of one tracer, coupled with p* like qc, kz levels, cross points:
+ *   TR_ATM1, TR_ATM2   chia, chib (put and get; part of the SAV state)
+ *   TR_PHY             chiphy (put only; persistent, zero until put)
+ *   TR_B0, TR_BT       chib0, chibt as che_init_bdy / chem_bdyin leave them (put and get); the
+ *                      host puts them at each boundary interval
+ *   TR_CHIB3D          mkslice's chib3d = max(chib / psb, 0) (get only; filled by
+ *                      rcmdyn_tend_pre_physics, Main/mod_slice.F90:196-200) */
+enum rcmdyn_tracer_field {
+  RCMDYN_TR_ATM1 = 0, RCMDYN_TR_ATM2, RCMDYN_TR_PHY, RCMDYN_TR_B0, RCMDYN_TR_BT, RCMDYN_TR_CHIB3D,
+  RCMDYN_NTRFIELDS
+};
+/* The most tracers one engine carries: above the reference's largest chemsimtype preset (52,
+ * Main/chemlib/mod_che_common.F90:269-397).  The bound only sizes host tables. */
+#define RCMDYN_MAXTR 96
+/* Declares ntr tracers (ntr = 0: switches the family off and frees its buffers; the state of
+ * the tracers is lost).  Goes through the engine's state machine like rcmdyn_set_condtq: pending
+ * work is flushed, the device is waited for and the captured graphs are dropped.  A call that
+ * repeats the current ntr keeps the buffers.  Refused, the family staying as it was, for
+ *   ntr < 0 or ntr > RCMDYN_MAXTR;
+ *   ichebdy != 1: the ichebdy = 0 relaxation indexes tile-local rows (Main/chemlib/
+ *     mod_che_bdyco.F90:808-896), so its result depends on the decomposition; not built;
+ *   idiffu = 3: the tracers have no sixth-order column planes;
+ *   isladvec = 1: slhadv_x of chi is not built. */
+int rcmdyn_set_tracers(rcmdyn_t* h, int32_t ntr, int32_t ichebdy);
+/* One field (enum rcmdyn_tracer_field) of tracer itr = 1..ntr; layout, bounds and box rules as in
+ * rcmdyn_put / rcmdyn_get, a band's wrapped frame columns included.  Refused before
+ * rcmdyn_set_tracers (or after ntr = 0), for itr out of range, for a put of TR_CHIB3D, a get of
+ * TR_PHY, and a get of TR_CHIB3D before the first rcmdyn_tend_pre_physics. */
+int rcmdyn_put_tracer(rcmdyn_t* h, int32_t field, int32_t itr, const double* src,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_get_tracer(rcmdyn_t* h, int32_t field, int32_t itr, double* dst,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+/* nudge_chiten's tables cefc(ib, k) and cegc(ib, k), ib = 1..nspgx, k = 1..kz, Fortran order (ib
+ * fastest).  The reference allocates them (Main/chemlib/mod_che_bdyco.F90:110-111) and assigns
+ * them nowhere, so its tracer relaxation adds zero: both start at zero here and stay so until
+ * put.  Read only for iboudy 1 and 5 (Main/mod_tendency.F90:1506). */
+int rcmdyn_put_tracer_nudge(rcmdyn_t* h, const double* cefc, const double* cegc);
 
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every

@@ -104,6 +104,11 @@ FIELD_NAMES = [
     "QIPHY", "QRPHY", "QSPHY", "ATMS_QXB3D_QI", "ATMS_QXB3D_QR", "ATMS_QXB3D_QS",
 ]
 FIELD = {n: i for i, n in enumerate(FIELD_NAMES)}
+# Fields of one chemical tracer, enum rcmdyn_tracer_field (same order): chia, chib, chiphy,
+# chib0, chibt and the mkslice export chib3d, each coupled with p* on kz levels
+TRACER_FIELDS = ["ATM1", "ATM2", "PHY", "B0", "BT", "CHIB3D"]
+TRACER_FIELD = {n: i for i, n in enumerate(TRACER_FIELDS)}
+MAXTR = 96           # RCMDYN_MAXTR
 TWO_D = {"PSA", "PSB", "MSFX", "MSFD", "CORIOL", "HT", "XPSB_B0", "XPSB_BT", "PSC",
          "PTEN", "PSDOTA", "ATM0_PS", "DPSDXM", "DPSDYM", "EF", "DDX", "DDY", "DMDX", "DMDY",
          "EX", "CRX", "CRY", "ATMS_PS2D", "ATMS_RHOX2D", "XPSB_B1", "ATM0_PSDOT", "KPBL"}

@@ -245,7 +245,9 @@ enum class FK {
   // nqx = 5: the hydrometeors beyond qc (qi, qr, qs), each kind in species order
   A1QX0, A1QX1, A1QX2, A2QX0, A2QX1, A2QX2, CQX0, CQX1, CQX2, SLQX0, SLQX1, SLQX2, D6QX0, D6QX1, D6QX2,
   // iuwvadv = 1: the PBL-top level (2-D)
-  KPBL
+  KPBL,
+  // chemical tracers (rcmdyn_set_tracers): chia, chib, the forecast, chib0, chibt of tracer XField::n
+  TRA1, TRA2, TRCQ, TRB0, TRBT
 };
 inline FK fkq(FK base, int n) { return (FK)((int)base + n); }
 
@@ -647,7 +649,7 @@ struct rcmdyn_engine {
     // halo staging: 8 directions x widest exchange (the hydrostatic prologue: 5 fields 2 wide
     // + 5 fields 3 wide + p*; at most 32 field-widths of kz+1 levels; nqx = 5 adds 3 fields 2
     // wide + 3 fields 3 wide)
-    staging_cap = std::max<long>(staging_cap, 8L * (std::max(g.nj, g.ni) + 2 * G) * (32 + 16 * (hc.nsp > 0)) * (kz + 1));
+    staging_cap = std::max<long>(staging_cap, staging_need(g, 0));
     t.sbuf = dalloc(t, staging_cap);
     t.rbuf = dalloc(t, staging_cap);
     if (halo) {
@@ -785,7 +787,8 @@ struct rcmdyn_engine {
                     {(const void*)k_scalars<OptGeneric>, SBT, "k_scalars<OptGeneric>"},
                     {(const void*)k_update<OptGeneric, Budget>, SBT, "k_update<OptGeneric, Budget>"},
                     {(const void*)k_scalars<OptGeneric, Budget>, SBT, "k_scalars<OptGeneric, Budget>"},
-                    {(const void*)k_qx_tend, QBT, "k_qx_tend"}};
+                    {(const void*)k_qx_tend<FamQx>, QBT, "k_qx_tend<FamQx>"},
+                    {(const void*)k_qx_tend<FamTr>, QBT, "k_qx_tend<FamTr>"}};
     for (const K& k : ks) {
       hipFuncAttributes a{};
       HIPCHK(hipFuncGetAttributes(&a, k.f));
@@ -851,7 +854,9 @@ struct rcmdyn_engine {
       throw std::runtime_error("rcmdyn: i_crm = 1 is built for the non-hydrostatic core over the band (i_band = 1)");
     if (cfg.i_band != 0 && cfg.idynamic == 2 && cfg.idiffu == 3)
       throw std::runtime_error("rcmdyn: idiffu = 3 on the non-hydrostatic band / CRM is not supported");
-    if (cfg.ichem != 0) throw std::runtime_error("rcmdyn: ichem = 1 (chemical tracers) is not supported");
+    if (cfg.ichem != 0)
+      throw std::runtime_error("rcmdyn: ichem = 1 is not supported in rcmdyn_config, which carries no tracer count: create "
+                               "with ichem = 0 and declare the chemical tracers with rcmdyn_set_tracers");
     if (const char* m = std::getenv("RCMDYN_RCCL_CHAN2"))   // the removed second-communicator modes
       if (std::string(m) != "one") throw std::runtime_error("rcmdyn: RCMDYN_RCCL_CHAN2 must be one (or unset)");
     // dynparam's upstream_mode (default .true., Main/mod_params.F90:646); .false. runs the
@@ -948,6 +953,7 @@ struct rcmdyn_engine {
     if (hflags) (void)hipHostFree(hflags);
     if (hgerr) (void)hipHostFree(hgerr);
     if (derr) (void)hipFree(derr);
+    free_tracers();
     for (auto& t : tiles)
       for (void* p : t.allocs) (void)hipFree(p);
     tiles.clear();
@@ -1055,8 +1061,14 @@ struct rcmdyn_engine {
 
 
   // ------------------------------------------------------------------ field access
-  double* fptr(Tile& t, FK f) {
+  double* fptr(Tile& t, FK f, int n = 0) {
     const int c = t.cur, q = thp(t);
+    const int tc = cfg.idynamic == 2 ? 0 : c;        // the tracers' parity (the NH core: in place)
+    switch (f) {
+      case FK::TRA1: return t.tra1[tc][n]; case FK::TRA2: return t.tra2[tc][n]; case FK::TRCQ: return t.trcq[n];
+      case FK::TRB0: return t.trb0[n]; case FK::TRBT: return t.trbt[n];
+      default: break;
+    }
     switch (f) {
       case FK::A1U: return t.a1u[c]; case FK::A1V: return t.a1v[c]; case FK::A1T: return t.a1t[q];
       case FK::A1QV: return t.a1qv[q]; case FK::A1QC: return t.a1qc[q];
@@ -1378,6 +1390,7 @@ struct rcmdyn_engine {
       for (int n = 0; n < hc.nsp; n++) { a.a2qx[n] = t.a2qx[n][c]; a.qxb3d[n] = t.atmsx[n]; }
       KLAUNCH(k_slice, grid3(g.jde2 - g.jde1 + 1, g.ide2 - g.ide1 + 1, 1), BLK, 0, stream, g, dc, a);
     });
+    tracer_slice();
   }
 
   void get(int f, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
@@ -1513,6 +1526,229 @@ struct rcmdyn_engine {
     }
   }
 
+  // ------------------------------------------------------------------ chemical tracers
+  // The chi chain of tend and bdyval (rcmdyn_set_tracers; species.hip's FamTr instances).  The
+  // family is declared after create, like the budget and condtq: the count is no field of
+  // rcmdyn_config.  Its buffers are the tiles' (Tile::tra1 ..), the two relaxation tables the
+  // engine's; the groups' argument tables are kernel inputs in device memory, so a put writes
+  // buffers the captured graphs already point to and only a new count or a new table state (zero
+  // or not) drops the graphs (the slice runs eagerly, from rcmdyn_tend_pre_physics alone).
+  int ntr = 0;
+  bool tr_bdy_dirty = false;          // chib0 / chibt put since the last tend: their ghost rings are stale
+  bool tr_relax = false;              // a cefc / cegc entry is non-zero
+  double *tr_cefc = nullptr, *tr_cegc = nullptr;
+  int tr_groups() const { return (ntr + NQXH - 1) / NQXH; }
+  TrArgs tr_args(Tile& t) {
+    TrArgs a{};
+    a.tab = static_cast<const QxArgs*>(t.trtab[cfg.idynamic == 2 ? 0 : t.cur]);
+    a.cefc = tr_cefc; a.cegc = tr_cegc;
+    a.ngroups = tr_groups();
+    a.relax = (int)(tr_relax && (cfg.iboudy == 1 || cfg.iboudy == 5));     // Main/mod_tendency.F90:1506
+    return a;
+  }
+  // the halo staging of a tile's widest grouped exchange, 8 directions: the hydrostatic prologue's
+  // 31 (nqx = 5: 46) field-widths of at most kz + 1 levels (setup_tile), and 5 more per tracer
+  // (atm1 2 wide, atm2 3 wide; rcmdyn_set_tracers)
+  long staging_need(const Geom& g, int ntracers) const {
+    return 8L * (std::max(g.nj, g.ni) + 2 * G) * (32 + 16 * (hc.nsp > 0) + 5 * ntracers) * (cfg.kz + 1);
+  }
+  void grow_staging(int ntracers) {
+    if (!halo) return;
+    long need = staging_cap;
+    for (auto& t : tiles) need = std::max(need, staging_need(t.g, ntracers));
+    if (need <= staging_cap) return;
+    staging_cap = need;
+    for (auto& t : tiles)
+      for (double** b : {&t.sbuf, &t.rbuf, &t.sbuf2, &t.rbuf2}) {
+        if (!*b) continue;
+        t.allocs.erase(std::find(t.allocs.begin(), t.allocs.end(), (void*)*b));
+        HIPCHK(hipFree(*b));
+        *b = dalloc(t, staging_cap);
+      }
+  }
+  void free_tracers() {
+    for (auto& t : tiles) {
+      for (void* p : t.tr_allocs) (void)hipFree(p);
+      t.tr_allocs.clear();
+      for (auto* v : {&t.tra1[0], &t.tra1[1], &t.tra2[0], &t.tra2[1], &t.trcq, &t.trfq, &t.trphy, &t.trb0, &t.trbt,
+                      &t.trs3d})
+        v->clear();
+      t.trdep = t.trdepf = nullptr;
+      t.trtab[0] = t.trtab[1] = nullptr;
+      t.trsout = nullptr;
+    }
+    if (tr_cefc) (void)hipFree(tr_cefc);
+    if (tr_cegc) (void)hipFree(tr_cegc);
+    tr_cefc = tr_cegc = nullptr;
+    tr_relax = false;
+    ntr = 0;
+  }
+  template <class T>
+  T* tr_alloc(Tile& t, size_t n) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, n * sizeof(T)));
+    t.tr_allocs.push_back(p);
+    HIPCHK(hipMemset(p, 0, n * sizeof(T)));
+    return (T*)p;
+  }
+  void set_tracers(int n, int ichebdy) {
+    if (n < 0 || n > RCMDYN_MAXTR)
+      throw std::runtime_error("rcmdyn_set_tracers: ntr must lie in 0 .. RCMDYN_MAXTR = " + std::to_string(RCMDYN_MAXTR));
+    if (n > 0) {
+      if (ichebdy != 1)
+        throw std::runtime_error("rcmdyn_set_tracers: ichebdy must be 1 (the ichebdy = 0 relaxation indexes tile-local "
+                                 "rows, Main/chemlib/mod_che_bdyco.F90:808-896: its result depends on the decomposition)");
+      if (cfg.idiffu == 3)
+        throw std::runtime_error("rcmdyn_set_tracers: idiffu = 3 is not built for tracers (no sixth-order column planes of chi)");
+      if (cfg.isladvec == 1)
+        throw std::runtime_error("rcmdyn_set_tracers: isladvec = 1 is not built for tracers (slhadv_x of chi)");
+    }
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    if (n == ntr) return;
+    invalidate_graphs();
+    free_tracers();
+    if (n == 0) return;
+    try {
+      grow_staging(n);
+      const int kz = cfg.kz, ng = (n + NQXH - 1) / NQXH, npar = cfg.idynamic == 2 ? 1 : 2;
+      HIPCHK(hipMalloc((void**)&tr_cefc, sizeof(double) * cfg.nspgx * kz));
+      HIPCHK(hipMalloc((void**)&tr_cegc, sizeof(double) * cfg.nspgx * kz));
+      HIPCHK(hipMemset(tr_cefc, 0, sizeof(double) * cfg.nspgx * kz));
+      HIPCHK(hipMemset(tr_cegc, 0, sizeof(double) * cfg.nspgx * kz));
+      for (auto& t : tiles) {
+        const Geom& g = t.g;
+        const size_t P3 = (size_t)g.plane * kz;
+        const int R = g.ici2 - g.ici1 + 1;
+        for (int q = 0; q < n; q++) {
+          for (int b = 0; b < npar; b++) {
+            t.tra1[b].push_back(tr_alloc<double>(t, P3));
+            t.tra2[b].push_back(tr_alloc<double>(t, P3));
+          }
+          t.trcq.push_back(tr_alloc<double>(t, P3)); t.trfq.push_back(tr_alloc<double>(t, P3));
+          t.trphy.push_back(tr_alloc<double>(t, P3));
+          t.trb0.push_back(tr_alloc<double>(t, P3)); t.trbt.push_back(tr_alloc<double>(t, P3));
+          t.trs3d.push_back(nullptr);
+        }
+        t.trdep = tr_alloc<unsigned>(t, (size_t)ng * NQXH * kz * negfix_rowwords(g));
+        t.trdepf = tr_alloc<unsigned>(t, (size_t)ng * NQXH * kz * R);
+        t.trsout = tr_alloc<double*>(t, n);
+        for (int b = 0; b < npar; b++) {
+          std::vector<QxArgs> tab(ng);
+          for (int gq = 0; gq < ng; gq++) {
+            QxArgs& q = tab[gq];
+            q = QxArgs{};
+            q.nsp = std::min(NQXH, n - gq * NQXH);
+            for (int m = 0; m < q.nsp; m++) {
+              const int x = gq * NQXH + m, o = npar == 1 ? b : 1 - b;
+              q.a1[m] = t.tra1[b][x]; q.a2[m] = t.tra2[b][x];
+              q.b1[m] = t.tra1[o][x]; q.b2[m] = t.tra2[o][x];
+              q.cq[m] = t.trcq[x]; q.fq[m] = t.trfq[x]; q.phy[m] = t.trphy[x];
+              q.b0[m] = t.trb0[x]; q.bt[m] = t.trbt[x];
+            }
+            q.dep = t.trdep + (size_t)gq * NQXH * kz * negfix_rowwords(g);
+            q.depf = t.trdepf + (size_t)gq * NQXH * kz * R;
+          }
+          t.trtab[b] = tr_alloc<QxArgs>(t, ng);
+          HIPCHK(hipMemcpy(t.trtab[b], tab.data(), sizeof(QxArgs) * ng, hipMemcpyHostToDevice));
+        }
+      }
+      ntr = n;
+    } catch (...) {
+      free_tracers();
+      throw;
+    }
+    ghosts_stale = true;
+  }
+  // the buffer of one tracer field on tile t (TR_CHIB3D: null before the first slice)
+  double* tracer_ptr(Tile& t, int field, int x) {
+    const int c = cfg.idynamic == 2 ? 0 : t.cur;
+    switch (field) {
+      case RCMDYN_TR_ATM1: return t.tra1[c][x]; case RCMDYN_TR_ATM2: return t.tra2[c][x];
+      case RCMDYN_TR_PHY: return t.trphy[x]; case RCMDYN_TR_B0: return t.trb0[x]; case RCMDYN_TR_BT: return t.trbt[x];
+      case RCMDYN_TR_CHIB3D: return t.trs3d[x];
+      default: return nullptr;
+    }
+  }
+  void tracer_check(const char* who, int field, int itr) const {
+    if (ntr == 0) throw std::runtime_error(std::string(who) + ": no tracers are declared (rcmdyn_set_tracers)");
+    if (field < 0 || field >= RCMDYN_NTRFIELDS) throw std::runtime_error(std::string(who) + ": unknown tracer field");
+    if (itr < 1 || itr > ntr)
+      throw std::runtime_error(std::string(who) + ": itr must lie in 1 .. ntr = " + std::to_string(ntr));
+  }
+  void put_tracer(int field, int itr, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+    tracer_check("rcmdyn_put_tracer", field, itr);
+    if (field == RCMDYN_TR_CHIB3D) throw std::runtime_error("rcmdyn_put_tracer: TR_CHIB3D is read-only (the mkslice export)");
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
+    for (auto& t : tiles) scatter_box(t, tracer_ptr(t, field, itr - 1), cfg.kz, src, j1, j2, i1, i2, k1, k2);
+    if (field == RCMDYN_TR_B0 || field == RCMDYN_TR_BT) tr_bdy_dirty = true;
+    else ghosts_stale = true;
+  }
+  void get_tracer(int field, int itr, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    tracer_check("rcmdyn_get_tracer", field, itr);
+    if (field == RCMDYN_TR_PHY) throw std::runtime_error("rcmdyn_get_tracer: TR_PHY is put-only (the host's chiphy)");
+    settle();
+    if (field == RCMDYN_TR_CHIB3D && !tiles.empty() && !tiles[0].trs3d[itr - 1])
+      throw std::runtime_error("rcmdyn_get_tracer: no slice fields yet (rcmdyn_tend_pre_physics)");
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      gather_box(t, tracer_ptr(t, field, itr - 1), cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
+    }
+  }
+  void put_tracer_nudge(const double* cefc, const double* cegc) {
+    if (ntr == 0) throw std::runtime_error("rcmdyn_put_tracer_nudge: no tracers are declared (rcmdyn_set_tracers)");
+    if (!cefc || !cegc) throw std::runtime_error("rcmdyn_put_tracer_nudge: null table");
+    const size_t n = (size_t)cfg.nspgx * cfg.kz;
+    bool nz = false;
+    for (size_t q = 0; q < n; q++) {
+      if (!std::isfinite(cefc[q]) || !std::isfinite(cegc[q]))
+        throw std::runtime_error("rcmdyn_put_tracer_nudge: the tables must be finite");
+      nz = nz || cefc[q] != 0.0 || cegc[q] != 0.0;
+    }
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(tr_cefc, cefc, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(tr_cegc, cegc, n * sizeof(double), hipMemcpyHostToDevice));
+    if (nz != tr_relax) invalidate_graphs();         // the term's switch is a kernel argument
+    tr_relax = nz;
+  }
+  // tend's tracer launches after the forecast's exchange: the fix and filter, the serial chains
+  void tracer_fix(Tile& t) {
+    const Geom& g = t.g;
+    const int kz = cfg.kz, ng = tr_groups();
+    KLAUNCH_AS("k_tr_fix", k_qx_fix<FamTr>, grid3(g.jdx2() - g.jdx1() + 1, g.idx2() - g.idx1() + 1, ng * kz), BLK, 0,
+               stream, g, dc, tr_args(t));
+    KLAUNCH_AS("k_tr_serial", k_qx_serial<FamTr>, dim3(ng * NQXH * kz), dim3(negfix_threads(g)),
+               sizeof(double) * negfix_lds(g), stream, g, dc, tr_args(t));
+    KLAUNCH_AS("k_tr_post", k_qx_post<FamTr>, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, ng * NQXH * kz), BLK, 0,
+               stream, g, dc, tr_args(t));
+  }
+  // chem_bdyval_coupled of every tile; integ / pre_clock as k_bdyval_chi
+  void tracer_bdyval(int integ, int pre_clock) {
+    if (!ntr) return;
+    each([&](Tile& t) {
+      KLAUNCH(k_bdyval_chi, dim3(cfg.kz, ntr), dim3(256), 0, stream, t.g, ds, tr_args(t), ntr, integ, pre_clock,
+              cfg.dtsec);
+    });
+  }
+  // mkslice's chib3d (run_slice)
+  void tracer_slice() {
+    if (!ntr) return;
+    for (auto& t : tiles) {
+      if (t.trs3d[0]) continue;
+      for (int q = 0; q < ntr; q++) t.trs3d[q] = tr_alloc<double>(t, (size_t)t.g.plane * cfg.kz);
+      HIPCHK(hipMemcpy(t.trsout, t.trs3d.data(), sizeof(double*) * ntr, hipMemcpyHostToDevice));
+    }
+    each([&](Tile& t) {
+      const Geom& g = t.g;
+      KLAUNCH(k_tr_slice, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, ntr * cfg.kz), BLK, 0, stream, g, cfg.kz, ntr,
+              tr_args(t), t.rpsb, t.trsout);
+    });
+  }
+
   // Mass check of tend (Main/mod_massck.F90:190-306): the switch, the launches tend issues after
   // its prologue exchange, and the host's read of the log.  The log's capacity is a kernel
   // argument, so the captured graphs are dropped when it or the switch changes.
@@ -1629,7 +1865,7 @@ struct rcmdyn_engine {
     int o = idx - cfg.tile_first;
     return (o >= 0 && o < (int)tiles.size()) ? &tiles[o] : nullptr;
   }
-  struct XField { FK f; int nk; int width = 0; int sides = -1; };  // 0/-1: the call's default
+  struct XField { FK f; int nk; int width = 0; int sides = -1; int n = 0; };  // 0/-1: the call's default; n: tracer
   // (j1,j2,i1,i2) of the box sent toward d (send) or received from d (recv)
   static void box(const Geom& g, int d, int w, bool send, int b[4]) {
     b[0] = g.jde1; b[1] = g.jde2; b[2] = g.ide1; b[3] = g.ide2;
@@ -1756,7 +1992,7 @@ struct rcmdyn_engine {
     }
     auto fn = [&](Tile& t, int d, bool send, std::vector<Seg>& v) {
       for (const XField& x : fs)
-        if (recv_dir(x.sides, send ? OPP[d] : d)) v.push_back(field_seg(t, fptr(t, x.f), x.nk, d, x.width, send));
+        if (recv_dir(x.sides, send ? OPP[d] : d)) v.push_back(field_seg(t, fptr(t, x.f, x.n), x.nk, d, x.width, send));
     };
     auto all = [](int) { return true; };
     exchange_generic(fn, all, all);
@@ -1953,6 +2189,15 @@ struct rcmdyn_engine {
       bdy_dirty = false;
       invalidate_graphs();
     }
+    if (tr_bdy_dirty) {
+      // chib0 / chibt as the b0 / bt of the other families: the relaxation reads them one point
+      // out of the ghost-ring points it runs at
+      std::vector<XField> v;
+      add_tr(v, FK::TRB0, cfg.kz, 2);
+      add_tr(v, FK::TRBT, cfg.kz, 2);
+      for (size_t a = 0; a < v.size(); a += 8) xchv(std::vector<XField>(v.begin() + a, v.begin() + std::min(v.size(), a + 8)));
+      tr_bdy_dirty = false;
+    }
     if (kpbl_dirty) {
       // the physics puts kpbl on its own points (a rank puts its interior); vadv4d ind = 3 of
       // the fused hydrostatic step reads it on the ghost ring k_scalars computes in place of
@@ -2058,7 +2303,7 @@ struct rcmdyn_engine {
     f.red = red; f.red_off = t.red_off;
     f.qfuse = qfuse() ? 1 : 0; f.negcnt = t.negcnt; f.neglist = t.neglist;
     for (int n = 0; n < hc.nsp; n++) f.qxa1[n] = t.a1qx[n][c];
-    if (hc.nsp) f.xkcs = t.xkcs;              // k_qx_tend's diffusion reads the scaled xkc
+    if (hc.nsp || ntr) f.xkcs = t.xkcs;       // k_qx_tend's diffusion reads the scaled xkc (the tracers' too)
     return f;
   }
 
@@ -2081,6 +2326,10 @@ struct rcmdyn_engine {
   // the XField entries of the hydrometeors beyond qc for one kind (A1QX0 ..), width w
   void add_qx(std::vector<XField>& v, FK base, int nk, int w) const {
     for (int n = 0; n < hc.nsp; n++) v.push_back({fkq(base, n), nk, w});
+  }
+  // the same of the declared tracers (TRA1 ..): they join the species' grouped exchanges
+  void add_tr(std::vector<XField>& v, FK kind, int nk, int w) const {
+    for (int n = 0; n < ntr; n++) v.push_back({kind, nk, w, -1, n});
   }
 
   // istep of sound (Main/mod_sound.F90:201-205) for the host time mirror
@@ -2133,6 +2382,8 @@ struct rcmdyn_engine {
     if (cfg.ibltyp == 2) { pro.push_back({FK::A1TKE, kp, 1}); pro2.push_back({FK::A2TKE, kp, wd}); }
     add_qx(pro, FK::A1QX0, kz, 1);
     add_qx(pro2, FK::A2QX0, kz, wq);
+    add_tr(pro, FK::TRA1, kz, 1);         // Main/mod_tendency.F90:874, 1087-1089
+    add_tr(pro2, FK::TRA2, kz, wq);
     fork_point();
     xchv(pro);
     fork_after_exchange();
@@ -2210,13 +2461,14 @@ struct rcmdyn_engine {
       if (hc.nsp) {
         // the hydrometeors beyond qc: their fix and RAW filter in place (they feed nothing
         // else of the step; k_nh_tend_c read atm1 for the water load before)
-        KLAUNCH(k_qx_fix, grid3(g.jdx2() - g.jdx1() + 1, g.idx2() - g.idx1() + 1, kz), BLK, 0, stream, g, dc,
-                qx_args(t));      // the column box, as the hydrostatic launch: its jci x ici fix
-        KLAUNCH(k_qx_serial, dim3(hc.nsp * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc,
-                qx_args(t));
-        KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
-                qx_args(t));
+        KLAUNCH_AS("k_qx_fix", k_qx_fix<FamQx>, grid3(g.jdx2() - g.jdx1() + 1, g.idx2() - g.idx1() + 1, kz), BLK, 0,
+                   stream, g, dc, qx_args(t));      // the column box, as the hydrostatic launch: its jci x ici fix
+        KLAUNCH_AS("k_qx_serial", k_qx_serial<FamQx>, dim3(hc.nsp * kz), dim3(negfix_threads(g)),
+                   sizeof(double) * negfix_lds(g), stream, g, dc, qx_args(t));
+        KLAUNCH_AS("k_qx_post", k_qx_post<FamQx>, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0,
+                   stream, g, dc, qx_args(t));
       }
+      if (ntr) tracer_fix(t);        // the tracers likewise, in place
       KLAUNCH(k_nh_negfix, dim3(1024), dim3(256), 0, stream, g, dc, f);
       KLAUNCH(k_nh_negfix_serial, dim3(2 * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc, f);
       // tend's time filters (tfuse = 0) with part A of the first acoustic sub-step (sound, :163-718)
@@ -2315,19 +2567,25 @@ struct rcmdyn_engine {
       if (budget) launch(budget_args(t));
       else launch();
       // the chains of qi, qr, qs after it on the same stream
-      KLAUNCH(k_nh_qx_tend, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0, stream, g, dc, ds, f,
-              qx_args(t));
+      KLAUNCH_AS("k_nh_qx_tend", k_nh_qx_tend<FamQx>, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, cfg.kz), BLK, 0,
+                 stream, g, dc, ds, f, qx_args(t));
     } else {
       with_extras(t, [&](auto... x) {
         constexpr auto kern = k_nh_tend_c<false, decltype(x)...>;
         KLAUNCH_AS("k_nh_tend_c<false>", kern, grid, blk, 0, stream, g, dc, ds, f, (int)diag, istep, x...);
       });
     }
+    // the tracers' chains after it on the same stream, a group of NQXH per z slice of kz levels
+    if (ntr)
+      KLAUNCH_AS("k_nh_tr_tend", k_nh_qx_tend<FamTr>,
+                 grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, tr_groups() * cfg.kz), BLK, 0, stream, g, dc, ds, f,
+                 tr_args(t));
   }
   // the forecasts exchanged after the tendency kernels (atmc%qx, :381)
   std::vector<XField> cq_fields() const {
     std::vector<XField> v{{FK::CQV, cfg.kz}, {FK::CQC, cfg.kz}};
     add_qx(v, FK::CQX0, cfg.kz, 1);
+    add_tr(v, FK::TRCQ, cfg.kz, 1);       // atmc%chi, Main/mod_tendency.F90:570
     return v;
   }
 
@@ -2349,6 +2607,7 @@ struct rcmdyn_engine {
       KLAUNCH(k_nh_bdyval_w1, dim3(1), dim3(256), 0, stream, g, nhfields(t));
     });
     xch_slices();
+    tracer_bdyval(-1, 0);                      // before the last tile's clock advance below
     for (size_t q = 0; q < tiles.size(); q++) {
       Tile& t = tiles[q];
       const int c = t.cur;
@@ -2397,6 +2656,8 @@ struct rcmdyn_engine {
                              {FK::A2QC, kz, 3}};
     add_qx(pro, FK::A1QX0, kz, 2);        // nqx = 5: qi, qr, qs with qc
     add_qx(pro2, FK::A2QX0, kz, 3);
+    add_tr(pro, FK::TRA1, kz, 2);         // the tracers, as the species
+    add_tr(pro2, FK::TRA2, kz, 3);
     // UW TKE: atm1 1 wide, atm2 idif wide (Main/mod_tendency.F90:871, 1079)
     if (cfg.ibltyp == 2) {
       pro.push_back({FK::A1TKE, kz + 1, 1});
@@ -2522,8 +2783,9 @@ struct rcmdyn_engine {
       // nqx = 5: the hydrometeors beyond qc, their forecast (and ring), then the fix and filter
       each([&](Tile& t) {
         const Geom& g = t.g;
-        KLAUNCH(k_qx_tend, dim3((g.jcx2() - g.jcx1() + QBJ) / QBJ, (g.icx2() - g.icx1() + QBI) / QBI, kz), dim3(QBT),
-                0, stream, g, dc, ds, fields(t), qx_args(t));
+        KLAUNCH_AS("k_qx_tend", k_qx_tend<FamQx>,
+                   dim3((g.jcx2() - g.jcx1() + QBJ) / QBJ, (g.icx2() - g.icx1() + QBI) / QBI, kz), dim3(QBT), 0, stream, g,
+                   dc, ds, fields(t), qx_args(t));
       });
       if (!fused) {
         std::vector<XField> cq;
@@ -2532,14 +2794,33 @@ struct rcmdyn_engine {
       }
       each([&](Tile& t) {
         const Geom& g = t.g;
-        KLAUNCH(k_qx_fix, grid3(g.jdx2() - g.jdx1() + 1, g.idx2() - g.idx1() + 1, kz), BLK, 0, stream, g, dc,
-                qx_args(t));
+        KLAUNCH_AS("k_qx_fix", k_qx_fix<FamQx>, grid3(g.jdx2() - g.jdx1() + 1, g.idx2() - g.idx1() + 1, kz), BLK, 0,
+                   stream, g, dc, qx_args(t));
         if (serial_with_corr()) return;          // the serial chains then run in launch_corrections
-        KLAUNCH(k_qx_serial, dim3(hc.nsp * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc,
-                qx_args(t));
-        KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc,
-                qx_args(t));
+        KLAUNCH_AS("k_qx_serial", k_qx_serial<FamQx>, dim3(hc.nsp * kz), dim3(negfix_threads(g)),
+                   sizeof(double) * negfix_lds(g), stream, g, dc, qx_args(t));
+        KLAUNCH_AS("k_qx_post", k_qx_post<FamQx>, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0,
+                   stream, g, dc, qx_args(t));
       });
+    }
+    if (ntr) {
+      // the tracers after the species, on the same qdot, scaled xkc and mass fluxes: a group of
+      // NQXH per z slice of kz levels; the forecast on the ring as the species', so no exchange
+      // of atmc%chi unless the split step is not fused; the serial chains straight after the fix
+      // (nothing of the step waits for them)
+      each([&](Tile& t) {
+        const Geom& g = t.g;
+        const Fields f = fields(t);
+        KLAUNCH_AS("k_tr_tend", k_qx_tend<FamTr>,
+                   dim3((g.jcx2() - g.jcx1() + QBJ) / QBJ, (g.icx2() - g.icx1() + QBI) / QBI, tr_groups() * kz),
+                   dim3(QBT), 0, stream, g, dc, ds, f, tr_args(t));
+      });
+      if (!fused) {
+        std::vector<XField> cq;
+        add_tr(cq, FK::TRCQ, kz, 1);
+        xchv(cq);
+      }
+      each([&](Tile& t) { tracer_fix(t); });
     }
     if (!fused) xch({{FK::CQV, kz}, {FK::CQC, kz}});     // else k_scalars computed the ring
     // negative-moisture fix + p* RA filter + qv/qc RAW filter; then the new level is current
@@ -2657,7 +2938,8 @@ struct rcmdyn_engine {
         KLAUNCH(k_negfix_serial_qx, dim3((2 + hc.nsp) * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g),
                 stream, g, dc, qf, qx);
         KLAUNCH(k_negfix_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, 2 * kz), BLK, 0, stream, g, dc, qf);
-        KLAUNCH(k_qx_post, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0, stream, g, dc, qx);
+        KLAUNCH_AS("k_qx_post", k_qx_post<FamQx>, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, hc.nsp * kz), BLK, 0,
+                   stream, g, dc, qx);
       } else if (qfuse() && own) {
         KLAUNCH(k_negfix_serial, dim3(2 * kz), dim3(negfix_threads(g)), sizeof(double) * negfix_lds(g), stream, g, dc,
                 qf);
@@ -2744,6 +3026,7 @@ struct rcmdyn_engine {
       // the ghost-ring step wrote the slice entries past the tile itself (k_bdyval_set)
       if (ghosts_stale || !split_fused()) xch_slices();
     }
+    tracer_bdyval(lines_done ? 1 : -1, (int)lines_done);      // before the last tile's clock advance below
     for (size_t q = 0; q < tiles.size(); q++) {
       Tile& t = tiles[q];
       const int adv = q + 1 == tiles.size() ? (lines_done ? 2 : 1) : 0;
@@ -3301,6 +3584,24 @@ int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src, int32_t j1, int32_t j2, in
 int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                       int32_t k1, int32_t k2) {
   return guard(h, [&] { h->get_condtq(term, dst, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_set_tracers(rcmdyn_t* h, int32_t ntr, int32_t ichebdy) {
+  return guard(h, [&] { h->set_tracers(ntr, ichebdy); });
+}
+
+int rcmdyn_put_tracer(rcmdyn_t* h, int32_t field, int32_t itr, const double* src, int32_t j1, int32_t j2, int32_t i1,
+                      int32_t i2, int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->put_tracer(field, itr, src, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_get_tracer(rcmdyn_t* h, int32_t field, int32_t itr, double* dst, int32_t j1, int32_t j2, int32_t i1,
+                      int32_t i2, int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_tracer(field, itr, dst, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_put_tracer_nudge(rcmdyn_t* h, const double* cefc, const double* cegc) {
+  return guard(h, [&] { h->put_tracer_nudge(cefc, cegc); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

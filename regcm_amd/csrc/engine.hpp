@@ -209,6 +209,17 @@ struct Tile {
   unsigned* depx = nullptr;          // nqx = 5: the species planes' row bitmaps (as depplane)
   unsigned* depxf = nullptr;         // nqx = 5: the species planes' row flags (k_qx_fix -> k_qx_serial)
   unsigned* depqf = nullptr;         // qfuse: the qv / qc planes' row flags (negfix_list -> the serial passes)
+  // chemical tracers (rcmdyn_set_tracers; species.hip's FamTr instances), one entry per tracer:
+  // chia / chib ping-pong like qc (the NH core: in place, parity 0 only), the forecast and fixed
+  // values, chiphy, chib0 / chibt, the chib3d export (allocated by the first slice); the planes'
+  // row bitmaps and flags of the negative fix, NQXH * kz planes per group of NQXH tracers; the
+  // groups' argument tables in device memory, one per parity (kernels.hpp TrArgs), and the
+  // chib3d pointers for k_tr_slice.  tr_allocs: what rcmdyn_set_tracers(0) frees.
+  std::vector<double*> tra1[2], tra2[2], trcq, trfq, trphy, trb0, trbt, trs3d;
+  unsigned *trdep = nullptr, *trdepf = nullptr;
+  void* trtab[2] = {nullptr, nullptr};
+  double** trsout = nullptr;
+  std::vector<void*> tr_allocs;
   unsigned *depplane;              // per (n,k) plane: bitmap of the rows with a serially dependent negative point
   int* negcnt = nullptr;           // hydrostatic qfuse: the negative forecasts k_scalars listed
   uint32_t* neglist = nullptr;

@@ -188,10 +188,48 @@ struct QxArgs {
   double *cq[NQXH], *fq[NQXH];
   double *sl[NQXH], *d6[NQXH];
   const double* phy[NQXH];
+  const double *b0[NQXH], *bt[NQXH];   // tracers: chib0, chibt of the boundary relaxation (null for the species)
   unsigned* dep;               // per (species, level) plane: row bitmap of the serially dependent negative points
   unsigned* depf;              // per (species, level) plane and row: k_qx_fix's flag of such a point (k_qx_serial
                                // turns the flags into the bitmap)
-  int nsp;                     // hydrometeors beyond qc (0 for nqx = 2)
+  int nsp;                     // hydrometeors beyond qc (0 for nqx = 2); tracers: those of the group
+};
+
+// The chemical tracers (rcmdyn_set_tracers) go through the hydrometeors' kernels in groups of up
+// to NQXH: one QxArgs per group in a table in device memory, the group index on a grid dimension
+// (z = group * kz + level, or group * NQXH * kz + plane), so a block stages the cell's mass
+// fluxes once for its group.  cefc / cegc: nudge_chiten's tables, cefc(ib, k) at [(k - 1) *
+// nspgx + ib - 1]; relax: the relaxation term runs (iboudy 1 or 5 and a table entry is non-zero)
+struct TrArgs {
+  const QxArgs* tab;
+  const double *cefc, *cegc;
+  int ngroups, relax;
+};
+
+// The two families of the kernels of species.hip and of the serial negative-value fix
+// (qxcommon.hpp), a compile-time parameter F: what differs between the reference's chain of a
+// hydrometeor beyond qc and of a tracer.
+//   floor   the decoupling max(atm1 * rpsa, 0) (Main/mod_tendency.F90:1022-1026) against the
+//           plain product of the tracers (:1030-1032)
+//   thr     vadv4d's threshold of ind = 1 against ind = 2 (Main/mod_advection.F90:878, 900)
+//   fixfac  the factor of the negative-value fix (Main/mod_tendency.F90:389 against :576)
+//   cr      the NH adiabatic term atmx%qx * cr (:1615-1617; n = 1..nqx only, no tracer)
+//   relax   nudge_chiten (Main/chemlib/mod_che_bdyco.F90:898-982; the hydrometeors relax nothing)
+//   Args    the argument block: the species' QxArgs by value, the tracers' table
+static constexpr double MINTR = 1.0e-30;     // Share/mod_constants.F90:63 (double precision)
+struct FamQx {
+  using Args = QxArgs;
+  static constexpr bool floor = true, cr = true, relax = false, grouped = false;
+  static constexpr double fixfac = 0.01;
+  static __host__ __device__ __forceinline__ double thr(double ps) { return 1.0e-8 * 1.0e-8 * ps; }
+  static __device__ __forceinline__ const QxArgs& group(const Args& a, int) { return a; }
+};
+struct FamTr {
+  using Args = TrArgs;
+  static constexpr bool floor = false, cr = false, relax = true, grouped = true;
+  static constexpr double fixfac = 0.1;
+  static __host__ __device__ __forceinline__ double thr(double ps) { return MINTR * ps; }
+  static __device__ __forceinline__ const QxArgs& group(const Args& a, int grp) { return a.tab[grp]; }
 };
 
 // serial negative-moisture fix-up of k_split_project's extra blocks: the q fields before
@@ -278,16 +316,31 @@ __global__ void k_pack_segs(SegList L, double* __restrict__ buf, int unpack);
 __global__ void k_copy_frame(Geom g, Geom w, int nplanes, const double* __restrict__ src, long sstride, double* dst, long dstride);
 
 // species.hip: the hydrometeors beyond qc (nqx = 5), hydrostatic core (the ping-pong buffers)
-__global__ void k_qx_tend(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f, QxArgs q);
-__global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q);
-__global__ void k_qx_serial(Geom g, const Consts* __restrict__ c, QxArgs q);
-__global__ void k_qx_post(Geom g, const Consts* __restrict__ c, QxArgs q);
+// F: the family (FamQx, FamTr above); species.hip instantiates both of each kernel
+template <class F>
+__global__ void k_qx_tend(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
+                          typename F::Args a);
+template <class F>
+__global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, typename F::Args a);
+template <class F>
+__global__ void k_qx_serial(Geom g, const Consts* __restrict__ c, typename F::Args a);
+template <class F>
+__global__ void k_qx_post(Geom g, const Consts* __restrict__ c, typename F::Args a);
 __global__ void k_negfix_serial_qx(Geom g, const Consts* __restrict__ c, QFix qf, QxArgs q);
 struct NHFields;
 // the non-hydrostatic chains of the same hydrometeors (in place; k_qx_fix / k_qx_serial then
 // run with b* = a*)
+template <class F>
 __global__ void k_nh_qx_tend(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, NHFields f,
-                             QxArgs q);
+                             typename F::Args a);
+// chem_bdyval_coupled, ichebdy = 1 (Main/chemlib/mod_che_bdyco.F90:565-758), one block per
+// (level, tracer); integ as k_bdyval_qx; pre_clock: the step's clock is not advanced yet (the
+// bdyval lines ran in k_split_correct_bdy), so dt is the one the advance will set
+__global__ void k_bdyval_chi(Geom g, const StepState* __restrict__ s, TrArgs a, int ntr, int integ, int pre_clock,
+                             double dtsec);
+// mkslice's chib3d = max(atm2 * rpsb, 0) (Main/mod_slice.F90:196-200) of every tracer on the
+// tile's cross points (z = tracer * kz + level)
+__global__ void k_tr_slice(Geom g, int kz, int ntr, TrArgs a, const double* __restrict__ rpsb, double* const* out);
 // bdyval's boundary copies and inflow/outflow of the hydrometeors beyond qc (both cores);
 // integ: 1 integrating, 0 the initial call, -1 from the step clock (lcount > 0)
 __global__ void k_bdyval_qx(Geom g, const StepState* __restrict__ s, QxArgs q, int integ, int do_qc,

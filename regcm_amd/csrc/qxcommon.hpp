@@ -10,7 +10,10 @@
 
 namespace rcm {
 
-// negative-moisture fix helpers (K6, kernels.hip): the reference's value of one point
+// negative-moisture fix helpers (K6, kernels.hip): the reference's value of one point.  F: the
+// family (kernels.hpp), whose fixfac is the factor of the mean of the nine |q| (0.01 for the
+// moisture species, 0.1 for the tracers); the callers of qv, qc and the species take the default
+template <class F = FamQx>
 __device__ __forceinline__ double negfix_sum(const Geom& g, const double* sv, const double* fx, int j, int i, int k,
                                              bool use_fixed) {
   double sum = 0.0;
@@ -23,7 +26,7 @@ __device__ __forceinline__ double negfix_sum(const Geom& g, const double* sv, co
       }
       sum = sum + fabs(v);
     }
-  return 0.01 * sum / 9.0;
+  return F::fixfac * sum / 9.0;
 }
 
 __device__ __forceinline__ bool negfix_dependent(const Geom& g, const double* sv, int j, int i, int k) {
@@ -72,7 +75,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 // one wavefront (lane = threadIdx.x & 63) resolves plane `plane` (level k of sv / fx); post(j,
 // i, v) writes what follows from a fixed value (the filters), on the lane of point (j, i)
-template <class Post>
+template <class F = FamQx, class Post>
 __device__ void negfix_sweep(const Geom& g, const double* sv, double* fx, unsigned* dep, int plane, int k,
                              double* lds, Post post) {
   const int lane = (int)threadIdx.x & 63;
@@ -107,7 +110,7 @@ __device__ void negfix_sweep(const Geom& g, const double* sv, double* fx, unsign
             while (m) {
               const int b = __ffsll((long long)m) - 1;
               m &= m - 1;
-              const double v = negfix_sum(g, sv, fx, j0 + b, i, k, true);
+              const double v = negfix_sum<F>(g, sv, fx, j0 + b, i, k, true);
               F3(fx, j0 + b, i, k) = v;
               post(j0 + b, i, v);
             }
@@ -144,7 +147,7 @@ __device__ void negfix_sweep(const Geom& g, const double* sv, double* fx, unsign
                 }
                 sum = sum + fabs(v);
               }
-            rowc[jb - g.jci1] = 0.01 * sum / 9.0;
+            rowc[jb - g.jci1] = F::fixfac * sum / 9.0;
           }
         }
         wave_lds_sync();
@@ -191,7 +194,7 @@ __device__ __forceinline__ double lane_shr1(double x) {      // lane l gets lane
   return __shfl_up(x, 1, 64);
 #endif
 }
-template <class A>
+template <class F = FamQx, class A>
 __device__ void negfix_dense_dpp(const Geom& g, const double* sv, double* fx, int k, double* ring, const A& acc) {
   constexpr int P = 4, NQ = 3 + A::NI, SK = 8;
   const int r = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
@@ -246,7 +249,7 @@ __device__ void negfix_dense_dpp(const Geom& g, const double* sv, double* fx, in
         sum = sum + fabs(w2[2]);
         // / 9 as div_by (fastmath.hpp: the division's bits from the rounded reciprocal in three
         // dependent operations; the step's critical path runs through it), for normal operands
-        const double xs = 0.01 * sum;
+        const double xs = F::fixfac * sum;
         const double v = xs >= 0x1p-960 ? div_by(xs, 9.0, 1.0 / 9.0) : xs / 9.0;
         pub = v;
         prev = v;
@@ -287,7 +290,7 @@ __device__ __forceinline__ bool negfix_is_dependent(const Geom& g, const double*
 // holds the ring), else the row sweep by wavefront 0.  lds: ldsn doubles (see negfix_lds);
 // mode (Consts::negfix_mode, tests): 1 runs the row sweep on every marked plane.
 constexpr int NEGFIX_SPARSE = 16;
-template <class A, class Post>
+template <class F = FamQx, class A, class Post>
 __device__ void negfix_resolve(const Geom& g, const double* sv, double* fx, unsigned* dep, int plane, int k,
                                double* lds, int ldsn, const A& acc, Post post, int mode = 0) {
   const int nw = negfix_rowwords(g), R = g.ici2 - g.ici1 + 1;
@@ -298,12 +301,12 @@ __device__ void negfix_resolve(const Geom& g, const double* sv, double* fx, unsi
   const int T = (int)(blockDim.x * blockDim.y * blockDim.z);
   const int tid = (int)(threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z));
   if (mode == 0 && nm > NEGFIX_SPARSE && R <= T && 4 * R <= ldsn) {
-    negfix_dense_dpp(g, sv, fx, k, lds, acc);
+    negfix_dense_dpp<F>(g, sv, fx, k, lds, acc);
     __syncthreads();                           // every wave read the bitmap before it is cleared
     for (int w = tid; w < nw; w += T) words[w] = 0;
     return;
   }
-  if (tid < 64) negfix_sweep(g, sv, fx, dep, plane, k, negfix_sweep_lds(g) <= ldsn ? lds : nullptr, post);
+  if (tid < 64) negfix_sweep<F>(g, sv, fx, dep, plane, k, negfix_sweep_lds(g) <= ldsn ? lds : nullptr, post);
 }
 
 // qc inflow/outflow (present_qc = .false., bdyflow), Main/mod_bdycod.F90:2153-2220, one

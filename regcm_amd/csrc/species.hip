@@ -24,6 +24,11 @@
 // (Main/mod_tendency.F90:1615-1617) and updates the state in place: k_qx_fix / k_qx_serial then
 // filter into the same buffers (each thread reads and writes only its own point's levels).
 //
+// The chemical tracers (rcmdyn_set_tracers) take the same chain with the differences of the
+// family FamTr (kernels.hpp): no decoupling floor, vadv4d ind = 2, the fix factor 0.1, no NH cr
+// term, nudge_chiten between advection and diffusion; k_bdyval_chi is chem_bdyval_coupled and
+// k_tr_slice the chib3d export.  Up to NQXH tracers share a block, the group on the grid's z.
+//
 // Transcendental-free: every result is bit-identical to the oracle's restatement
 // (-ffp-contract=off).
 #include "engine.hpp"
@@ -45,17 +50,22 @@ constexpr int QW2 = QBJ + 4, QH2 = QBI + 4;    // halo 2
 // tile and its ghost ring (jcx x icx, as k_scalars: the ring is what the exchange of atmc%qx
 // would deliver), one level per block.  Reads the scaled diffusion coefficient k_scalars
 // stored (xkc * rdxsq * p*b at the interior points) and qdot of k_columns.
+// F: the family (kernels.hpp).  A tracer launch carries its groups on z = group * kz + level.
+template <class F>
 __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restrict__ c,
-                                                 const StepState* __restrict__ s, Fields f, QxArgs q) {
+                                                 const StepState* __restrict__ s, Fields f, typename F::Args fa) {
   __shared__ double sUMC[QDH][QDW], sVMC[QDH][QDW];
-  __shared__ double sX[NQXH][QH1][QW1];          // atmx%qx = max(atm1 * rpsa, 0), halo 1
+  __shared__ double sX[NQXH][QH1][QW1];          // atmx%qx = max(atm1 * rpsa, 0) (tracers: no floor), halo 1
   __shared__ double sB[NQXH][QH2][QW2];          // qxb3d = max(atm2 * (1/psb), 0), halo 2
   const int tid = threadIdx.x;
-  const int J0 = g.jcx1() + (int)blockIdx.x * QBJ, I0 = g.icx1() + (int)blockIdx.y * QBI, k = (int)blockIdx.z + 1;
+  const int kz = c->kz;
+  const int grp = F::grouped ? (int)blockIdx.z / kz : 0, k = (F::grouped ? (int)blockIdx.z % kz : (int)blockIdx.z) + 1;
+  const QxArgs& q = F::group(fa, grp);
+  const int J0 = g.jcx1() + (int)blockIdx.x * QBJ, I0 = g.icx1() + (int)blockIdx.y * QBI;
   const uint32_t P8 = g.P8, L8 = g.L8, kof = (uint32_t)(k - 1) * L8;
   (void)P8;
   const int jlo = g.j0, jhi = g.j0 + g.nj - 1, ilo = g.i0, ihi = g.i0 + g.ni - 1;
-  const int kz = c->kz, nsp = q.nsp;
+  const int nsp = q.nsp;
   const int tj = tid % QBJ, ti = tid / QBJ;
   const int j = J0 + tj, i = I0 + ti;
   const bool valid = j <= g.jcx2() && i <= g.icx2();
@@ -78,7 +88,7 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
 #pragma unroll
     for (int n = 0; n < NQXH; n++) x[n] = n < nsp ? LD(q.a1[n], q2 + kof) : 0.0;
 #pragma unroll
-    for (int n = 0; n < NQXH; n++) sX[n][ii][jj] = ok ? dmax(x[n] * rp, d_zero) : 0.0;
+    for (int n = 0; n < NQXH; n++) sX[n][ii][jj] = ok ? (F::floor ? dmax(x[n] * rp, d_zero) : x[n] * rp) : 0.0;
   }
   for (int t = tid; t < QW2 * QH2; t += QBT) {
     const int jj = t % QW2, ii = t / QW2, jg = J0 - 2 + jj, ig = I0 - 2 + ii;
@@ -124,7 +134,7 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
       if (k >= 2) tq = tq + (uw_fg(c, k, kpb, c0, cm, fk) * q0) * c->xds[k];
       if (k + 1 <= kz) tq = tq - (uw_fg(c, k + 1, kpb, cp, c0, fk) * q1) * c->xds[k];
     } else {
-      const double thr = MINQQ * MINQQ * ps;
+      const double thr = F::thr(ps);
       if (k >= 2) {
         const double fl = (q0 > d_zero) ? ((cm > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero)
                                         : ((c0 > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero);
@@ -134,6 +144,22 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
         const double fl = (q1 > d_zero) ? ((c0 > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero)
                                         : ((cp > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero);
         tq = tq - fl * c->xds[k];
+      }
+    }
+    // nudge_chiten, ichebdy = 1 (Main/chemlib/mod_che_bdyco.F90:898-982), on atm2 (Main/
+    // mod_tendency.F90:1507) between the advection and the diffusion: the band's south / north
+    // points sum fls1..4 as west, east, south, north, its west / east points as south, north,
+    // west, east
+    if constexpr (F::relax) {
+      const int rg = fa.relax ? (int)f.rgcr[o2 >> 3] : 0;
+      if (rg > 0) {
+        const double xt = s->xbctime + dt;
+        const int ib = f.ibcr[o2 >> 3];
+        const double xf = fa.cefc[(k - 1) * c->nspgx + ib - 1], xg = fa.cegc[(k - 1) * c->nspgx + ib - 1];
+#define FLS(dj, di) bdy_minus_state(LD(q.b0[n], O3(dj, di)), LD(q.bt[n], O3(dj, di)), LD(q.a2[n], O3(dj, di)), xt)
+        if (rg <= 2) tq = relax(tq, xf, xg, FLS(0, 0), FLS(-1, 0), FLS(1, 0), FLS(0, -1), FLS(0, 1));
+        else tq = relax(tq, xf, xg, FLS(0, 0), FLS(0, -1), FLS(0, 1), FLS(-1, 0), FLS(1, 0));
+#undef FLS
       }
     }
     // diffu_x4d on the mkslice field qxb3d; idiffu = 3: k_diffu6's column term (as k_scalars)
@@ -152,11 +178,16 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
 // qi, qr, qs at the interior cross points (owned points only, as the NH tendency kernels):
 // hadvqx, vadv4d ind 1 / 3, + atmx%qx * cr (:1615-1617), diffu_x4d on the scaled xkcr, the
 // sums with qxphy, the forecast; the ring jce \ jci takes atm2.
+template <class F>
 __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __restrict__ c,
-                                                    const StepState* __restrict__ s, NHFields f, QxArgs q) {
-  THREAD_POINT(g.jce1, g.ice1);
+                                                    const StepState* __restrict__ s, NHFields f, typename F::Args fa) {
+  const int j = g.jce1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = g.ice1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int kz = c->kz;
+  const int grp = F::grouped ? (int)blockIdx.z / kz : 0, k = (F::grouped ? (int)blockIdx.z % kz : (int)blockIdx.z) + 1;
+  const QxArgs& q = F::group(fa, grp);
   if (!(in(j, g.jce1, g.jce2) && in(i, g.ice1, g.ice2))) return;
-  const int nsp = q.nsp, kz = c->kz;
+  const int nsp = q.nsp;
   if (!(in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2))) {
     for (int n = 0; n < nsp; n++) F3(q.cq[n], j, i, k) = F3(q.a2[n], j, i, k);
     return;
@@ -174,17 +205,19 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
                rs = F2(f.rpsa, j, i - 1), rn = F2(f.rpsa, j, i + 1);
   const double cr = F3(f.cr, j, i, k);
   const double xkc = F3(f.xkcr, j, i, k) * c->rdxsq * pbs;      // calc_coeff's xkc
-  const double thr = MINQQ * MINQQ * ps;
+  const double thr = F::thr(ps);
   const int kpb = f.kpbl ? (int)F2(f.kpbl, j, i) : 0;
+  // atmx of the family: the species' floor at zero, the tracers' plain product
+  auto dec = [](double x, double r) { return F::floor ? dmax(x * r, d_zero) : x * r; };
   for (int n = 0; n < nsp; n++) {
     const double* a = q.a1[n];
     double cd;
     if (c->isladvec) {
       cd = d_zero + F3(q.sl[n], j, i, k);
     } else {
-      const double xc = dmax(F3(a, j, i, k) * r0, d_zero), xw = dmax(F3(a, j - 1, i, k) * rw, d_zero);
-      const double xe = dmax(F3(a, j + 1, i, k) * re, d_zero), xs = dmax(F3(a, j, i - 1, k) * rs, d_zero);
-      const double xn = dmax(F3(a, j, i + 1, k) * rn, d_zero);
+      const double xc = dec(F3(a, j, i, k), r0), xw = dec(F3(a, j - 1, i, k), rw);
+      const double xe = dec(F3(a, j + 1, i, k), re), xs = dec(F3(a, j, i - 1, k), rs);
+      const double xn = dec(F3(a, j, i + 1, k), rn);
       cd = d_zero + hadv_flux(c, xmf, ps, u1, u2, v1, v2, xc, xw, xe, xs, xn, 0);
     }
     auto cflux = [&](int kk) {
@@ -196,7 +229,20 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
     };
     if (k >= 2) cd = cd + cflux(k) * c->xds[k];
     if (k + 1 <= kz) cd = cd - cflux(k + 1) * c->xds[k];
-    cd = cd + dmax(F3(a, j, i, k) * r0, d_zero) * cr;
+    if constexpr (F::cr) cd = cd + dmax(F3(a, j, i, k) * r0, d_zero) * cr;
+    if constexpr (F::relax) {     // nudge_chiten, as in k_qx_tend
+      const int rg = fa.relax ? (int)F2(f.rgcr, j, i) : 0;
+      if (rg > 0) {
+        const double xt = s->xbctime + dt;
+        const int ib = F2(f.ibcr, j, i);
+        const double xf = fa.cefc[(k - 1) * c->nspgx + ib - 1], xg = fa.cegc[(k - 1) * c->nspgx + ib - 1];
+#define FLS(dj, di) \
+  bdy_minus_state(F3(q.b0[n], j + (dj), i + (di), k), F3(q.bt[n], j + (dj), i + (di), k), F3(q.a2[n], j + (dj), i + (di), k), xt)
+        if (rg <= 2) cd = relax(cd, xf, xg, FLS(0, 0), FLS(-1, 0), FLS(1, 0), FLS(0, -1), FLS(0, 1));
+        else cd = relax(cd, xf, xg, FLS(0, 0), FLS(0, -1), FLS(0, 1), FLS(-1, 0), FLS(1, 0));
+#undef FLS
+      }
+    }
     if (c->idiffu == 3) {
       if (j == g.jci2) cd = cd + F3(q.d6[n], j, i, k);
     } else {
@@ -218,8 +264,13 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
 // copies of the column box's other points (atm1, and atm2 on owned points: bdyval and the next
 // step's exchange read them).  A negative point with a negative sweep-predecessor flags its
 // (species, level) plane for k_qx_serial; the others read original values only.
-__global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q) {
-  THREAD_POINT(g.jdx1(), g.idx1());
+template <class F>
+__global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, typename F::Args fa) {
+  const int j = g.jdx1() + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = g.idx1() + (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int grp = F::grouped ? (int)blockIdx.z / c->kz : 0;
+  const int k = (F::grouped ? (int)blockIdx.z % c->kz : (int)blockIdx.z) + 1;
+  const QxArgs& q = F::group(fa, grp);
   if (j > g.jdx2() || i > g.idx2()) return;
   const uint32_t o3 = g.o3(j, i, k);
   const bool ci = in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
@@ -244,7 +295,7 @@ __global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, QxArgs q) {
       continue;
     }
     if (v < d_zero) {
-      v = negfix_sum(g, q.cq[n], q.fq[n], j, i, k, false);
+      v = negfix_sum<F>(g, q.cq[n], q.fq[n], j, i, k, false);
       ST(q.fq[n], o3, v);
     }
     double n1, n2;
@@ -274,6 +325,7 @@ struct QxRaw {
   }
 };
 // one (species, level) plane of k_qx_serial (lds: negfix_lds(g) doubles)
+template <class F>
 __device__ __forceinline__ void qx_serial_plane(const Geom& g, const Consts* __restrict__ c, const QxArgs& q,
                                                 int plane, double* lds) {
   const int kz = c->kz;
@@ -298,11 +350,14 @@ __device__ __forceinline__ void qx_serial_plane(const Geom& g, const Consts* __r
     }
     __syncthreads();
   }
-  negfix_resolve(g, q.cq[n], q.fq[n], q.dep, plane, k, lds, negfix_lds(g), NoPost{}, [](int, int, double) {}, c->negfix_mode);
+  negfix_resolve<F>(g, q.cq[n], q.fq[n], q.dep, plane, k, lds, negfix_lds(g), NoPost{}, [](int, int, double) {}, c->negfix_mode);
 }
-__global__ __launch_bounds__(512) void k_qx_serial(Geom g, const Consts* __restrict__ c, QxArgs q) {
+// a block per plane; the tracers: NQXH * kz blocks per group
+template <class F>
+__global__ __launch_bounds__(512) void k_qx_serial(Geom g, const Consts* __restrict__ c, typename F::Args fa) {
   extern __shared__ double lds[];
-  qx_serial_plane(g, c, q, (int)blockIdx.x, lds);
+  const int per = NQXH * c->kz, b = (int)blockIdx.x;
+  qx_serial_plane<F>(g, c, F::group(fa, F::grouped ? b / per : 0), F::grouped ? b % per : b, lds);
 }
 // hydrostatic qfuse: the serial chains of the qv / qc planes (blocks [0, 2 kz), as
 // k_negfix_serial) and of the species planes (k_qx_serial) in one launch after the split
@@ -312,7 +367,7 @@ __global__ __launch_bounds__(512) void k_negfix_serial_qx(Geom g, const Consts* 
   extern __shared__ double lds[];
   const int b = (int)blockIdx.x, kz = c->kz;
   if (b >= 2 * kz) {
-    qx_serial_plane(g, c, q, b - 2 * kz, lds);
+    qx_serial_plane<FamQx>(g, c, q, b - 2 * kz, lds);
     return;
   }
   const int n = b / kz, k = b % kz + 1;
@@ -326,10 +381,13 @@ __global__ __launch_bounds__(512) void k_negfix_serial_qx(Geom g, const Consts* 
 
 // filter_raw_4d of the points k_qx_serial fixed, a thread per interior point of a
 // (species, level) plane (z = plane)
-__global__ void k_qx_post(Geom g, const Consts* __restrict__ c, QxArgs q) {
+template <class F>
+__global__ void k_qx_post(Geom g, const Consts* __restrict__ c, typename F::Args fa) {
   const int j = g.jci1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int i = g.ici1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
-  const int plane = (int)blockIdx.z, kz = c->kz, n = plane / kz, k = plane % kz + 1;
+  const int kz = c->kz, per = NQXH * kz, z = (int)blockIdx.z;
+  const QxArgs& q = F::group(fa, F::grouped ? z / per : 0);
+  const int plane = F::grouped ? z % per : z, n = plane / kz, k = plane % kz + 1;
   if (j > g.jci2 || i > g.ici2 || n >= q.nsp) return;
   if (!negfix_is_dependent(g, q.cq[n], j, i, k)) return;
   const QxRaw acc{g, c, q.a1[n], q.a2[n], q.b1[n], q.b2[n], k};
@@ -361,5 +419,65 @@ __global__ void k_bdyval_qx(Geom g, const StepState* __restrict__ s, QxArgs q, i
   }
   bdyval_qc_level(g, do_qc, 0, a1, nullptr, [&](int j, int i) { return F2(psa, j, i); }, sl, slen, k);
 }
+
+// K_TR4.  chem_bdyval_coupled with ichebdy = 1 (Main/chemlib/mod_che_bdyco.F90:565-758), one
+// block per (level, tracer): while integrating, chib = chia on the boundary lines (west / east
+// on ice, south / north on jci: the corners go with west / east, where qx's copies take them with
+// south / north), then chia = chib0 + xt * chibt (west / east on ici, south / north on jce).
+__global__ void k_bdyval_chi(Geom g, const StepState* __restrict__ s, TrArgs a, int ntr, int integ, int pre_clock,
+                             double dtsec) {
+  const int k = (int)blockIdx.x + 1, n = (int)blockIdx.y;
+  if (n >= ntr) return;
+  const QxArgs& q = a.tab[n / NQXH];
+  const int m = n % NQXH;
+  double* a1 = q.a1[m];
+  double* a2 = q.a2[m];
+  const double* b0 = q.b0[m];
+  const double* bt = q.bt[m];
+  if (integ > 0 || (integ < 0 && s->lcount > 0)) {
+    for (int i = g.ice1 + (int)threadIdx.x; i <= g.ice2; i += (int)blockDim.x) {
+      if (g.bl) F3(a2, g.jce1, i, k) = F3(a1, g.jce1, i, k);
+      if (g.br) F3(a2, g.jce2, i, k) = F3(a1, g.jce2, i, k);
+    }
+    for (int j = g.jci1 + (int)threadIdx.x; j <= g.jci2; j += (int)blockDim.x) {
+      if (g.bb) F3(a2, j, g.ice1, k) = F3(a1, j, g.ice1, k);
+      if (g.bt) F3(a2, j, g.ice2, k) = F3(a1, j, g.ice2, k);
+    }
+    __syncthreads();
+  }
+  const double dt = pre_clock ? ((s->lcount + 1 == 2) ? d_two * dtsec : s->dt) : s->dt;
+  const double xt = s->xbctime + dt;
+  for (int i = g.ici1 + (int)threadIdx.x; i <= g.ici2; i += (int)blockDim.x) {
+    if (g.bl) F3(a1, g.jce1, i, k) = F3(b0, g.jce1, i, k) + xt * F3(bt, g.jce1, i, k);
+    if (g.br) F3(a1, g.jce2, i, k) = F3(b0, g.jce2, i, k) + xt * F3(bt, g.jce2, i, k);
+  }
+  for (int j = g.jce1 + (int)threadIdx.x; j <= g.jce2; j += (int)blockDim.x) {
+    if (g.bb) F3(a1, j, g.ice1, k) = F3(b0, j, g.ice1, k) + xt * F3(bt, j, g.ice1, k);
+    if (g.bt) F3(a1, j, g.ice2, k) = F3(b0, j, g.ice2, k) + xt * F3(bt, j, g.ice2, k);
+  }
+}
+
+// mkslice's chib3d (Main/mod_slice.F90:196-200) on the tile's cross points, z = tracer * kz + level
+__global__ void k_tr_slice(Geom g, int kz, int ntr, TrArgs a, const double* __restrict__ rpsb, double* const* out) {
+  const int j = g.jce1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = g.ice1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int n = (int)blockIdx.z / kz, k = (int)blockIdx.z % kz + 1;
+  if (j > g.jce2 || i > g.ice2 || n >= ntr) return;
+  const double* a2 = a.tab[n / NQXH].a2[n % NQXH];
+  F3(out[n], j, i, k) = dmax(F3(a2, j, i, k) * F2(rpsb, j, i), d_zero);
+}
+
+// the instances of both families
+#define RCM_QX_INSTANCES(F)                                                                                        \
+  template __global__ void k_qx_tend<F>(Geom, const Consts* __restrict__, const StepState* __restrict__, Fields,   \
+                                        typename F::Args);                                                         \
+  template __global__ void k_nh_qx_tend<F>(Geom, const Consts* __restrict__, const StepState* __restrict__,        \
+                                           NHFields, typename F::Args);                                            \
+  template __global__ void k_qx_fix<F>(Geom, const Consts* __restrict__, typename F::Args);                         \
+  template __global__ void k_qx_serial<F>(Geom, const Consts* __restrict__, typename F::Args);                      \
+  template __global__ void k_qx_post<F>(Geom, const Consts* __restrict__, typename F::Args);
+RCM_QX_INSTANCES(FamQx)
+RCM_QX_INSTANCES(FamTr)
+#undef RCM_QX_INSTANCES
 
 }  // namespace rcm

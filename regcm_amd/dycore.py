@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from .config import FIELD, RcmdynConfig, build_config, field_levels
+from .config import FIELD, TRACER_FIELD, RcmdynConfig, build_config, field_levels
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RCMDYN_LIB selects an instrumented build (tools/phases.py); default: the in-tree engine
@@ -34,6 +34,7 @@ EXPORTED = [
     "rcmdyn_set_budget", "rcmdyn_get_budget", "rcmdyn_reset_budget",
     "rcmdyn_set_massck", "rcmdyn_get_massck",
     "rcmdyn_set_condtq", "rcmdyn_put_rh0adj", "rcmdyn_get_condtq",
+    "rcmdyn_set_tracers", "rcmdyn_put_tracer", "rcmdyn_get_tracer", "rcmdyn_put_tracer_nudge",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
@@ -96,6 +97,10 @@ def lib():
     L.rcmdyn_set_condtq.argtypes = [P, i32, ctypes.c_double]
     L.rcmdyn_put_rh0adj.argtypes = [P, dp, i32, i32, i32, i32, i32, i32]
     L.rcmdyn_get_condtq.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_set_tracers.argtypes = [P, i32, i32]
+    L.rcmdyn_put_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put_tracer_nudge.argtypes = [P, dp, dp]
     _lib = L
     return L
 
@@ -331,6 +336,37 @@ class DynCore:
         self._check(lib().rcmdyn_get_condtq(self.h, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                             1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
         return out
+
+    def set_tracers(self, ntr: int, ichebdy: int = 1):
+        """Declares ntr chemical tracers (the reference's ichem = 1 chain of tend and bdyval);
+        ntr = 0 switches the family off and frees its buffers.  Only ichebdy = 1 is built."""
+        self._check(lib().rcmdyn_set_tracers(self.h, ntr, ichebdy))
+
+    def put_tracer(self, name, itr: int, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+        """One field (TRACER_FIELDS name or number) of tracer itr = 1..ntr, a (kz, ni, nj) array
+        coupled with p*, starting at the global indices (j1, i1, k1)."""
+        f = TRACER_FIELD[name] if isinstance(name, str) else int(name)
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        nk, ni, nj = a.shape
+        self._check(lib().rcmdyn_put_tracer(self.h, f, itr, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+
+    def get_tracer(self, name, itr: int) -> np.ndarray:
+        """One field of tracer itr as a (kz, iy, jx) array."""
+        f = TRACER_FIELD[name] if isinstance(name, str) else int(name)
+        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
+        self._check(lib().rcmdyn_get_tracer(self.h, f, itr, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
+        return out
+
+    def put_tracer_nudge(self, cefc: np.ndarray, cegc: np.ndarray):
+        """nudge_chiten's tables as (kz, nspgx) arrays, [k - 1, ib - 1] = cefc(ib, k); zero until put."""
+        a = np.ascontiguousarray(cefc, dtype=np.float64)
+        b = np.ascontiguousarray(cegc, dtype=np.float64)
+        if a.shape != (self.rc.kz, self.rc.nspgx) or b.shape != a.shape:
+            raise EngineError(f"put_tracer_nudge: the tables must have shape (kz, nspgx) = {(self.rc.kz, self.rc.nspgx)}")
+        self._check(lib().rcmdyn_put_tracer_nudge(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  b.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

@@ -58,6 +58,12 @@ module mod_gpu_dyn
   integer(c_int32_t), parameter, public :: &
     condtq_rh0adj = 0, condtq_t = 1, condtq_qv = 2, condtq_qc = 3, rcmdyn_ncondtq = 4
 
+  ! fields of one chemical tracer (enum rcmdyn_tracer_field): chia, chib, chiphy (put only), chib0,
+  ! chibt, the mkslice export chib3d (get only); the most tracers of one engine (RCMDYN_MAXTR)
+  integer(c_int32_t), parameter, public :: &
+    tr_atm1 = 0, tr_atm2 = 1, tr_phy = 2, tr_b0 = 3, tr_bt = 4, tr_chib3d = 5, rcmdyn_ntrfields = 6
+  integer, parameter, public :: rcmdyn_maxtr = 96
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -91,7 +97,8 @@ module mod_gpu_dyn
     integer(c_int32_t) :: ibltyp, iuwvadv
     real(c_double) :: nuk, tkemin
     ! ABI 6: physicsparam ipptls and the nqx param sets from it (2, or 5 for ipptls >= 2);
-    ! i_band (1: tropical band, hydrostatic core), i_crm, ichem (refused if set)
+    ! i_band (1: tropical band, hydrostatic core), i_crm, ichem (refused if set: the tracers
+    ! are declared with rcmdyn_set_tracers)
     integer(c_int32_t) :: ipptls, nqx
     integer(c_int32_t) :: i_band, i_crm, ichem
   end type rcmdyn_config
@@ -299,6 +306,35 @@ module mod_gpu_dyn
       integer(c_int32_t), value :: term, j1, j2, i1, i2, k1, k2
       real(c_double), intent(out) :: dst(*)
     end function
+    ! the chemical tracers (the reference's ichem = 1 chain of tend and bdyval): ntr of them
+    ! (0: the family off, its buffers freed); ichebdy must be 1
+    integer(c_int) function rcmdyn_set_tracers(h, ntr, ichebdy) bind(c, name='rcmdyn_set_tracers')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: ntr, ichebdy
+    end function
+    ! one field (tr_atm1 .. tr_bt) of tracer itr = 1..ntr from src(j1:j2,i1:i2,k1:k2)
+    integer(c_int) function rcmdyn_put_tracer(h, f, itr, src, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_put_tracer')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: f, itr, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(in) :: src(*)
+    end function
+    ! one field (tr_atm1, tr_atm2, tr_b0, tr_bt, tr_chib3d) of tracer itr into dst(j1:j2,i1:i2,k1:k2)
+    integer(c_int) function rcmdyn_get_tracer(h, f, itr, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_tracer')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: f, itr, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
+    ! nudge_chiten's tables cefc(nspgx,kz), cegc(nspgx,kz); zero until put, as the reference leaves them
+    integer(c_int) function rcmdyn_put_tracer_nudge(h, cefc, cegc) bind(c, name='rcmdyn_put_tracer_nudge')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      real(c_double), intent(in) :: cefc(*), cegc(*)
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -320,6 +356,7 @@ module mod_gpu_dyn
   public :: rcmdyn_kernel_times, rcmdyn_set_budget, rcmdyn_get_budget, rcmdyn_reset_budget
   public :: rcmdyn_set_massck, rcmdyn_get_massck
   public :: rcmdyn_set_condtq, rcmdyn_put_rh0adj, rcmdyn_get_condtq
+  public :: rcmdyn_set_tracers, rcmdyn_put_tracer, rcmdyn_get_tracer, rcmdyn_put_tracer_nudge
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains
