@@ -944,6 +944,68 @@ __device__ __forceinline__ void scalars_qraw(const Consts* __restrict__ c, const
   ST(n ? f.b2qc : f.b2qv, o3, n2);
 }
 
+// The vertical-flux summands of one scalars point at level k, whole as the t, qv and qc chains
+// of scalars_block add them: a at interface k (added where k >= 2), b at interface k + 1
+// (subtracted where k + 1 <= kz); a summand past its guard is never added and stays zero.
+// They read point operands and Consts only, no LDS.  scalars_block forms the pair of t between
+// the issue of its staging loads and their first use; the moisture pairs in their chains (formed
+// early as well they spill).
+struct VPair { double a, b; };
+// vadv3d ind = 1 (Main/mod_advection.F90:771-783): pf/pb from psb (mkslice :263-271)
+__device__ __forceinline__ VPair vflux_t(const Consts* __restrict__ c, int k, int kz, double pb, double q0, double q1,
+                                         double t1, double t1m, double t1p) {
+  VPair v = {d_zero, d_zero};
+  const double ptop = c->ptop, c287 = c->c287, xds = c->xds[k];
+#define PF(K) ((c->sigma[K] * pb + ptop) * d_1000)
+#define PB(K) ((c->hsigma[K] * pb + ptop) * d_1000)
+  if (k >= 2)
+    v.a = (q0 * (c->twt1[k] * t1 * powpos(PF(k) / PB(k), c287) +
+                 c->twt2[k] * t1m * powpos(PF(k) / PB(k - 1), c287))) * xds;
+  if (k + 1 <= kz)
+    v.b = (q1 * (c->twt1[k + 1] * t1p * powpos(PF(k + 1) / PB(k + 1), c287) +
+                 c->twt2[k + 1] * t1 * powpos(PF(k + 1) / PB(k), c287))) * xds;
+#undef PB
+#undef PF
+  return v;
+}
+// vadvqv: both values of an interface above MINQQ p*, else no flux (xds is read once, ahead of
+// the divergent selects: read behind one it becomes a vector load)
+__device__ __forceinline__ VPair vflux_qv(const Consts* __restrict__ c, int k, int kz, double ps, double q0, double q1,
+                                          double qv1, double qv1m, double qv1p) {
+  VPair v = {d_zero, d_zero};
+  const double thr = MINQQ * ps, xds = c->xds[k];
+  const double qc0 = qv1;
+  if (k >= 2) {
+    const double qm = qv1m;
+    v.a = q0 * ((qc0 > thr && qm > thr) ? qc0 * powpos(qm / qc0, c->qcon[k]) : d_zero) * xds;
+  }
+  if (k + 1 <= kz) {
+    const double qp = qv1p;
+    v.b = q1 * ((qp > thr && qc0 > thr) ? qp * powpos(qc0 / qp, c->qcon[k + 1]) : d_zero) * xds;
+  }
+  return v;
+}
+// vadv4d ind = 1: the upstream value above MINQQ^2 p*, else no flux
+__device__ __forceinline__ VPair vflux_qc(const Consts* __restrict__ c, int k, int kz, double ps, double q0, double q1,
+                                          double qc1, double qc1m, double qc1p) {
+  VPair v = {d_zero, d_zero};
+  const double thr = MINQQ * MINQQ * ps, xds = c->xds[k];
+  const double c0 = qc1;
+  if (k >= 2) {
+    const double cm = qc1m;
+    const double fl = (q0 > d_zero) ? ((cm > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero)
+                                    : ((c0 > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero);
+    v.a = fl * xds;
+  }
+  if (k + 1 <= kz) {
+    const double cp = qc1p;
+    const double fl = (q1 > d_zero) ? ((c0 > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero)
+                                    : ((cp > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero);
+    v.b = fl * xds;
+  }
+  return v;
+}
+
 // LDS of one k_scalars block
 struct ScaLDS {
   double sUMC[SDH][SDW], sVMC[SDH][SDW], sUD[SDH][SDW], sVD[SDH][SDW], sUB[SDH][SDW], sVB[SDH][SDW];
@@ -989,15 +1051,13 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   const int j = J0 + tj, i = I0 + ti;
   const bool valid = j >= g.jcx1() && j <= g.jcx2() && i <= g.icx2();
   const uint32_t o2 = valid ? g.o2(j, i) : g.o2(g.jce1, g.ice1), o3 = o2 + kof;
-  const double t1 = LD(f.a1t, o3), t2 = LD(f.a2t, o3), qv2 = LD(f.a2qv, o3), qc2 = LD(f.a2qc, o3);
-  const double qv1 = LD(f.a1qv, o3), qc1 = LD(f.a1qc, o3);
-  const double t1m = (k >= 2) ? LD(f.a1t, o3 - L8) : 0.0, qv1m = (k >= 2) ? LD(f.a1qv, o3 - L8) : 0.0;
-  const double qc1m = (k >= 2) ? LD(f.a1qc, o3 - L8) : 0.0;
-  const double t1p = (k < kz) ? LD(f.a1t, o3 + L8) : 0.0, qv1p = (k < kz) ? LD(f.a1qv, o3 + L8) : 0.0;
-  const double qc1p = (k < kz) ? LD(f.a1qc, o3 + L8) : 0.0;
+  // (first the operands of the arithmetic done under the staging loads, see below; the others
+  // follow that arithmetic, and the atm2 values the barrier)
+  const double t1 = LD(f.a1t, o3);
+  const double t1m = (k >= 2) ? LD(f.a1t, o3 - L8) : 0.0, t1p = (k < kz) ? LD(f.a1t, o3 + L8) : 0.0;
   const double q0 = LD(f.qdot, o3), q1 = LD(f.qdot, o3 + L8);
-  const double xm = LD(f.xmsf, o2), rp = LD(f.rpsa, o2), pb = LD(f.psb, o2), mx = LD(f.msfx, o2);
-  const double ptn = LD(f.pten, o2), hgf = LD(f.hgfact, o2);
+  const double pb = LD(f.psb, o2);
+  const double rp = LD(f.rpsa, o2), mx = LD(f.msfx, o2);
   const int rgc = f.rgcr[o2 >> 3];
   // ---- stage.  Every global load of the three staging sets is issued before the first LDS
   // write, so the block waits one memory latency instead of one per set and slot; lanes past
@@ -1043,6 +1103,26 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       crb[n] = ct2[n] = cqv[n] = cqc[n] = 0.0;
     }
   }
+  // ---- under the staging loads: arithmetic of the point that reads no LDS, from the point
+  // operands loaded first (the wave would otherwise idle until the first staged value arrives):
+  // the two summands of vadv3d with their four x**y, whole as the t chain adds them (operands,
+  // order, rounding; the level guards stay around the additions), and two scalars of omega and
+  // of the adiabatic term.  t1m, t1p, mx and rp end here.  The section must not wait on a
+  // staging load: a scratch reload or a vector load of Consts inside it waits for them all,
+  // which is why the moisture fluxes are not here (they spill at 128 VGPRs).
+  __builtin_amdgcn_sched_barrier(0);
+  const VPair vft = vflux_t(c, k, kz, pb, q0, q1, t1, t1m, t1p);
+  const double rdx8m = d_one / (c->dx8 * mx);              // omega's 1 / (dx8 msfx)
+  const double adiden = c->ptop * rp + c->hsigma[k];       // the adiabatic term's pressure / p*
+  __builtin_amdgcn_sched_barrier(0);
+  // the point operands that only the chains behind the barrier read, loaded behind that
+  // arithmetic so that it has their registers: their latency passes under the LDS writes
+  const double xm = LD(f.xmsf, o2), ptn = LD(f.pten, o2), hgf = LD(f.hgfact, o2);
+  const double qv1 = LD(f.a1qv, o3), qv1m = (k >= 2) ? LD(f.a1qv, o3 - L8) : 0.0;
+  const double qv1p = (k < kz) ? LD(f.a1qv, o3 + L8) : 0.0;
+  const double qc1 = LD(f.a1qc, o3), qc1m = (k >= 2) ? LD(f.a1qc, o3 - L8) : 0.0;
+  const double qc1p = (k < kz) ? LD(f.a1qc, o3 + L8) : 0.0;
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int n = 0; n < NA; n++) {
     const int t = tid + n * SBT, jj = t % SDW, ii = t / SDW;
@@ -1079,6 +1159,9 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   __syncthreads();
   PT_MARK();
   if (!valid) return;
+  // (the atm2 values of the point, which only the forecasts at the end of each chain read: lines
+  // this block has just staged, loaded behind the barrier to keep registers free ahead of it)
+  const double t2 = LD(f.a2t, o3), qv2 = LD(f.a2qv, o3), qc2 = LD(f.a2qc, o3);
 #define DT(S, dj, di) S[ti + (di)][tj + (dj)]
   // calc_coeff Smagorinsky xkc, Main/mod_diffusion.F90:194-210 (ubd3d/vbd3d = atm2 * (1/psdotb))
   double xkc;
@@ -1127,24 +1210,14 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     double t0 = td;
     if constexpr (BUD) bud(b.t[0], td, d_zero);
     // vadv3d ind = 1 (Main/mod_advection.F90:771-783): pf/pb from psb (mkslice :263-271)
-    {
-      const double ptop = c->ptop, c287 = c->c287;
-#define PF(K) ((c->sigma[K] * pb + ptop) * d_1000)
-#define PB(K) ((c->hsigma[K] * pb + ptop) * d_1000)
-      if (k >= 2)
-        td = td + (q0 * (c->twt1[k] * t1 * powpos(PF(k) / PB(k), c287) +
-                         c->twt2[k] * t1m * powpos(PF(k) / PB(k - 1), c287))) * c->xds[k];
-      if (k + 1 <= kz)
-        td = td - (q1 * (c->twt1[k + 1] * t1p * powpos(PF(k + 1) / PB(k + 1), c287) +
-                         c->twt2[k + 1] * t1 * powpos(PF(k + 1) / PB(k), c287))) * c->xds[k];
-#undef PB
-#undef PF
-    }
+    // (the two interface summands: vflux_t, formed under the staging loads)
+    if (k >= 2) td = td + vft.a;
+    if (k + 1 <= kz) td = td - vft.b;
     if constexpr (BUD) { bud(b.t[1], td, t0); t0 = td; }
     // omega, Main/mod_tendency.F90:1200-1214
     double om;
     {
-      const double dummy = d_one / (c->dx8 * mx);
+      const double dummy = rdx8m;                   // 1 / (dx8 msfx), formed under the staging loads
       const double su = DT(sUD, 0, 0) + DT(sUD, 0, 1) + DT(sUD, 1, 1) + DT(sUD, 1, 0);
       const double sv = DT(sVD, 0, 0) + DT(sVD, 0, 1) + DT(sVD, 1, 1) + DT(sVD, 1, 0);
       const double x = su * (H1T(sPS, 1, 0) - H1T(sPS, -1, 0)) + sv * (H1T(sPS, 0, 1) - H1T(sPS, 0, -1));
@@ -1156,7 +1229,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
       const double qv = H1T(sXQV, 0, 0);
       const double tv = H1T(sXT, 0, 0) * (d_one + c->ep1 * qv);
       const double rovcpm = c->rgas / (c->cpd * (d_one + 0.80 * qv));
-      td = td + (om * rovcpm * tv) / (c->ptop * rp + c->hsigma[k]);
+      td = td + (om * rovcpm * tv) / adiden;
     }
     if constexpr (BUD) { bud(b.t[2], td, t0); t0 = td; }
     // nudge3d (iboudy 1/5) or the sponge3d summand (iboudy 4, see k_momentum)
@@ -1202,18 +1275,10 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
                                                H1T(sXQV, 0, 1), 2);
   double tq0 = tq;
   if constexpr (BUD) bud(b.q[0], tq, d_zero);
-  {
-    const double thr = MINQQ * ps;
-    const double qc0 = qv1;
-    if (k >= 2) {
-      const double qm = qv1m;
-      tq = tq + q0 * ((qc0 > thr && qm > thr) ? qc0 * powpos(qm / qc0, c->qcon[k]) : d_zero) * c->xds[k];
-    }
-    if (k + 1 <= kz) {
-      const double qp = qv1p;
-      tq = tq - q1 * ((qp > thr && qc0 > thr) ? qp * powpos(qc0 / qp, c->qcon[k + 1]) : d_zero) * c->xds[k];
-    }
-  }
+  // vadvqv (:916-934)
+  const VPair vfq = vflux_qv(c, k, kz, ps, q0, q1, qv1, qv1m, qv1p);
+  if (k >= 2) tq = tq + vfq.a;
+  if (k + 1 <= kz) tq = tq - vfq.b;
   if constexpr (BUD) { bud(b.q[1], tq, tq0); tq0 = tq; }
   double spq = d_zero;
   if (rgc > 0 && O::iboudy(c) == 4) {
@@ -1260,20 +1325,10 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
     if (k >= 2) tc = tc + (uw_fg(c, k, kpb, qc1, qc1m, fk) * q0) * c->xds[k];
     if (k + 1 <= kz) tc = tc - (uw_fg(c, k + 1, kpb, qc1p, qc1, fk) * q1) * c->xds[k];
   } else {
-    const double thr = MINQQ * MINQQ * ps;
-    const double c0 = qc1;
-    if (k >= 2) {
-      const double cm = qc1m;
-      const double fl = (q0 > d_zero) ? ((cm > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero)
-                                      : ((c0 > thr) ? q0 * (c->twt1[k] * c0 + c->twt2[k] * cm) : d_zero);
-      tc = tc + fl * c->xds[k];
-    }
-    if (k + 1 <= kz) {
-      const double cp = qc1p;
-      const double fl = (q1 > d_zero) ? ((c0 > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero)
-                                      : ((cp > thr) ? q1 * (c->twt1[k + 1] * cp + c->twt2[k + 1] * c0) : d_zero);
-      tc = tc - fl * c->xds[k];
-    }
+    // vadv4d ind = 1
+    const VPair vfc = vflux_qc(c, k, kz, ps, q0, q1, qc1, qc1m, qc1p);
+    if (k >= 2) tc = tc + vfc.a;
+    if (k + 1 <= kz) tc = tc - vfc.b;
   }
   tc = diffu(tc, sQCB, f.d6qc);
 #undef DT
