@@ -508,6 +508,69 @@ int rcmdyn_get_tracer(rcmdyn_t* h, int32_t field, int32_t itr, double* dst,
  * put.  Read only for iboudy 1 and 5 (Main/mod_tendency.F90:1506). */
 int rcmdyn_put_tracer_nudge(rcmdyn_t* h, const double* cefc, const double* cegc);
 
+/* Cumulus mixing of the tracers inside tend (the reference's `call cumtran(atm1%chi,atm2%chi)` for
+ * ichcumtra = 1, Main/mod_tendency.F90:595-603, Main/chemlib/mod_che_cumtran.F90:118-167): off by
+ * default.  When on, a tend whose clock before its advance has lcount > 0 (rcmtimer%integrating)
+ * and lcount % ncum == 0 (syncro_cum%act, ncum = dtcum / dtsec in steps) mixes every tracer, after
+ * the time filter and before the clock advance, at the interior cross points where DOTRAN is set
+ * and KTOP > 0: with kctop = max(KTOP, 4), deltas and the two column means are summed over
+ * k = kctop .. kz in that order, and both time levels take x * (1 - cumfrc) + cumfrc * xbar /
+ * deltas there.  kctop > kz leaves the column as it is.  The operations and their order are the
+ * Fortran text's.  The producers of the three inputs (init_cumtran's mask from cveg2d and icup, the
+ * convection scheme's kcumtop and convcldfra) stay the host's.
+ *
+ * rcmdyn_set_cumtran: refused while no tracers are declared and for ncum < 1, the switch staying
+ * as it was.  Goes through the engine's state machine like rcmdyn_set_condtq (ncum is a kernel
+ * argument: the captured graphs are dropped).  A switch-on from off starts from zeroed inputs
+ * (KTOP = 0 mixes nothing, so no tend waits for a put).  rcmdyn_set_tracers with another count
+ * switches it off and frees its buffers.
+ * rcmdyn_put_cumtran / rcmdyn_get_cumtran: one input (enum rcmdyn_cumtran_field), layout, bounds
+ * and box rules as rcmdyn_put_tracer (the 2-D fields with k1 = k2 = 1), a band's wrapped frame
+ * columns included:
+ *   CUM_DOTRAN  2-D, 0 or 1
+ *   CUM_KTOP    2-D, kcumtop as doubles holding integers in 0 .. kz (like KPBL)
+ *   CUM_CLDFRA  kz levels, convcldfra, finite and in [0, 1]
+ * A value outside those sets refuses the whole put.  A put writes the buffers the captured graphs
+ * read: it drops nothing.  Both fail while the switch is off and for an unknown field. */
+enum rcmdyn_cumtran_field { RCMDYN_CUM_DOTRAN = 0, RCMDYN_CUM_KTOP, RCMDYN_CUM_CLDFRA, RCMDYN_NCUMFIELDS };
+int rcmdyn_set_cumtran(rcmdyn_t* h, int32_t on, int32_t ncum);
+int rcmdyn_put_cumtran(rcmdyn_t* h, int32_t field, const double* src,
+                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_get_cumtran(rcmdyn_t* h, int32_t field, double* dst,
+                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+
+/* Tracer budget (the reference's ichdiag > 0): the accumulators of the five ten2diag calls on
+ * aten%chi (Main/mod_tendency.F90:1403-1412, 1503-1511, 1540-1542) and of cumtran (Main/chemlib/
+ * mod_che_cumtran.F90:124-130, 159-166), kz levels per tracer, on the interior cross points:
+ *   TRDIAG_ADVH  cadvhdiag += chidyn * rw after hadv (the running sum is 0 + hadv)
+ *   TRDIAG_ADVV  cadvvdiag += (chidyn after vadv - after hadv) * rw
+ *   TRDIAG_BDY   cbdydiag  += (after nudge_chi - before) * rw; booked on every iboudy, + 0.0 where
+ *                nothing is relaxed (iboudy other than 1 / 5, or zero tables)
+ *   TRDIAG_DIFH  cdifhdiag += (after diffu_x - before) * rw
+ *   TRDIAG_CONV  cconvdiag += (atm2 after cumtran - before) / dt * 2 * cfdout, in a tend where
+ *                cumtran acts (with cumtran off it stays zero)
+ * Each stage term is the rounded difference of two running sums times rw, then added, as
+ * extracttenchi forms it (:2177-2207).  rw is alarm_out_atm%rw, cfdout alarm_out_che%rw
+ * (Main/chemlib/mod_che_start.F90:341).  The prognostic results are identical with the budget on
+ * or off.  The boundary-layer, convection-scheme, emission, deposition and chemistry diagnostics
+ * (ctbldiag, the scheme's own cconvdiag share, ...) stay the host's.
+ *
+ * rcmdyn_set_tracer_budget: refused without tracers and for a non-finite factor.  The switch or a
+ * changed factor drops the captured graphs, as rcmdyn_set_budget does; the sums start at zero at
+ * a switch-on from off.  rcmdyn_set_tracers with another count switches it off and frees it.
+ * rcmdyn_get_tracer_budget: one term (enum rcmdyn_tracer_diag) of tracer itr = 1..ntr, box rules
+ * as rcmdyn_get_budget; refused while off and for a term or itr out of range.
+ * rcmdyn_reset_tracer_budget: zeroes every sum (the host does it after writing them at
+ * alarm_out_che).  There is no put: the reference does not carry the sums through SAV. */
+enum rcmdyn_tracer_diag {
+  RCMDYN_TRDIAG_ADVH = 0, RCMDYN_TRDIAG_ADVV, RCMDYN_TRDIAG_BDY, RCMDYN_TRDIAG_DIFH, RCMDYN_TRDIAG_CONV,
+  RCMDYN_NTRDIAG
+};
+int rcmdyn_set_tracer_budget(rcmdyn_t* h, int32_t on, double rw, double cfdout);
+int rcmdyn_get_tracer_budget(rcmdyn_t* h, int32_t term, int32_t itr, double* dst,
+                             int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_reset_tracer_budget(rcmdyn_t* h);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

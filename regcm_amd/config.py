@@ -109,6 +109,12 @@ FIELD = {n: i for i, n in enumerate(FIELD_NAMES)}
 TRACER_FIELDS = ["ATM1", "ATM2", "PHY", "B0", "BT", "CHIB3D"]
 TRACER_FIELD = {n: i for i, n in enumerate(TRACER_FIELDS)}
 MAXTR = 96           # RCMDYN_MAXTR
+# enum rcmdyn_cumtran_field: the inputs of the tracers' cumulus mixing (init_cumtran's mask, kcumtop,
+# convcldfra); enum rcmdyn_tracer_diag: the terms of the tracer budget (ichdiag > 0)
+CUMTRAN_FIELDS = ["DOTRAN", "KTOP", "CLDFRA"]
+CUMTRAN_FIELD = {n: i for i, n in enumerate(CUMTRAN_FIELDS)}
+TRACER_DIAG_TERMS = ["ADVH", "ADVV", "BDY", "DIFH", "CONV"]
+TRACER_DIAG_TERM = {n: i for i, n in enumerate(TRACER_DIAG_TERMS)}
 TWO_D = {"PSA", "PSB", "MSFX", "MSFD", "CORIOL", "HT", "XPSB_B0", "XPSB_BT", "PSC",
          "PTEN", "PSDOTA", "ATM0_PS", "DPSDXM", "DPSDYM", "EF", "DDX", "DDY", "DMDX", "DMDY",
          "EX", "CRX", "CRY", "ATMS_PS2D", "ATMS_RHOX2D", "XPSB_B1", "ATM0_PSDOT", "KPBL"}

@@ -788,7 +788,8 @@ struct rcmdyn_engine {
                     {(const void*)k_update<OptGeneric, Budget>, SBT, "k_update<OptGeneric, Budget>"},
                     {(const void*)k_scalars<OptGeneric, Budget>, SBT, "k_scalars<OptGeneric, Budget>"},
                     {(const void*)k_qx_tend<FamQx>, QBT, "k_qx_tend<FamQx>"},
-                    {(const void*)k_qx_tend<FamTr>, QBT, "k_qx_tend<FamTr>"}};
+                    {(const void*)k_qx_tend<FamTr>, QBT, "k_qx_tend<FamTr>"},
+                    {(const void*)k_qx_tend<FamTr, TrBudget>, QBT, "k_qx_tend<FamTr, TrBudget>"}};
     for (const K& k : ks) {
       hipFuncAttributes a{};
       HIPCHK(hipFuncGetAttributes(&a, k.f));
@@ -1576,7 +1577,11 @@ struct rcmdyn_engine {
       t.trdep = t.trdepf = nullptr;
       t.trtab[0] = t.trtab[1] = nullptr;
       t.trsout = nullptr;
+      t.cum[0] = t.cum[1] = t.cum[2] = nullptr;
+      t.trbud.clear();
+      t.trbudtab = nullptr;
     }
+    cumtran = trbudget = false;
     if (tr_cefc) (void)hipFree(tr_cefc);
     if (tr_cegc) (void)hipFree(tr_cegc);
     tr_cefc = tr_cegc = nullptr;
@@ -1715,7 +1720,128 @@ struct rcmdyn_engine {
     if (nz != tr_relax) invalidate_graphs();         // the term's switch is a kernel argument
     tr_relax = nz;
   }
-  // tend's tracer launches after the forecast's exchange: the fix and filter, the serial chains
+  // Cumulus mixing of the tracers (cumtran, Main/chemlib/mod_che_cumtran.F90:118-167) inside tend:
+  // the switch, the host's three inputs and their read.  The inputs are the tiles' (Tile::cum,
+  // allocated at the first switch-on, freed with the tracers, zeroed at every switch-on from off);
+  // ncum is a kernel argument, so the captured graphs are dropped when it or the switch changes.  A
+  // put writes the buffers the graphs already point to.
+  bool cumtran = false;
+  int cum_ncum = 1;
+  void set_cumtran(int on, int ncum) {
+    if (on) {
+      if (ntr == 0) throw std::runtime_error("rcmdyn_set_cumtran: no tracers are declared (rcmdyn_set_tracers)");
+      if (ncum < 1) throw std::runtime_error("rcmdyn_set_cumtran: ncum must be at least 1 (dtcum / dtsec in steps)");
+    }
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    const bool b = on != 0;
+    if (b == cumtran && (!b || ncum == cum_ncum)) return;
+    if (b && !cumtran)
+      for (auto& t : tiles)
+        for (int q = 0; q < RCMDYN_NCUMFIELDS; q++) {
+          const size_t n = (size_t)t.g.plane * cum_levels(q);
+          if (!t.cum[q]) t.cum[q] = tr_alloc<double>(t, n);
+          else HIPCHK(hipMemset(t.cum[q], 0, n * sizeof(double)));
+        }
+    invalidate_graphs();
+    cumtran = b;
+    if (b) cum_ncum = ncum;
+  }
+  int cum_levels(int field) const { return field == RCMDYN_CUM_CLDFRA ? cfg.kz : 1; }
+  void cumtran_check(const char* who, int field) const {
+    if (!cumtran) throw std::runtime_error(std::string(who) + ": cumtran is off (rcmdyn_set_cumtran)");
+    if (field < 0 || field >= RCMDYN_NCUMFIELDS) throw std::runtime_error(std::string(who) + ": unknown cumtran field");
+  }
+  void put_cumtran(int field, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+    cumtran_check("rcmdyn_put_cumtran", field);
+    const int nk = cum_levels(field);
+    const size_t n = (size_t)std::max(0, j2 - j1 + 1) * std::max(0, i2 - i1 + 1) * (nk == 1 ? 1 : std::max(0, k2 - k1 + 1));
+    for (size_t q = 0; q < n; q++) {
+      const double v = src[q];
+      if (field == RCMDYN_CUM_DOTRAN && v != 0.0 && v != 1.0)
+        throw std::runtime_error("rcmdyn_put_cumtran: CUM_DOTRAN must hold 0 or 1");
+      if (field == RCMDYN_CUM_KTOP && (!(v >= 0.0) || !(v <= cfg.kz) || v != std::floor(v)))
+        throw std::runtime_error("rcmdyn_put_cumtran: CUM_KTOP must hold integers in 0 .. kz");
+      if (field == RCMDYN_CUM_CLDFRA && (!(v >= 0.0) || !(v <= 1.0)))
+        throw std::runtime_error("rcmdyn_put_cumtran: CUM_CLDFRA must be finite and lie in [0, 1]");
+    }
+    settle();                                        // a pending lazy tend reads the previous values
+    HIPCHK(hipStreamSynchronize(stream));
+    for (auto& t : tiles) scatter_box(t, t.cum[field], nk, src, j1, j2, i1, i2, nk == 1 ? 1 : k1, nk == 1 ? 1 : k2);
+  }
+  void get_cumtran(int field, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    cumtran_check("rcmdyn_get_cumtran", field);
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    const int nk = cum_levels(field);
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      gather_box(t, t.cum[field], nk, dst, j1, j2, i1, i2, nk == 1 ? 1 : k1, nk == 1 ? 1 : k2, g.jde1, g.jde2, g.ide1,
+                 g.ide2);
+    }
+  }
+  TrCum cum_args(const Tile& t) const {
+    return TrCum{t.cum[0], t.cum[1], t.cum[2], trbudget ? t.trbudtab + RCMDYN_TRDIAG_CONV * ntr : nullptr, trb_cfdout,
+                 cum_ncum};
+  }
+
+  // Tracer budget (ichdiag > 0): the switch, the host's read and its reset.  The accumulators
+  // [term][tracer] are the tiles' (allocated at the first switch-on, freed with the tracers, zeroed
+  // at every switch-on from off), their pointer table a device array; rw and cfdout are kernel
+  // arguments and the switch selects other kernel instances, so the captured graphs are dropped when
+  // any of them changes.
+  bool trbudget = false;
+  double trb_rw = 1.0, trb_cfdout = 1.0;
+  void set_tracer_budget(int on, double rw, double cfdout) {
+    if (on) {
+      if (ntr == 0) throw std::runtime_error("rcmdyn_set_tracer_budget: no tracers are declared (rcmdyn_set_tracers)");
+      if (!std::isfinite(rw)) throw std::runtime_error("rcmdyn_set_tracer_budget: rw must be finite");
+      if (!std::isfinite(cfdout)) throw std::runtime_error("rcmdyn_set_tracer_budget: cfdout must be finite");
+    }
+    settle();                                        // a lazy tend replays its graph first
+    HIPCHK(hipStreamSynchronize(stream));
+    const bool b = on != 0;
+    if (b == trbudget && (!b || (rw == trb_rw && cfdout == trb_cfdout))) return;
+    if (b && !trbudget)
+      for (auto& t : tiles) {
+        const size_t P3 = (size_t)t.g.plane * cfg.kz;
+        if (t.trbud.empty()) {
+          for (int q = 0; q < NTRBUDTERM * ntr; q++) t.trbud.push_back(tr_alloc<double>(t, P3));
+          t.trbudtab = tr_alloc<double*>(t, t.trbud.size());
+          HIPCHK(hipMemcpy(t.trbudtab, t.trbud.data(), sizeof(double*) * t.trbud.size(), hipMemcpyHostToDevice));
+        } else {
+          for (double* d : t.trbud) HIPCHK(hipMemset(d, 0, P3 * sizeof(double)));
+        }
+      }
+    invalidate_graphs();
+    trbudget = b;
+    if (b) { trb_rw = rw; trb_cfdout = cfdout; }
+  }
+  void get_tracer_budget(int term, int itr, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    if (!trbudget) throw std::runtime_error("rcmdyn_get_tracer_budget: the tracer budget is off (rcmdyn_set_tracer_budget)");
+    if (term < 0 || term >= RCMDYN_NTRDIAG) throw std::runtime_error("rcmdyn_get_tracer_budget: unknown budget term");
+    if (itr < 1 || itr > ntr)
+      throw std::runtime_error("rcmdyn_get_tracer_budget: itr must lie in 1 .. ntr = " + std::to_string(ntr));
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
+    check_now();
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      gather_box(t, t.trbud[term * ntr + itr - 1], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
+    }
+  }
+  void reset_tracer_budget() {
+    if (!trbudget) throw std::runtime_error("rcmdyn_reset_tracer_budget: the tracer budget is off (rcmdyn_set_tracer_budget)");
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
+    for (auto& t : tiles)
+      for (double* d : t.trbud) HIPCHK(hipMemset(d, 0, (size_t)t.g.plane * cfg.kz * sizeof(double)));
+  }
+  TrBudget trbud_args(const Tile& t) const { return TrBudget{t.trbudtab, trb_rw, ntr}; }
+
+  // tend's tracer launches after the forecast's exchange: the fix and filter, the serial chains,
+  // then (cumtran on) the cumulus mixing of the filtered levels, ahead of the step's clock advance
   void tracer_fix(Tile& t) {
     const Geom& g = t.g;
     const int kz = cfg.kz, ng = tr_groups();
@@ -1725,6 +1851,9 @@ struct rcmdyn_engine {
                sizeof(double) * negfix_lds(g), stream, g, dc, tr_args(t));
     KLAUNCH_AS("k_tr_post", k_qx_post<FamTr>, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, ng * NQXH * kz), BLK, 0,
                stream, g, dc, tr_args(t));
+    if (cumtran)
+      KLAUNCH(k_tr_cumtran, grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, ntr), BLK, 0, stream, g, dc, ds, tr_args(t),
+              ntr, cum_args(t));
   }
   // chem_bdyval_coupled of every tile; integ / pre_clock as k_bdyval_chi
   void tracer_bdyval(int integ, int pre_clock) {
@@ -2576,10 +2705,15 @@ struct rcmdyn_engine {
       });
     }
     // the tracers' chains after it on the same stream, a group of NQXH per z slice of kz levels
-    if (ntr)
-      KLAUNCH_AS("k_nh_tr_tend", k_nh_qx_tend<FamTr>,
-                 grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, tr_groups() * cfg.kz), BLK, 0, stream, g, dc, ds, f,
-                 tr_args(t));
+    if (ntr) {
+      const dim3 tg = grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, tr_groups() * cfg.kz);
+      if (trbudget) {
+        constexpr auto kern = k_nh_qx_tend<FamTr, TrBudget>;
+        KLAUNCH_AS("k_nh_tr_tend<budget>", kern, tg, BLK, 0, stream, g, dc, ds, f, tr_args(t), trbud_args(t));
+      } else {
+        KLAUNCH_AS("k_nh_tr_tend", k_nh_qx_tend<FamTr>, tg, BLK, 0, stream, g, dc, ds, f, tr_args(t));
+      }
+    }
   }
   // the forecasts exchanged after the tendency kernels (atmc%qx, :381)
   std::vector<XField> cq_fields() const {
@@ -2811,9 +2945,13 @@ struct rcmdyn_engine {
       each([&](Tile& t) {
         const Geom& g = t.g;
         const Fields f = fields(t);
-        KLAUNCH_AS("k_tr_tend", k_qx_tend<FamTr>,
-                   dim3((g.jcx2() - g.jcx1() + QBJ) / QBJ, (g.icx2() - g.icx1() + QBI) / QBI, tr_groups() * kz),
-                   dim3(QBT), 0, stream, g, dc, ds, f, tr_args(t));
+        const dim3 tg((g.jcx2() - g.jcx1() + QBJ) / QBJ, (g.icx2() - g.icx1() + QBI) / QBI, tr_groups() * kz);
+        if (trbudget) {
+          constexpr auto kern = k_qx_tend<FamTr, TrBudget>;
+          KLAUNCH_AS("k_tr_tend<budget>", kern, tg, dim3(QBT), 0, stream, g, dc, ds, f, tr_args(t), trbud_args(t));
+        } else {
+          KLAUNCH_AS("k_tr_tend", k_qx_tend<FamTr>, tg, dim3(QBT), 0, stream, g, dc, ds, f, tr_args(t));
+        }
       });
       if (!fused) {
         std::vector<XField> cq;
@@ -3602,6 +3740,33 @@ int rcmdyn_get_tracer(rcmdyn_t* h, int32_t field, int32_t itr, double* dst, int3
 
 int rcmdyn_put_tracer_nudge(rcmdyn_t* h, const double* cefc, const double* cegc) {
   return guard(h, [&] { h->put_tracer_nudge(cefc, cegc); });
+}
+
+int rcmdyn_set_cumtran(rcmdyn_t* h, int32_t on, int32_t ncum) {
+  return guard(h, [&] { h->set_cumtran(on, ncum); });
+}
+
+int rcmdyn_put_cumtran(rcmdyn_t* h, int32_t field, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                       int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->put_cumtran(field, src, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_get_cumtran(rcmdyn_t* h, int32_t field, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                       int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_cumtran(field, dst, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_set_tracer_budget(rcmdyn_t* h, int32_t on, double rw, double cfdout) {
+  return guard(h, [&] { h->set_tracer_budget(on, rw, cfdout); });
+}
+
+int rcmdyn_get_tracer_budget(rcmdyn_t* h, int32_t term, int32_t itr, double* dst, int32_t j1, int32_t j2, int32_t i1,
+                             int32_t i2, int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_tracer_budget(term, itr, dst, j1, j2, i1, i2, k1, k2); });
+}
+
+int rcmdyn_reset_tracer_budget(rcmdyn_t* h) {
+  return guard(h, [&] { h->reset_tracer_budget(); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

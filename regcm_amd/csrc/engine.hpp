@@ -219,6 +219,12 @@ struct Tile {
   unsigned *trdep = nullptr, *trdepf = nullptr;
   void* trtab[2] = {nullptr, nullptr};
   double** trsout = nullptr;
+  // cumtran's inputs (rcmdyn_set_cumtran), in rcmdyn_cumtran_field order: dotran and kcumtop (2-D),
+  // convcldfra; the tracer budget's accumulators [term * ntr + tracer] (rcmdyn_set_tracer_budget)
+  // and their pointer table in device memory; all among tr_allocs
+  double* cum[RCMDYN_NCUMFIELDS] = {};
+  std::vector<double*> trbud;
+  double** trbudtab = nullptr;
   std::vector<void*> tr_allocs;
   unsigned *depplane;              // per (n,k) plane: bitmap of the rows with a serially dependent negative point
   int* negcnt = nullptr;           // hydrostatic qfuse: the negative forecasts k_scalars listed

@@ -206,6 +206,32 @@ struct TrArgs {
   int ngroups, relax;
 };
 
+// Tracer budget (ichdiag > 0, rcmdyn_set_tracer_budget): the accumulators cadvhdiag, cadvvdiag,
+// cbdydiag, cdifhdiag of the five ten2diag calls on aten%chi (Main/mod_tendency.F90:1403-1412,
+// 1503-1511, 1540-1542) and cconvdiag of cumtran (Main/chemlib/mod_che_cumtran.F90:159-166), one
+// frame array of kz levels per (term, tracer): acc[term * ntr + tracer] in device memory.  A
+// trailing argument of its own of the budget instances k_qx_tend<FamTr, TrBudget> and
+// k_nh_qx_tend<FamTr, TrBudget> (as Budget of the t / qv kernels); the other instances take none
+// and hold no code for it.  Each stage term is the rounded difference of the running chidyn around
+// its stage, acc = acc + (after - before) * rw, on the tile's own jci x ici.
+constexpr int NTRBUDTERM = RCMDYN_NTRDIAG;     // advh, advv, bdy, difh, conv
+struct TrBudget {
+  double* const* acc;
+  double rw;                   // alarm_out_atm%rw (extracttenchi, :2177-2207)
+  int ntr;
+};
+
+// Cumulus mixing of the tracers (cumtran, rcmdyn_set_cumtran): init_cumtran's mask (0 / 1) and
+// kcumtop (2-D, doubles holding integers), convcldfra (kz levels); ncum: syncro_cum's period in
+// steps; conv / cfdout: cconvdiag's accumulators [tracer] and alarm_out_che%rw, conv null with the
+// tracer budget off
+struct TrCum {
+  const double *dotran, *ktop, *cldfra;
+  double* const* conv;
+  double cfdout;
+  int ncum;
+};
+
 // The two families of the kernels of species.hip and of the serial negative-value fix
 // (qxcommon.hpp), a compile-time parameter F: what differs between the reference's chain of a
 // hydrometeor beyond qc and of a tracer.
@@ -317,9 +343,10 @@ __global__ void k_copy_frame(Geom g, Geom w, int nplanes, const double* __restri
 
 // species.hip: the hydrometeors beyond qc (nqx = 5), hydrostatic core (the ping-pong buffers)
 // F: the family (FamQx, FamTr above); species.hip instantiates both of each kernel
-template <class F>
+// B...: empty, or TrBudget for the tracers' budget instance (k_qx_tend, k_nh_qx_tend)
+template <class F, class... B>
 __global__ void k_qx_tend(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, Fields f,
-                          typename F::Args a);
+                          typename F::Args a, B... b);
 template <class F>
 __global__ void k_qx_fix(Geom g, const Consts* __restrict__ c, typename F::Args a);
 template <class F>
@@ -330,9 +357,14 @@ __global__ void k_negfix_serial_qx(Geom g, const Consts* __restrict__ c, QFix qf
 struct NHFields;
 // the non-hydrostatic chains of the same hydrometeors (in place; k_qx_fix / k_qx_serial then
 // run with b* = a*)
-template <class F>
+template <class F, class... B>
 __global__ void k_nh_qx_tend(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, NHFields f,
-                             typename F::Args a);
+                             typename F::Args a, B... b);
+// cumtran2 (Main/chemlib/mod_che_cumtran.F90:132-166) on the filtered time levels b1 / b2 of every
+// tracer at the tile's own jci x ici, a thread per (j, i, tracer); acts when lcount > 0 and
+// lcount % ncum == 0 (rcmtimer%integrating, syncro_cum%act)
+__global__ void k_tr_cumtran(Geom g, const Consts* __restrict__ c, const StepState* __restrict__ s, TrArgs a, int ntr,
+                             TrCum cu);
 // chem_bdyval_coupled, ichebdy = 1 (Main/chemlib/mod_che_bdyco.F90:565-758), one block per
 // (level, tracer); integ as k_bdyval_qx; pre_clock: the step's clock is not advanced yet (the
 // bdyval lines ran in k_split_correct_bdy), so dt is the one the advance will set

@@ -28,6 +28,9 @@
 // family FamTr (kernels.hpp): no decoupling floor, vadv4d ind = 2, the fix factor 0.1, no NH cr
 // term, nudge_chiten between advection and diffusion; k_bdyval_chi is chem_bdyval_coupled and
 // k_tr_slice the chib3d export.  Up to NQXH tracers share a block, the group on the grid's z.
+// Two switches complete tend's tracer chain: k_tr_cumtran (rcmdyn_set_cumtran) mixes the filtered
+// levels over the convective column, and the TrBudget instances of the two tendency kernels
+// (rcmdyn_set_tracer_budget) book the ichdiag terms.
 //
 // Transcendental-free: every result is bit-identical to the oracle's restatement
 // (-ffp-contract=off).
@@ -51,9 +54,16 @@ constexpr int QW2 = QBJ + 4, QH2 = QBI + 4;    // halo 2
 // would deliver), one level per block.  Reads the scaled diffusion coefficient k_scalars
 // stored (xkc * rdxsq * p*b at the interior points) and qdot of k_columns.
 // F: the family (kernels.hpp).  A tracer launch carries its groups on z = group * kz + level.
-template <class F>
+// B...: TrBudget for the tracers' budget instance (rcmdyn_set_tracer_budget): it snapshots the
+// running chidyn around each stage as tend does with chiten0 (Main/mod_tendency.F90:1403-1412,
+// 1503-1511, 1540-1542) and adds the difference times rw to the stage's accumulator
+// (extracttenchi, :2177-2207) at the tile's own jci x ici; the ring's forecasts book nothing.
+template <class F, class... B>
 __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restrict__ c,
-                                                 const StepState* __restrict__ s, Fields f, typename F::Args fa) {
+                                                 const StepState* __restrict__ s, Fields f, typename F::Args fa,
+                                                 B... xb) {
+  constexpr bool BUD = pack_has<TrBudget, B...>;
+  const TrBudget bd = pack_get<TrBudget>(xb...);
   __shared__ double sUMC[QDH][QDW], sVMC[QDH][QDW];
   __shared__ double sX[NQXH][QH1][QW1];          // atmx%qx = max(atm1 * rpsa, 0) (tracers: no floor), halo 1
   __shared__ double sB[NQXH][QH2][QW2];          // qxb3d = max(atm2 * (1/psb), 0), halo 2
@@ -117,14 +127,24 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
   const double vavg1 = sVMC[ti][tj + 1] + sVMC[ti][tj];
   const double vavg2 = sVMC[ti + 1][tj + 1] + sVMC[ti + 1][tj];
   const int kpb = f.kpbl ? (int)LD(f.kpbl, o2) : 0;
+  const bool bown = BUD && in(j, g.jci1, g.jci2) && in(i, g.ici1, g.ici2);
   for (int n = 0; n < nsp; n++) {
     const int b1 = tj + 1, a1 = ti + 1, b2 = tj + 2, a2 = ti + 2;
+    // the budget instance: acc = acc + (after - before) * rw of term m for this tracer
+    auto bud = [&](int m, double x) {
+      if (bown) {
+        double* acc = bd.acc[m * bd.ntr + grp * NQXH + n];
+        ST(acc, o3, LD(acc, o3) + x * bd.rw);
+      }
+    };
+    [[maybe_unused]] double t0 = d_zero;     // chiten0: the running chidyn before the stage
 #define X1(dj, di) sX[n][a1 + (di)][b1 + (dj)]
     // hadvqx (:639-653), or the semi-Lagrangian start of qxdyn (:1378-1380)
     double tq = c->isladvec ? LD(q.sl[n], o3)
                             : d_zero + hadv_flux(c, xm, ps, uavg1, uavg2, vavg1, vavg2, X1(0, 0), X1(-1, 0),
                                                  X1(1, 0), X1(0, -1), X1(0, 1), 0);
 #undef X1
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_ADVH, tq); t0 = tq; }
     // vadv4d (:859-961): ind = 1, or 3 with iuwvadv = 1 (the PBL-top rule at kpbl)
     const double* qa = q.a1[n];
     const double c0 = LD(qa, o3);
@@ -146,6 +166,7 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
         tq = tq - fl * c->xds[k];
       }
     }
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_ADVV, tq - t0); t0 = tq; }
     // nudge_chiten, ichebdy = 1 (Main/chemlib/mod_che_bdyco.F90:898-982), on atm2 (Main/
     // mod_tendency.F90:1507) between the advection and the diffusion: the band's south / north
     // points sum fls1..4 as west, east, south, north, its west / east points as south, north,
@@ -162,12 +183,15 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
 #undef FLS
       }
     }
+    // cbdydiag is booked on every iboudy (:1503-1511): + 0.0 where nothing was relaxed
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_BDY, tq - t0); t0 = tq; }
     // diffu_x4d on the mkslice field qxb3d; idiffu = 3: k_diffu6's column term (as k_scalars)
     if (c->idiffu == 3) {
       if (j == g.jci2 || (!g.bl && j == g.jce1 - 1)) tq = tq + LD(q.d6[n], o3);
     } else {
       tq = diffu_x(g, c, j, i, tq, xkcs, [&](int dj, int di) { return sB[n][a2 + di][b2 + dj]; });
     }
+    if constexpr (BUD) bud(RCMDYN_TRDIAG_DIFH, tq - t0);
     // qxten = (0 + qxdyn) + qxphy (:332-335); the forecast (:375-380)
     tq = (d_zero + tq) + (q.phy[n] ? LD(q.phy[n], o3) : d_zero);
     ST(q.cq[n], o3, LD(q.a2[n], o3) + dt * tq);
@@ -178,9 +202,14 @@ __global__ __launch_bounds__(QBT) void k_qx_tend(Geom g, const Consts* __restric
 // qi, qr, qs at the interior cross points (owned points only, as the NH tendency kernels):
 // hadvqx, vadv4d ind 1 / 3, + atmx%qx * cr (:1615-1617), diffu_x4d on the scaled xkcr, the
 // sums with qxphy, the forecast; the ring jce \ jci takes atm2.
-template <class F>
+// B...: TrBudget for the tracers' budget instance, the same four stages as k_qx_tend (no tracer has
+// an adiabatic term).
+template <class F, class... B>
 __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __restrict__ c,
-                                                    const StepState* __restrict__ s, NHFields f, typename F::Args fa) {
+                                                    const StepState* __restrict__ s, NHFields f, typename F::Args fa,
+                                                    B... xb) {
+  constexpr bool BUD = pack_has<TrBudget, B...>;
+  const TrBudget bd = pack_get<TrBudget>(xb...);
   const int j = g.jce1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int i = g.ice1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
   const int kz = c->kz;
@@ -212,6 +241,11 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
   for (int n = 0; n < nsp; n++) {
     const double* a = q.a1[n];
     double cd;
+    auto bud = [&](int m, double x) {
+      double* acc = bd.acc[m * bd.ntr + grp * NQXH + n];
+      F3(acc, j, i, k) = F3(acc, j, i, k) + x * bd.rw;
+    };
+    [[maybe_unused]] double t0 = d_zero;     // chiten0: the running chidyn before the stage
     if (c->isladvec) {
       cd = d_zero + F3(q.sl[n], j, i, k);
     } else {
@@ -220,6 +254,7 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
       const double xn = dec(F3(a, j, i + 1, k), rn);
       cd = d_zero + hadv_flux(c, xmf, ps, u1, u2, v1, v2, xc, xw, xe, xs, xn, 0);
     }
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_ADVH, cd); t0 = cd; }
     auto cflux = [&](int kk) {
       const double svv = F3(f.qdot, j, i, kk);
       const double fk = F3(a, j, i, kk), fkm = F3(a, j, i, kk - 1);
@@ -230,6 +265,7 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
     if (k >= 2) cd = cd + cflux(k) * c->xds[k];
     if (k + 1 <= kz) cd = cd - cflux(k + 1) * c->xds[k];
     if constexpr (F::cr) cd = cd + dmax(F3(a, j, i, k) * r0, d_zero) * cr;
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_ADVV, cd - t0); t0 = cd; }
     if constexpr (F::relax) {     // nudge_chiten, as in k_qx_tend
       const int rg = fa.relax ? (int)F2(f.rgcr, j, i) : 0;
       if (rg > 0) {
@@ -243,6 +279,7 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
 #undef FLS
       }
     }
+    if constexpr (BUD) { bud(RCMDYN_TRDIAG_BDY, cd - t0); t0 = cd; }
     if (c->idiffu == 3) {
       if (j == g.jci2) cd = cd + F3(q.d6[n], j, i, k);
     } else {
@@ -254,6 +291,7 @@ __global__ __launch_bounds__(256) void k_nh_qx_tend(Geom g, const Consts* __rest
       };
       cd = diffu_x(g, c, j, i, cd, xkc, fb);
     }
+    if constexpr (BUD) bud(RCMDYN_TRDIAG_DIFH, cd - t0);
     const double qt = d_zero + cd + (q.phy[n] ? F3(q.phy[n], j, i, k) : d_zero);
     F3(q.cq[n], j, i, k) = F3(q.a2[n], j, i, k) + dt * qt;
   }
@@ -467,17 +505,98 @@ __global__ void k_tr_slice(Geom g, int kz, int ntr, TrArgs a, const double* __re
   F3(out[n], j, i, k) = dmax(F3(a2, j, i, k) * F2(rpsb, j, i), d_zero);
 }
 
+// K_TR5.  cumtran2 (Main/chemlib/mod_che_cumtran.F90:132-156; tend calls it on atm1%chi, atm2%chi
+// after timefilter_apply and before the clock advance, Main/mod_tendency.F90:595-603): the mixing of
+// every tracer over the convective column, on the two filtered time levels b1 / b2 (the NH core: a1 /
+// a2 in place) at the tile's own jci x ici.  A thread per (j, i, tracer), lanes along j; the sums run
+// serially in k in the text's order.  The launch sits in the captured step, so the act test (rcmtimer%
+// integrating and syncro_cum%act on the clock of the tend being completed, wave-uniform) comes ahead of
+// every other load, and a wave whose columns are all non-convective leaves after the two 2-D loads.
+// cu.conv: cconvdiag (:159-166), the pseudo-tendency of atm2 with the tend's dt; every point of an
+// acting tend books it, the untouched ones (x - x) / dt * 2 * cfdout = + 0.0.
+__global__ __launch_bounds__(256) void k_tr_cumtran(Geom g, const Consts* __restrict__ c,
+                                                    const StepState* __restrict__ s, TrArgs a, int ntr, TrCum cu) {
+  const long long lc = s->lcount;
+  if (!(lc > 0 && lc % cu.ncum == 0)) return;
+  const int j = g.jci1 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = g.ici1 + (int)(blockIdx.y * blockDim.y + threadIdx.y);
+  const int n = (int)blockIdx.z;
+  if (j > g.jci2 || i > g.ici2 || n >= ntr) return;
+  const int kz = c->kz;
+  const bool mix = F2(cu.dotran, j, i) != d_zero;
+  const int ktop = (int)F2(cu.ktop, j, i);
+  const int kctop = mix && ktop > 0 ? (ktop > 4 ? ktop : 4) : kz + 1;
+  double* conv = cu.conv ? cu.conv[n] : nullptr;
+  if (kctop > kz && !conv) return;
+  const QxArgs& q = a.tab[n / NQXH];
+  double* xa = q.b1[n % NQXH];
+  double* xb = q.b2[n % NQXH];
+  // both passes walk the column in chunks of CK levels, the chunk's loads issued together (levels
+  // past kz load level kz and are not used): the sums still add one level after the other
+  constexpr int CK = 4;
+  double deltas = d_zero, chiabar = d_zero, chibbar = d_zero;
+  for (int k0 = kctop; k0 <= kz; k0 += CK) {
+    double va[CK], vb[CK];
+#pragma unroll
+    for (int u = 0; u < CK; u++) {
+      const int k = k0 + u <= kz ? k0 + u : kz;
+      va[u] = F3(xa, j, i, k);
+      vb[u] = F3(xb, j, i, k);
+    }
+#pragma unroll
+    for (int u = 0; u < CK; u++) {
+      if (k0 + u > kz) break;
+      const double ds = c->dsigma[k0 + u];
+      deltas = deltas + ds;
+      chiabar = chiabar + va[u] * ds;
+      chibbar = chibbar + vb[u] * ds;
+    }
+  }
+  const double dt = s->dt;
+  for (int k0 = conv ? 1 : kctop; k0 <= kz; k0 += CK) {
+    double va[CK], vb[CK], vf[CK], vc[CK];
+#pragma unroll
+    for (int u = 0; u < CK; u++) {
+      const int k = k0 + u <= kz ? k0 + u : kz;
+      va[u] = F3(xa, j, i, k);
+      vb[u] = F3(xb, j, i, k);
+      vf[u] = F3(cu.cldfra, j, i, k);
+      vc[u] = conv ? F3(conv, j, i, k) : d_zero;
+    }
+#pragma unroll
+    for (int u = 0; u < CK; u++) {
+      const int k = k0 + u;
+      if (k > kz) break;
+      const double b0 = vb[u];
+      double bn = b0;
+      if (k >= kctop) {
+        const double cumfrc = vf[u];
+        F3(xa, j, i, k) = va[u] * (d_one - cumfrc) + cumfrc * chiabar / deltas;
+        bn = b0 * (d_one - cumfrc) + cumfrc * chibbar / deltas;
+        F3(xb, j, i, k) = bn;
+      }
+      if (conv) F3(conv, j, i, k) = vc[u] + (bn - b0) / dt * d_two * cu.cfdout;
+    }
+  }
+}
+
 // the instances of both families
+#define RCM_QX_TEND(F, ...)                                                                                        \
+  template __global__ void k_qx_tend<F, ##__VA_ARGS__>(Geom, const Consts* __restrict__,                           \
+                                                       const StepState* __restrict__, Fields, typename F::Args,   \
+                                                       ##__VA_ARGS__);                                             \
+  template __global__ void k_nh_qx_tend<F, ##__VA_ARGS__>(Geom, const Consts* __restrict__,                        \
+                                                          const StepState* __restrict__, NHFields,                 \
+                                                          typename F::Args, ##__VA_ARGS__);
 #define RCM_QX_INSTANCES(F)                                                                                        \
-  template __global__ void k_qx_tend<F>(Geom, const Consts* __restrict__, const StepState* __restrict__, Fields,   \
-                                        typename F::Args);                                                         \
-  template __global__ void k_nh_qx_tend<F>(Geom, const Consts* __restrict__, const StepState* __restrict__,        \
-                                           NHFields, typename F::Args);                                            \
+  RCM_QX_TEND(F)                                                                                                   \
   template __global__ void k_qx_fix<F>(Geom, const Consts* __restrict__, typename F::Args);                         \
   template __global__ void k_qx_serial<F>(Geom, const Consts* __restrict__, typename F::Args);                      \
   template __global__ void k_qx_post<F>(Geom, const Consts* __restrict__, typename F::Args);
 RCM_QX_INSTANCES(FamQx)
 RCM_QX_INSTANCES(FamTr)
+RCM_QX_TEND(FamTr, TrBudget)          // the tracers' budget instance
 #undef RCM_QX_INSTANCES
+#undef RCM_QX_TEND
 
 }  // namespace rcm

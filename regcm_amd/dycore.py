@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from .config import FIELD, TRACER_FIELD, RcmdynConfig, build_config, field_levels
+from .config import CUMTRAN_FIELD, FIELD, TRACER_DIAG_TERM, TRACER_FIELD, RcmdynConfig, build_config, field_levels
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RCMDYN_LIB selects an instrumented build (tools/phases.py); default: the in-tree engine
@@ -35,6 +35,8 @@ EXPORTED = [
     "rcmdyn_set_massck", "rcmdyn_get_massck",
     "rcmdyn_set_condtq", "rcmdyn_put_rh0adj", "rcmdyn_get_condtq",
     "rcmdyn_set_tracers", "rcmdyn_put_tracer", "rcmdyn_get_tracer", "rcmdyn_put_tracer_nudge",
+    "rcmdyn_set_cumtran", "rcmdyn_put_cumtran", "rcmdyn_get_cumtran",
+    "rcmdyn_set_tracer_budget", "rcmdyn_get_tracer_budget", "rcmdyn_reset_tracer_budget",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
@@ -101,6 +103,12 @@ def lib():
     L.rcmdyn_put_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
     L.rcmdyn_get_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
     L.rcmdyn_put_tracer_nudge.argtypes = [P, dp, dp]
+    L.rcmdyn_set_cumtran.argtypes = [P, i32, i32]
+    L.rcmdyn_put_cumtran.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_cumtran.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_set_tracer_budget.argtypes = [P, i32, ctypes.c_double, ctypes.c_double]
+    L.rcmdyn_get_tracer_budget.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_reset_tracer_budget.argtypes = [P]
     _lib = L
     return L
 
@@ -367,6 +375,52 @@ class DynCore:
             raise EngineError(f"put_tracer_nudge: the tables must have shape (kz, nspgx) = {(self.rc.kz, self.rc.nspgx)}")
         self._check(lib().rcmdyn_put_tracer_nudge(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                                   b.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    def set_cumtran(self, on: bool = True, ncum: int = 1):
+        """The tracers' cumulus mixing (cumtran, ichcumtra = 1) inside tend: it acts in a tend whose
+        clock has lcount > 0 and lcount % ncum == 0 (ncum = dtcum / dtsec).  The three inputs start
+        at zero (kcumtop = 0 mixes nothing) until put_cumtran."""
+        self._check(lib().rcmdyn_set_cumtran(self.h, 1 if on else 0, ncum))
+
+    def put_cumtran(self, name, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+        """One input (CUMTRAN_FIELDS name or number): DOTRAN (0 / 1) and KTOP (integers in 0 .. kz)
+        as (ni, nj) or (1, ni, nj) arrays, CLDFRA (in [0, 1]) as a (kz, ni, nj) array, starting at
+        the global indices (j1, i1, k1)."""
+        f = CUMTRAN_FIELD[name] if isinstance(name, str) else int(name)
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        nk, ni, nj = a.shape
+        self._check(lib().rcmdyn_put_cumtran(self.h, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                             j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+
+    def get_cumtran(self, name) -> np.ndarray:
+        """One held input as a (1, iy, jx) array (DOTRAN, KTOP) or a (kz, iy, jx) array (CLDFRA)."""
+        f = CUMTRAN_FIELD[name] if isinstance(name, str) else int(name)
+        nk = self.rc.kz if f == CUMTRAN_FIELD["CLDFRA"] else 1
+        out = np.zeros((nk, self.rc.iy, self.rc.jx))
+        self._check(lib().rcmdyn_get_cumtran(self.h, f, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                             1, self.rc.jx, 1, self.rc.iy, 1, nk))
+        return out
+
+    def set_tracer_budget(self, on: bool = True, rw: float = 1.0, cfdout: float = 1.0):
+        """The tracer budget (ichdiag > 0): every later tend adds each stage term times rw (the
+        host's alarm_out_atm%rw) to its accumulator, and an acting cumtran its pseudo-tendency
+        times cfdout (alarm_out_che%rw)."""
+        self._check(lib().rcmdyn_set_tracer_budget(self.h, 1 if on else 0, rw, cfdout))
+
+    def get_tracer_budget(self, term, itr: int) -> np.ndarray:
+        """One accumulator (TRACER_DIAG_TERMS name or number) of tracer itr as a (kz, iy, jx) array:
+        zero outside the interior cross points."""
+        n = TRACER_DIAG_TERM[term] if isinstance(term, str) else int(term)
+        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
+        self._check(lib().rcmdyn_get_tracer_budget(self.h, n, itr, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                   1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
+        return out
+
+    def reset_tracer_budget(self):
+        """Zeroes every accumulator (the host does it after writing them at alarm_out_che)."""
+        self._check(lib().rcmdyn_reset_tracer_budget(self.h))
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

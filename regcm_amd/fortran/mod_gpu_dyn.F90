@@ -64,6 +64,14 @@ module mod_gpu_dyn
     tr_atm1 = 0, tr_atm2 = 1, tr_phy = 2, tr_b0 = 3, tr_bt = 4, tr_chib3d = 5, rcmdyn_ntrfields = 6
   integer, parameter, public :: rcmdyn_maxtr = 96
 
+  ! inputs of the tracers' cumulus mixing (enum rcmdyn_cumtran_field): init_cumtran's mask (0 / 1),
+  ! kcumtop (both 2-D), convcldfra; terms of the tracer budget (enum rcmdyn_tracer_diag): cadvhdiag,
+  ! cadvvdiag, cbdydiag, cdifhdiag, cumtran's share of cconvdiag
+  integer(c_int32_t), parameter, public :: &
+    cum_dotran = 0, cum_ktop = 1, cum_cldfra = 2, rcmdyn_ncumfields = 3
+  integer(c_int32_t), parameter, public :: &
+    trdiag_advh = 0, trdiag_advv = 1, trdiag_bdy = 2, trdiag_difh = 3, trdiag_conv = 4, rcmdyn_ntrdiag = 5
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -335,6 +343,49 @@ module mod_gpu_dyn
       type(c_ptr), value :: h
       real(c_double), intent(in) :: cefc(*), cegc(*)
     end function
+    ! cumtran (ichcumtra = 1) inside tend on (1) or off (0, the default); ncum = dtcum / dtsec: it
+    ! acts in a tend whose clock has lcount > 0 and mod(lcount, ncum) == 0
+    integer(c_int) function rcmdyn_set_cumtran(h, on, ncum) bind(c, name='rcmdyn_set_cumtran')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on, ncum
+    end function
+    ! one input (cum_dotran, cum_ktop: 2-D, k1 = k2 = 1; cum_cldfra) from src(j1:j2,i1:i2,k1:k2);
+    ! the host puts kcumtop and convcldfra after its cumulus call
+    integer(c_int) function rcmdyn_put_cumtran(h, f, src, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_put_cumtran')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: f, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(in) :: src(*)
+    end function
+    integer(c_int) function rcmdyn_get_cumtran(h, f, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_cumtran')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: f, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
+    ! the tracer budget (ichdiag > 0) on (1) or off (0, the default); rw = alarm_out_atm%rw,
+    ! cfdout = alarm_out_che%rw
+    integer(c_int) function rcmdyn_set_tracer_budget(h, on, rw, cfdout) bind(c, name='rcmdyn_set_tracer_budget')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on
+      real(c_double), value :: rw, cfdout
+    end function
+    ! one term (trdiag_advh .. trdiag_conv) of tracer itr into dst(j1:j2,i1:i2,k1:k2)
+    integer(c_int) function rcmdyn_get_tracer_budget(h, term, itr, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_tracer_budget')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: term, itr, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
+    integer(c_int) function rcmdyn_reset_tracer_budget(h) bind(c, name='rcmdyn_reset_tracer_budget')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -357,6 +408,8 @@ module mod_gpu_dyn
   public :: rcmdyn_set_massck, rcmdyn_get_massck
   public :: rcmdyn_set_condtq, rcmdyn_put_rh0adj, rcmdyn_get_condtq
   public :: rcmdyn_set_tracers, rcmdyn_put_tracer, rcmdyn_get_tracer, rcmdyn_put_tracer_nudge
+  public :: rcmdyn_set_cumtran, rcmdyn_put_cumtran, rcmdyn_get_cumtran
+  public :: rcmdyn_set_tracer_budget, rcmdyn_get_tracer_budget, rcmdyn_reset_tracer_budget
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains
