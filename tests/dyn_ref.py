@@ -1,0 +1,686 @@
+"""A NumPy statement of the reference's horizontal diffusion and lateral-boundary relaxation, and of
+the hydrostatic tendencies they are added to, for one limited-area tile (neither i_band nor i_crm),
+from the state after the initial bdyval.  Written from the Fortran text; nothing here reads the
+oracle or the engine.  Test infrastructure: tests/test_dyn_rows_cpu.py compares the oracle with it,
+tests/test_dyn_rows_gpu.py the engine.
+
+Every expression keeps the operation order of the text (left to right, the parentheses of the
+source), in float64.  calc_coeff, diffu_d, diffu_x, the nudge and sponge routines and the surface
+pressure tendency hold no transcendental function but the exp of the iboudy = 5 coefficient table
+(math.exp, the C library's), so they are comparable bit for bit; the advection, adiabatic and
+pressure-gradient terms hold libm pow / log and are compared at rtol 1e-10.
+
+  setup_boundaries  ba_cr / ba_dt, ibnd and the side           Main/mod_atm_interface.F90:383-542
+  setup_bdycon      fnudge, gnudge, fcx.., wgtx.., hefc..      Main/mod_bdycod.F90:203-273
+  psc2psd           psdotb, the edge and corner rules          Main/mpplib/mod_mppparam.F90:13811-13862
+  mkslice           ubd3d, tb3d, qxb3d (floors minqq and 0)    Main/mod_slice.F90:169-195
+  initialize_diff.  xkhz, xkhmax, dydc, hgfact                 Main/mod_diffusion.F90:100-140
+  calc_coeff        xkc (both cores), xkd, the scaling         Main/mod_diffusion.F90:193-249
+  diffu_d           idiffu 1 (interior, ring, corners) and 2   Main/mod_diffusion.F90:281-411
+  diffu_x3d / 4d3d  the same on cross points                   Main/mod_diffusion.F90:673-735, 822-892
+  nudge3d / 4d3d    t, qv (nfac / rfac)                        Main/mod_bdycod.F90:4218-4406, 3206-3392
+  nudgeuv           u, v on ba_dt                              Main/mod_bdycod.F90:3581-3823
+  nudge2d           p* with the level-kz coefficient           Main/mod_bdycod.F90:4597-4766
+  sponge3d/4d/uv/2d wgt * ften + (1 - wgt) * bt                Main/mod_bdycod.F90:2591-3122
+  compute_omega     cr, pten, qdot, omega                      Main/mod_tendency.F90:1118-1215
+  new_pressure      the p* boundary term                       Main/mod_tendency.F90:1428-1438
+  the call order    advection, curvature, adiabatic, boundary, diffusion, the sums, the
+                    pressure-gradient force, the u / v sums    Main/mod_tendency.F90:257-294, 398-411
+
+(The Coriolis term is `curvature`, called before `boundary`: u and v take advection, Coriolis,
+relaxation, diffusion and then the two pressure-gradient terms.)
+
+Arrays are (k, i, j) with the Fortran point (j, i, k) at [k - 1, i - 1, j - 1]; cross fields hold
+i = 1..iy-1, j = 1..jx-1 (the last row and column are unused).
+"""
+import math
+
+import numpy as np
+
+EGRAV = 9.80665                 # Share/mod_constants.F90:85
+REGRAV = 1.0 / EGRAV            # :182
+VONKAR = 0.4                    # :296
+MINQQ = 1.0e-8
+EP1 = 28.96454 / 18.01528 - 1.0  # amd / amw - 1 (:303)
+Z4 = (1.0, -4.0, 12.0)          # z4_c1..3, Main/mod_diffusion.F90:69-71
+O4 = (4.0 / 6.0, 1.0 / 6.0, -20.0 / 6.0)   # o4_c1..3, :63-65
+SOUTH, NORTH, WEST, EAST = 1, 2, 3, 4
+
+
+# ------------------------------------------------------------------------------ the band
+def band_sides(rc, dot):
+    """{(j, i): (side, ibnd)} of setup_boundaries for ba_dt (dot: icx = icy = 0, nspgd) or ba_cr
+    (nspgx), neither bandflag nor crmflag, on the points the nudge and sponge loops visit
+    (jdi x idi or jci x ici).  The four sides do not overlap (asserted)."""
+    jx, iy = rc.jx, rc.iy
+    nsp = rc.nspgd if dot else rc.nspgx
+    ic = 0 if dot else 1
+    igbb1, igbb2, jgbl1, jgbl2 = 2, nsp - 1, 2, nsp - 1
+    igbt1, igbt2 = iy - ic - nsp + 2, iy - ic - 1
+    jgbr1, jgbr2 = jx - ic - nsp + 2, jx - ic - 1
+    out = {}
+
+    def put(j, i, side, ib):
+        assert (j, i) not in out, (j, i)
+        out[(j, i)] = (side, ib)
+    for i in range(1, iy + 1):
+        if igbb1 <= i <= igbb2:
+            for j in range(1, jx + 1):
+                if jgbl1 <= j <= jgbr2:
+                    if j <= jgbl2 and i >= j:
+                        continue
+                    if j >= jgbr1 and i >= (jgbr2 - j + 2):
+                        continue
+                    put(j, i, SOUTH, i - igbb1 + 2)
+    for i in range(1, iy + 1):
+        if igbt1 <= i <= igbt2:
+            for j in range(1, jx + 1):
+                if jgbl1 <= j <= jgbr2:
+                    if j <= jgbl2 and (igbt2 - i + 2) >= j:
+                        continue
+                    if j >= jgbr1 and (igbt2 - i) >= (jgbr2 - j):
+                        continue
+                    put(j, i, NORTH, igbt2 - i + 2)
+    for i in range(1, iy + 1):
+        if i < igbb1 or i > igbt2:
+            continue
+        for j in range(1, jx + 1):
+            if jgbl1 <= j <= jgbl2:
+                if i < igbb2 and j > i:
+                    continue
+                if i > igbt1 and j > (igbt2 - i + 2):
+                    continue
+                put(j, i, WEST, j - jgbl1 + 2)
+    for i in range(1, iy + 1):
+        if i < igbb1 or i > igbt2:
+            continue
+        for j in range(1, jx + 1):
+            if jgbr1 <= j <= jgbr2:
+                if i < igbb2 and (jgbr2 - j + 2) > i:
+                    continue
+                if i > igbt1 and (jgbr2 - j) > (igbt2 - i):
+                    continue
+                put(j, i, EAST, jgbr2 - j + 2)
+    jhi, ihi = (jx - 1, iy - 1) if dot else (jx - 2, iy - 2)
+    return {p: v for p, v in out.items() if 2 <= p[0] <= jhi and 2 <= p[1] <= ihi}
+
+
+def band(rc, dot=False):
+    """{(j, i): ibnd} of the relaxation band on cross (ba_cr) or dot (ba_dt) points."""
+    return {p: ib for p, (_, ib) in band_sides(rc, dot).items()}
+
+
+def band_mask(rc, dot=False):
+    m = np.zeros((rc.iy, rc.jx), dtype=bool)
+    for (j, i) in band_sides(rc, dot):
+        m[i - 1, j - 1] = True
+    return m
+
+
+def domain_mask(rc, dot=False):
+    """[i, j] of jdi x idi (dot) or jci x ici."""
+    m = np.zeros((rc.iy, rc.jx), dtype=bool)
+    m[1:(rc.iy - 1 if dot else rc.iy - 2), 1:(rc.jx - 1 if dot else rc.jx - 2)] = True
+    return m
+
+
+def ring_masks(rc, dot=False):
+    """(ring, corners): the second-order lines jdi1 / jdi2 / idi1 / idi2 (or the cross ones) and
+    their four corners."""
+    dom = domain_mask(rc, dot)
+    inner = np.zeros_like(dom)
+    inner[2:(rc.iy - 2 if dot else rc.iy - 3), 2:(rc.jx - 2 if dot else rc.jx - 3)] = True
+    ring = dom & ~inner
+    i2, j2 = (rc.iy - 2, rc.jx - 2) if dot else (rc.iy - 3, rc.jx - 3)
+    corners = np.zeros_like(dom)
+    for i in (1, i2):
+        for j in (1, j2):
+            corners[i, j] = True
+    return ring, corners
+
+
+# ------------------------------------------------------------------------------ the coefficient tables
+def tables(rc):
+    """setup_bdycon: tables indexed [n] (fcx, gcx, fcd, gcd, wgtx, wgtd; n = 2..nsp-1) and [n, k - 1]
+    (hefc, hegc, hefd, hegd).  Every table is stated for every iboudy; the callers pick."""
+    kz = rc.kz
+    sig = rc.sigma
+    hsig = (sig[1:] + sig[:-1]) * 0.5
+    fnudge = rc.bdy_nm if rc.bdy_nm > 0.0 else 0.1 / rc.dt
+    gnudge = rc.bdy_dm if rc.bdy_dm > 0.0 else 1.0 / (rc.dt * 50.0)
+    t = dict(fnudge=fnudge, gnudge=gnudge)
+    for tag, nsp in (("x", rc.nspgx), ("d", rc.nspgd)):
+        f, g = np.zeros(nsp + 1), np.zeros(nsp + 1)
+        for n in range(2, nsp):
+            xfun = float(nsp - n) / float(nsp - 2)
+            f[n], g[n] = fnudge * xfun, gnudge * xfun
+        t["fc" + tag], t["gc" + tag] = f, g
+    wd, wx = np.ones(max(rc.nspgd + 1, 6)), np.ones(max(rc.nspgx + 1, 5))
+    wd[2:6] = (0.20, 0.55, 0.80, 0.95)
+    wx[2:5] = (0.4, 0.7, 0.9)
+    t["wgtd"], t["wgtx"] = wd, wx
+    anudge = [rc.high_nudge if h < 0.4 else rc.medium_nudge if h < 0.8 else rc.low_nudge for h in hsig]
+    for tag, nsp in (("c", rc.nspgx), ("d", rc.nspgd)):
+        f, g = np.zeros((nsp + 1, kz)), np.zeros((nsp + 1, kz))
+        for k in range(kz):
+            for n in range(2, nsp):
+                xfun = math.exp(-(float(n - 2) / anudge[k]))
+                f[n, k], g[n, k] = fnudge * xfun, gnudge * xfun
+        t["hef" + tag], t["heg" + tag] = f, g
+    return t
+
+
+# ------------------------------------------------------------------------------ slices
+def psc2psd(pc):
+    """psdot from the cross p* (iy, jx; the last row and column unused) on one global tile."""
+    iy, jx = pc.shape
+    pd = np.zeros_like(pc)
+    pd[1:iy - 1, 1:jx - 1] = (pc[1:iy - 1, 1:jx - 1] + pc[0:iy - 2, 1:jx - 1] + pc[1:iy - 1, 0:jx - 2] +
+                              pc[0:iy - 2, 0:jx - 2]) * 0.25
+    pd[iy - 1, 1:jx - 1] = (pc[iy - 2, 1:jx - 1] + pc[iy - 2, 0:jx - 2]) * 0.5
+    pd[0, 1:jx - 1] = (pc[0, 1:jx - 1] + pc[0, 0:jx - 2]) * 0.5
+    pd[1:iy - 1, 0] = (pc[1:iy - 1, 0] + pc[0:iy - 2, 0]) * 0.5
+    pd[1:iy - 1, jx - 1] = (pc[1:iy - 1, jx - 2] + pc[0:iy - 2, jx - 2]) * 0.5
+    pd[0, 0], pd[iy - 1, 0] = pc[0, 0], pc[iy - 2, 0]
+    pd[0, jx - 1], pd[iy - 1, jx - 1] = pc[0, jx - 2], pc[iy - 2, jx - 2]
+    return pd
+
+
+def b_slices(st):
+    """mkslice's b-level exports: (ubd3d, vbd3d, tb3d, qvb3d, qcb3d, psdotb)."""
+    psb = st["PSB"][0]
+    pd = psc2psd(psb)
+    rpd = 1.0 / pd
+    with np.errstate(divide="ignore", invalid="ignore"):       # the unused last row and column hold zeros
+        rpsb = 1.0 / psb
+        tb = st["ATM2_T"] * rpsb[None]
+        qv = np.maximum(st["ATM2_QV"] * rpsb[None], MINQQ)
+        qc = np.maximum(st["ATM2_QC"] * rpsb[None], 0.0) if "ATM2_QC" in st else None
+    return st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None], tb, qv, qc, pd
+
+
+# ------------------------------------------------------------------------------ calc_coeff
+def _hgfact(rc, ht, xkhz):
+    iy, jx = rc.iy, rc.jx
+    dx = rc.ds * 1000.0
+    hg = np.full((iy, jx), xkhz)
+    if rc.diffu_hgtf == 1:
+        c = ht[1:iy - 2, 1:jx - 2]
+        hg1 = np.abs((c - ht[0:iy - 3, 1:jx - 2]) / dx)
+        hg2 = np.abs((c - ht[2:iy - 1, 1:jx - 2]) / dx)
+        hg3 = np.abs((c - ht[1:iy - 2, 0:jx - 3]) / dx)
+        hg4 = np.abs((c - ht[1:iy - 2, 2:jx - 1]) / dx)
+        hgmax = np.maximum(np.maximum(hg1, hg2), np.maximum(hg3, hg4)) * REGRAV * 1.0e3
+        hg[1:iy - 2, 1:jx - 2] = xkhz / (1.0 + hgmax * hgmax)
+    return hg
+
+
+def _deformation(ud, vd):
+    """(dudx - dvdy)^2 + (dvdx + dudy)^2 at the cross points 1..iy-1 x 1..jx-1 (:198-206)."""
+    def q(a):
+        return a[:, :-1, :-1], a[:, :-1, 1:], a[:, 1:, :-1], a[:, 1:, 1:]   # (j,i) (j+1,i) (j,i+1) (j+1,i+1)
+    u00, u10, u01, u11 = q(ud)
+    v00, v10, v01, v11 = q(vd)
+    dudx = u10 + u11 - u00 - u01
+    dvdx = v10 + v11 - v00 - v01
+    dudy = u01 + u11 - u00 - u10
+    dvdy = v01 + v11 - v00 - v10
+    return (dudx - dvdy) * (dudx - dvdy) + (dvdx + dudy) * (dvdx + dudy)
+
+
+def _scale_coeff(rc, raw, psb, pd):
+    """xkd as the four-point mean of the unscaled xkc (:237-240), then both x rdxsq x p* (:241-249)."""
+    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    dx = rc.ds * 1000.0
+    rdxsq = 1.0 / (dx * dx)
+    xkd_raw = np.zeros((kz, iy, jx))
+    xkd_raw[:, 1:iy - 1, 1:jx - 1] = 0.25 * (raw[:, 1:iy - 1, 1:jx - 1] + raw[:, 0:iy - 2, 0:jx - 2] +
+                                             raw[:, 1:iy - 1, 0:jx - 2] + raw[:, 0:iy - 2, 1:jx - 1])
+    xkc = np.zeros((kz, iy, jx))
+    xkc[:, 1:iy - 2, 1:jx - 2] = raw[:, 1:iy - 2, 1:jx - 2] * rdxsq * psb[None, 1:iy - 2, 1:jx - 2]
+    xkd = np.zeros((kz, iy, jx))
+    xkd[:, 1:iy - 1, 1:jx - 1] = xkd_raw[:, 1:iy - 1, 1:jx - 1] * rdxsq * pd[None, 1:iy - 1, 1:jx - 1]
+    return dict(xkc_raw=raw, xkd_raw=xkd_raw, xkc=xkc, xkd=xkd)
+
+
+def hydro_coeff(rc, st):
+    """calc_coeff of the hydrostatic core: xkc_raw on ice x jce, xkd_raw on idi x jdi, and the scaled
+    xkc (ici x jci) and xkd (idi x jdi); zero elsewhere.  st: ATM2_U, ATM2_V, PSB, HT."""
+    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    dx = rc.ds * 1000.0
+    dxsq = dx * dx
+    xkhmax = dxsq / (64.0 * rc.dt)
+    dydc = rc.adyndif * VONKAR * VONKAR * dx * 0.25
+    xkhz = rc.ckh * 1.5e-3 * dxsq / rc.dt
+    psb = st["PSB"][0]
+    pd = psc2psd(psb)
+    rpd = 1.0 / pd
+    ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
+    hg = _hgfact(rc, st["HT"][0], xkhz)
+    duv = np.sqrt(_deformation(ud, vd))
+    raw = np.zeros((kz, iy, jx))
+    raw[:, :iy - 1, :jx - 1] = np.minimum(hg[None, :iy - 1, :jx - 1] + dydc * duv, xkhmax)
+    return _scale_coeff(rc, raw, psb, pd)
+
+
+def nh_coeff(rc, st):
+    """calc_coeff of the non-hydrostatic core (:212-230): the deformation less the vertical-velocity
+    term, floored at zero, xkhz = ckh dx and twice the hydrostatic xkhmax (:110-113).  st: ATM2_U,
+    ATM2_V, ATM2_W, PSB (and HT where diffu_hgtf = 1)."""
+    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    dx = rc.ds * 1000.0
+    dxsq = dx * dx
+    xkhmax = 2.0 * (dxsq / (64.0 * rc.dt))
+    dydc = rc.adyndif * VONKAR * VONKAR * dx * 0.25
+    xkhz = rc.ckh * dx
+    psb = st["PSB"][0]
+    pd = psc2psd(psb)
+    rpd = 1.0 / pd
+    ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        wb = st["ATM2_W"] * (1.0 / psb)[None]
+    hg = _hgfact(rc, st["HT"][0], xkhz) if rc.diffu_hgtf == 1 else np.full((iy, jx), xkhz)
+    dwdz = wb[:-1, :iy - 1, :jx - 1] - wb[1:, :iy - 1, :jx - 1]
+    duv = np.sqrt(np.maximum(_deformation(ud, vd) - dwdz * dwdz, 0.0))
+    raw = np.zeros((kz, iy, jx))
+    raw[:, :iy - 1, :jx - 1] = np.minimum(hg[None, :iy - 1, :jx - 1] + dydc * duv, xkhmax)
+    return _scale_coeff(rc, raw, psb, pd)
+
+
+def nh_xkc(rc, st):
+    """The scaled NH xkc on jci x ici (what the tracers and the budget read)."""
+    return nh_coeff(rc, st)["xkc"]
+
+
+# ------------------------------------------------------------------------------ diffusion
+def _diffu(rc, fm, xk, dot):
+    """The increments of one diffu_* call, in the order the text adds them: idiffu = 1: the
+    fourth-order interior (jdii x idii / jcii x icii), then the second-order lines west, east, south,
+    north (the corners lie on two lines and take two adds); idiffu = 2: the nine-point form on the
+    whole jdi x idi / jci x ici.  fm, xk: (nk, iy, jx); each increment is zero off its support."""
+    iy, jx = rc.iy, rc.jx
+    j2, i2 = (jx - 1, iy - 1) if dot else (jx - 2, iy - 2)
+    with np.errstate(invalid="ignore"):
+        P = np.pad(fm, ((0, 0), (2, 2), (2, 2)))
+
+        def F(dj, di):
+            return P[:, 2 + di:2 + di + iy, 2 + dj:2 + dj + jx]
+        jj, ii = np.meshgrid(np.arange(1, jx + 1), np.arange(1, iy + 1))
+        dom = (jj >= 2) & (jj <= j2) & (ii >= 2) & (ii <= i2)
+        if rc.idiffu == 2:
+            inc = xk * (O4[0] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) +
+                        O4[1] * (F(1, 1) + F(-1, -1) + F(-1, 1) + F(1, -1)) + O4[2] * fm)
+            return [np.where(dom[None], inc, 0.0)]
+        assert rc.idiffu == 1
+        inner = (jj >= 3) & (jj <= j2 - 1) & (ii >= 3) & (ii <= i2 - 1)
+        fourth = -(xk * (Z4[0] * (F(2, 0) + F(-2, 0) + F(0, 2) + F(0, -2)) +
+                         Z4[1] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) + Z4[2] * fm))
+        second = xk * (Z4[0] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) + Z4[1] * fm)
+        out = [np.where(inner[None], fourth, 0.0)]
+        for line in (jj == 2, jj == j2, ii == 2, ii == i2):
+            out.append(np.where((dom & line)[None], second, 0.0))
+        return out
+
+
+def diffu_x(rc, f, xkc):
+    """diffu_x3d / diffu_x4d3d (fac = 1) of the decoupled cross field f: the list of increments."""
+    return _diffu(rc, f, xkc, dot=False)
+
+
+def diffu_d(rc, u, v, xkd, msfd):
+    """diffu_d of ubd3d, vbd3d (each value divided by msfd at its own point): (u incs, v incs)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return _diffu(rc, u / msfd[None], xkd, dot=True), _diffu(rc, v / msfd[None], xkd, dot=True)
+
+
+def apply(ften, incs):
+    """ften + inc, one increment after the other (each its own rounded addition)."""
+    for a in incs:
+        ften = ften + a
+    return ften
+
+
+def total(incs):
+    return apply(np.zeros_like(incs[0]), incs)
+
+
+# ------------------------------------------------------------------------------ relaxation
+def _lap(fg):
+    """fls1 + fls2 + fls3 + fls4 - 4 fls0 (j-1, j+1, i-1, i+1), zero on the frame edge."""
+    out = np.zeros_like(fg)
+    c = fg[..., 1:-1, 1:-1]
+    out[..., 1:-1, 1:-1] = fg[..., 1:-1, :-2] + fg[..., 1:-1, 2:] + fg[..., :-2, 1:-1] + fg[..., 2:, 1:-1] - 4.0 * c
+    return out
+
+
+def _coef(rc, tab, dot, kind, nk):
+    """(xf, xg) as (nk, iy, jx), zero off the band: iboudy 1 the linear fcx / gcx (fcd / gcd for u, v);
+    iboudy 5 hefc / hegc(ib, k) for t and qv, (ib, kz) for p*, and for u, v hefc / hegc on the south
+    side, hefd / hegd on the other three (:3720, 3746, 3772, 3798)."""
+    xf, xg = np.zeros((nk, rc.iy, rc.jx)), np.zeros((nk, rc.iy, rc.jx))
+    for (j, i), (side, ib) in band_sides(rc, dot).items():
+        if rc.iboudy == 1:
+            f, g = (tab["fcd"][ib], tab["gcd"][ib]) if dot else (tab["fcx"][ib], tab["gcx"][ib])
+        elif kind == "ps":
+            f, g = tab["hefc"][ib, rc.kz - 1], tab["hegc"][ib, rc.kz - 1]
+        elif dot and side != SOUTH:
+            f, g = tab["hefd"][ib], tab["hegd"][ib]
+        else:
+            f, g = tab["hefc"][ib], tab["hegc"][ib]
+        xf[:, i - 1, j - 1], xg[:, i - 1, j - 1] = f, g
+    return xf, xg
+
+
+def nudge(rc, f, b0, bt, xt, kind, tab=None):
+    """The relaxation increments of one field (iboudy 1 or 5), in the order the text adds them.
+    kind 't', 'u', 'v', 'ps': ften + xf fls0 - xg (...), two additions: [xf fls0, -(xg (...))];
+    kind 'qv': ften + rfac (xf fls0 - xg (...)), one addition.  f: atm2 (coupled)."""
+    tab = tab or tables(rc)
+    dot = kind in ("u", "v")
+    if kind == "qv":
+        nfac = 1.0e3
+        rfac = 1.0 / nfac
+        fg = nfac * (b0 + xt * bt) - nfac * f
+    else:
+        fg = (b0 + xt * bt) - f
+    xf, xg = _coef(rc, tab, dot, kind, f.shape[0])
+    if kind == "qv":
+        return [rfac * (xf * fg - xg * _lap(fg))]
+    return [xf * fg, -(xg * _lap(fg))]
+
+
+def sponge(rc, ften, bt, dot, tab=None):
+    """sponge*: wgt(ib) ften + (1 - wgt(ib)) bt on the band, ften elsewhere (iboudy = 4)."""
+    tab = tab or tables(rc)
+    w = np.ones((rc.iy, rc.jx))
+    m = np.zeros((rc.iy, rc.jx), dtype=bool)
+    wgt = tab["wgtd" if dot else "wgtx"]
+    for (j, i), (_, ib) in band_sides(rc, dot).items():
+        w[i - 1, j - 1], m[i - 1, j - 1] = wgt[ib], True
+    return np.where(m, w * ften + (1.0 - w) * bt, ften)
+
+
+# ------------------------------------------------------------------------------ the hydrostatic tend
+HYDRO_INPUTS = ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "ATM2_V", "ATM2_T", "ATM2_QV",
+                "ATM2_QC", "PSA", "PSB", "MSFX", "MSFD", "CORIOL", "HT", "XUB_B0", "XUB_BT", "XVB_B0", "XVB_BT",
+                "XTB_B0", "XTB_BT", "XQB_B0", "XQB_BT", "XPSB_B0", "XPSB_BT")
+
+
+def sh(a, dj, di):
+    """sh(a)[k, i, j] = a[k, i + di, j + dj]."""
+    return np.roll(a, shift=(-di, -dj), axis=(-2, -1))
+
+
+class Sum:
+    """A running tendency: the value after each addition and the largest |partial sum| so far."""
+
+    def __init__(self, like):
+        self.v = np.zeros_like(like)
+        self.big = np.zeros_like(like)
+        self.at = {}
+
+    def add(self, incs, tag=None):
+        for a in incs if isinstance(incs, list) else [incs]:
+            self.v = self.v + a
+            with np.errstate(invalid="ignore"):
+                self.big = np.fmax(self.big, np.abs(self.v))
+        if tag:
+            self.at[tag] = self.v
+        return self
+
+    def put(self, v, tag):
+        """Take a value formed in place by a column recurrence."""
+        self.v = v
+        with np.errstate(invalid="ignore"):
+            self.big = np.fmax(self.big, np.abs(v))
+        self.at[tag] = v
+
+
+def hydro_tend(rc, g, dt, xbc, relax=True, diffuse=True):
+    """One hydrostatic tend from the state g after bdyval (no physics tendencies), dt and xbctime
+    as rcmdyn get_time returns them.  Returns the running sums of tdyn, qvdyn, qcdyn, udyn, vdyn after
+    each process (`at`: adh, adv, adi / cor, bdy, dif, pgf), the increments of the relaxation and
+    diffusion terms, the coefficients, pten before and after new_pressure, and the totals.
+    relax / diffuse = False leave the process out (for a test's own on/off differences)."""
+    from regcm_amd import constants as C
+    kz = rc.kz
+    sig = rc.sigma
+    hsig = (sig[1:] + sig[:-1]) * 0.5
+    dsig = sig[1:] - sig[:-1]
+    twt1 = np.zeros(kz + 1); twt2 = np.zeros(kz + 1)
+    for k in range(2, kz + 1):
+        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
+        twt2[k] = 1.0 - twt1[k]
+    dx = rc.ds * 1000.0
+    ul = rc.uoffc * 0.5 * rc.dt / dx
+    rgas = C.rgas
+    cpd = 3.5 * rgas
+    c287 = rgas / 1000.0                                         # Share/mod_constants.F90:132-134
+    ptop = rc.ptop
+    xt = xbc + dt
+    tab = tables(rc)
+    nudging = relax and rc.iboudy in (1, 5)
+    sponging = relax and rc.iboudy == 4
+    assert rc.ipgf == 0 and rc.idynamic == 1
+
+    u1, v1, t1, q1, qc1 = g["ATM1_U"], g["ATM1_V"], g["ATM1_T"], g["ATM1_QV"], g["ATM1_QC"]
+    pa, pb = g["PSA"][0], g["PSB"][0]
+    msfx, msfd = g["MSFX"][0], g["MSFD"][0]
+    psd = psc2psd(pa)                                            # psdota, the edge lines included
+    rpsd = 1.0 / psd
+    rpsa = np.divide(1.0, pa, out=np.zeros_like(pa), where=pa > 0)
+    umc, vmc = u1 * msfd, v1 * msfd
+    ud, vd = u1 * rpsd, v1 * rpsd
+    if rc.iboudy in (3, 4):
+        # decouple's inflow / outflow dependence (Main/mod_tendency.F90:908-918, 933-943, 958-968,
+        # 983-993): an outflow edge value is the first interior line's; west, east over idi, then
+        # south, north over jde (the corners read the lines just set).  After bdyval the boundary
+        # slices wue.. hold atm1 on the edge lines.
+        for a in (ud, vd):
+            a[:, 1:-1, 0] = np.where(u1[:, 1:-1, 0] <= 0.0, a[:, 1:-1, 1], a[:, 1:-1, 0])
+            a[:, 1:-1, -1] = np.where(u1[:, 1:-1, -1] >= 0.0, a[:, 1:-1, -2], a[:, 1:-1, -1])
+            a[:, 0, :] = np.where(v1[:, 0, :] >= 0.0, a[:, 1, :], a[:, 0, :])
+            a[:, -1, :] = np.where(v1[:, -1, :] <= 0.0, a[:, -2, :], a[:, -1, :])
+    old_err = np.seterr(divide="ignore", invalid="ignore")      # frame edges: never compared
+    # compute_omega: cr x dummy (a product with the reciprocal), pten, qdot
+    dummy = 1.0 / ((2.0 * dx) * msfx * msfx)
+    cr = ((sh(umc, 1, 1) + sh(umc, 1, 0) - sh(umc, 0, 1) - umc) +
+          (sh(vmc, 1, 1) + sh(vmc, 0, 1) - sh(vmc, 1, 0) - vmc)) * dummy
+    pten = np.zeros_like(pa)
+    for k in range(kz):
+        pten = pten - cr[k] * dsig[k]
+    qdot = np.zeros((kz + 1,) + pa.shape)
+    for k in range(2, kz + 1):
+        qdot[k - 1] = qdot[k - 2] - (pten + cr[k - 2]) * dsig[k - 2] * rpsa
+    # new_pressure: the boundary term of p*
+    pten0 = pten.copy()                                          # on jce x ice; the unused line zeroed
+    pten0[-1, :] = 0.0
+    pten0[:, -1] = 0.0
+    pinc = []
+    if sponging:
+        ptot = sponge(rc, pten0, g["XPSB_BT"][0], False, tab)
+    else:
+        if nudging:
+            pinc = [a[0] for a in nudge(rc, g["PSB"], g["XPSB_B0"], g["XPSB_BT"], xt, "ps", tab)]
+        ptot = apply(pten0, pinc)
+
+    xtd = t1 * rpsa
+    xq = np.maximum(q1 * rpsa, MINQQ)
+    xc = np.maximum(qc1 * rpsa, 0.0)
+    tv = xtd * (1.0 + EP1 * xq)
+    u1a = sh(umc, 0, 1) + umc
+    u2a = sh(umc, 1, 1) + sh(umc, 1, 0)
+    v1a = sh(vmc, 1, 0) + vmc
+    v2a = sh(vmc, 1, 1) + sh(vmc, 0, 1)
+    f1 = 0.5 * ul * (u2a + u1a) / pa
+    f2 = 0.5 * ul * (v2a + v1a) / pa
+    xmsf = 1.0 / (msfx * msfx * (4.0 * dx))
+
+    def hadv(c):
+        w, e_, s_, n = sh(c, -1, 0), sh(c, 1, 0), sh(c, 0, -1), sh(c, 0, 1)
+        fx1 = (1.0 + f1) * w + (1.0 - f1) * c
+        fx2 = (1.0 + f1) * c + (1.0 - f1) * e_
+        fy1 = (1.0 + f2) * s_ + (1.0 - f2) * c
+        fy2 = (1.0 + f2) * c + (1.0 - f2) * n
+        return -xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1), w, e_, s_, n
+
+    ub, vb, tb, qvb, qcb, pdb = b_slices(g)
+    co = hydro_coeff(rc, g)
+    if not diffuse:
+        co = {k: np.zeros_like(v) for k, v in co.items()}
+
+    # ---- t: hadvt (t_extrema limiter), vadv3d ind 1, the omega term, nudge3d, diffu_x3d
+    T = Sum(t1)
+    fg, w, e_, s_, n = hadv(xtd)
+    for (p_, m_) in ((n, s_), (e_, w)):
+        big = np.abs(p_ + m_ - 2.0 * xtd) / pa > rc.t_extrema
+        fg = np.where(big & (xtd > p_) & (xtd > m_), np.minimum(fg, 0.0), fg)
+        fg = np.where(big & (xtd < p_) & (xtd < m_), np.maximum(fg, 0.0), fg)
+    T.add(fg, "adh")
+    s2 = T.v.copy()
+    pbh = (hsig[:, None, None] * pb + ptop) * 1000.0
+    pbf = (sig[:, None, None] * pb + ptop) * 1000.0
+    for k in range(2, kz + 1):
+        dq = qdot[k - 1] * (twt1[k] * t1[k - 1] * (pbf[k - 1] / pbh[k - 1]) ** c287 +
+                            twt2[k] * t1[k - 2] * (pbf[k - 1] / pbh[k - 2]) ** c287)
+        s2[k - 2] = s2[k - 2] - dq * (1.0 / dsig[k - 2])
+        s2[k - 1] = s2[k - 1] + dq * (1.0 / dsig[k - 1])
+    T.put(s2, "adv")
+    dum8 = 1.0 / (8.0 * dx * msfx)
+    om = np.zeros_like(t1)
+    for k in range(kz):
+        om[k] = (0.5 * (qdot[k + 1] + qdot[k]) * pa + hsig[k] * (
+            pten + ((ud[k] + sh(ud, 0, 1)[k] + sh(ud, 1, 1)[k] + sh(ud, 1, 0)[k]) * (sh(pa, 1, 0) - sh(pa, -1, 0)) +
+                    (vd[k] + sh(vd, 0, 1)[k] + sh(vd, 1, 1)[k] + sh(vd, 1, 0)[k]) * (sh(pa, 0, 1) - sh(pa, 0, -1))) *
+            dum8))
+    rovcpm = rgas / (cpd * (1.0 + 0.80 * xq))
+    T.add((om * rovcpm * tv) / (ptop * rpsa + hsig[:, None, None]), "adi")
+    t_bdy = nudge(rc, g["ATM2_T"], g["XTB_B0"], g["XTB_BT"], xt, "t", tab) if nudging else []
+    T.add(t_bdy, "bdy")
+    t_dif = diffu_x(rc, tb, co["xkc"])
+    T.add(t_dif, "dif")
+
+    # ---- qv: hadvqv (q_rel_extrema limiter), vadvqv, nudge4d3d, diffu_x4d3d
+    Q = Sum(t1)
+    fq, w, e_, s_, n = hadv(xq)
+    den = np.maximum(xq, 1.0e-20)
+    for (p_, m_) in ((n, s_), (e_, w)):
+        big = np.abs(p_ + m_ - 2.0 * xq) / den > rc.q_rel_extrema
+        fq = np.where(big & (xq > p_) & (xq > m_), np.minimum(fq, 0.0), fq)
+        fq = np.where(big & (xq < p_) & (xq < m_), np.maximum(fq, 0.0), fq)
+    Q.add(fq, "adh")
+    q2s = Q.v.copy()
+    for k in range(2, kz + 1):
+        qcon = (sig[k - 1] - hsig[k - 1]) / (hsig[k - 2] - hsig[k - 1])   # Main/mod_params.F90:2214
+        fk, fkm = q1[k - 1], q1[k - 2]
+        ok = (fk > MINQQ * pa) & (fkm > MINQQ * pa)
+        flux = qdot[k - 1] * np.where(ok, fk * (fkm / fk) ** qcon, 0.0)
+        q2s[k - 2] = q2s[k - 2] - flux * (1.0 / dsig[k - 2])
+        q2s[k - 1] = q2s[k - 1] + flux * (1.0 / dsig[k - 1])
+    Q.put(q2s, "adv")
+    q_bdy = nudge(rc, g["ATM2_QV"], g["XQB_B0"], g["XQB_BT"], xt, "qv", tab) if nudging else []
+    Q.add(q_bdy, "bdy")
+    q_dif = diffu_x(rc, qvb, co["xkc"])
+    Q.add(q_dif, "dif")
+
+    # ---- qc: hadvqx, vadv4d ind 1, diffu_x4d3d (no relaxation of qc)
+    Cq = Sum(t1)
+    Cq.add(hadv(xc)[0], "adh")
+    c2 = Cq.v.copy()
+    for k in range(2, kz + 1):
+        fk, fkm, svv = qc1[k - 1], qc1[k - 2], qdot[k - 1]
+        thr = MINQQ * MINQQ * pa
+        ok = np.where(svv > 0.0, fkm > thr, fk > thr)
+        flux = np.where(ok, svv * (twt1[k] * fk + twt2[k] * fkm), 0.0)
+        c2[k - 2] = c2[k - 2] - flux * (1.0 / dsig[k - 2])
+        c2[k - 1] = c2[k - 1] + flux * (1.0 / dsig[k - 1])
+    Cq.put(c2, "adv")
+    c_dif = diffu_x(rc, qcb, co["xkc"])
+    Cq.add(c_dif, "dif")
+
+    # ---- u, v: hadvuv (hydrostatic upstream branch), vadvuv, Coriolis, nudgeuv, diffu_d, the
+    # pressure-gradient force with ipgf = 0
+    ucmona = sh(umc, 0, 1) + 2.0 * umc + sh(umc, 0, -1)
+    ucmonb = sh(umc, 1, 1) + 2.0 * sh(umc, 1, 0) + sh(umc, 1, -1)
+    ucmonc = sh(umc, -1, 1) + 2.0 * sh(umc, -1, 0) + sh(umc, -1, -1)
+    vcmona = sh(vmc, 1, 0) + 2.0 * vmc + sh(vmc, -1, 0)
+    vcmonb = sh(vmc, 1, 1) + 2.0 * sh(vmc, 0, 1) + sh(vmc, -1, 1)
+    vcmonc = sh(vmc, 1, -1) + 2.0 * sh(vmc, 0, -1) + sh(vmc, -1, -1)
+    ff1, ff2 = ul * (sh(ud, 1, 0) + ud), ul * (sh(ud, -1, 0) + ud)
+    ff3, ff4 = ul * (sh(vd, 0, 1) + vd), ul * (sh(vd, 0, -1) + vd)
+    ucb = (1.0 + ff1) * ucmona + (1.0 - ff1) * ucmonb
+    ucc_ = (1.0 + ff2) * ucmonc + (1.0 - ff2) * ucmona
+    vcb = (1.0 + ff3) * vcmona + (1.0 - ff3) * vcmonb
+    vcc_ = (1.0 + ff4) * vcmonc + (1.0 - ff4) * vcmona
+    dm = 1.0 / (msfd * msfd * 16.0 * dx)
+    U, V = Sum(t1), Sum(t1)
+    U.add(-dm * ((sh(ud, 1, 0) + ud) * ucb - (ud + sh(ud, -1, 0)) * ucc_ +
+                 (sh(ud, 0, 1) + ud) * vcb - (ud + sh(ud, 0, -1)) * vcc_), "adh")
+    V.add(-dm * ((sh(vd, 1, 0) + vd) * ucb - (vd + sh(vd, -1, 0)) * ucc_ +
+                 (sh(vd, 0, 1) + vd) * vcb - (vd + sh(vd, 0, -1)) * vcc_), "adh")
+    udyn, vdyn = U.v.copy(), V.v.copy()
+    for k in range(2, kz + 1):                                   # vadvuv of atm1 u, v
+        qq = 0.25 * (qdot[k - 1] + sh(qdot, 0, -1)[k - 1] + sh(qdot, -1, 0)[k - 1] + sh(qdot, -1, -1)[k - 1])
+        uu = qq * (twt1[k] * u1[k - 1] + twt2[k] * u1[k - 2])
+        vv = qq * (twt1[k] * v1[k - 1] + twt2[k] * v1[k - 2])
+        udyn[k - 2] = udyn[k - 2] - uu / dsig[k - 2]
+        udyn[k - 1] = udyn[k - 1] + uu / dsig[k - 1]
+        vdyn[k - 2] = vdyn[k - 2] - vv / dsig[k - 2]
+        vdyn[k - 1] = vdyn[k - 1] + vv / dsig[k - 1]
+    U.put(udyn, "adv")
+    V.put(vdyn, "adv")
+    cor = g["CORIOL"][0]
+    U.add(cor * v1, "cor")
+    V.add(-(cor * u1), "cor")
+    u_bdy = nudge(rc, g["ATM2_U"], g["XUB_B0"], g["XUB_BT"], xt, "u", tab) if nudging else []
+    v_bdy = nudge(rc, g["ATM2_V"], g["XVB_B0"], g["XVB_BT"], xt, "v", tab) if nudging else []
+    U.add(u_bdy, "bdy")
+    V.add(v_bdy, "bdy")
+    u_dif, v_dif = diffu_d(rc, ub, vb, co["xkd"], msfd)
+    U.add(u_dif, "dif")
+    V.add(v_dif, "dif")
+    rtbar = 0.25 * (sh(tv, -1, -1) + sh(tv, -1, 0) + sh(tv, 0, -1) + tv)
+    rtbar = rgas * rtbar * psd
+    h = hsig[:, None, None]
+    U.add(-(rtbar * (np.log(0.5 * (pa + sh(pa, 0, -1)) * h + ptop) -
+                     np.log(0.5 * (sh(pa, -1, 0) + sh(pa, -1, -1)) * h + ptop)) / (dx * msfd)))
+    V.add(-(rtbar * (np.log(0.5 * (pa + sh(pa, -1, 0)) * h + ptop) -
+                     np.log(0.5 * (sh(pa, -1, -1) + sh(pa, 0, -1)) * h + ptop)) / (dx * msfd)))
+    td = t1 * (1.0 + EP1 * xq)
+    tvfac = 1.0 / (1.0 + xc / (1.0 + xq))
+    phi = np.zeros_like(t1)
+    phi[kz - 1] = g["HT"][0] - rgas * (td[kz - 1] * rpsa * tvfac[kz - 1]) * np.log(
+        (hsig[kz - 1] + ptop * rpsa) / (1.0 + ptop * rpsa))
+    for lev in range(kz - 1, 0, -1):                             # 1-based lev = kz-1 .. 1
+        tvavg = ((td[lev - 1] * dsig[lev - 1] + td[lev] * dsig[lev]) /
+                 (pa * (dsig[lev - 1] + dsig[lev]))) * tvfac[lev - 1]
+        phi[lev - 1] = phi[lev] - rgas * tvavg * np.log((hsig[lev - 1] + ptop * rpsa) / (hsig[lev] + ptop * rpsa))
+    U.add(-(psd * (phi + sh(phi, 0, -1) - sh(phi, -1, 0) - sh(phi, -1, -1)) / (2.0 * dx * msfd)), "pgf")
+    V.add(-(psd * (phi + sh(phi, -1, 0) - sh(phi, 0, -1) - sh(phi, -1, -1)) / (2.0 * dx * msfd)), "pgf")
+    np.seterr(**old_err)
+
+    # ---- the sums: aten(pc_total) is zero when boundary runs, so the sponge leaves (1 - wgt) bt
+    # there and the dynamic sum is added to it (:285-294, 404-411)
+    zero = np.zeros_like(t1)
+    res = dict(T=T, Q=Q, C=Cq, U=U, V=V, coeff=co, tab=tab, pten0=pten0, p_bdy=pinc, qdot=qdot,
+               t_bdy=t_bdy, q_bdy=q_bdy, u_bdy=u_bdy, v_bdy=v_bdy, t_dif=t_dif, q_dif=q_dif, c_dif=c_dif,
+               u_dif=u_dif, v_dif=v_dif, PTEN=ptot)
+    sp = {}
+    for name, S, bt, dot in (("TTEN", T, "XTB_BT", False), ("QVTEN", Q, "XQB_BT", False), ("QCTEN", Cq, None, False),
+                             ("UTEN", U, "XUB_BT", True), ("VTEN", V, "XVB_BT", True)):
+        base = sponge(rc, zero, g[bt], dot, tab) if (sponging and bt) else zero
+        sp[name] = base
+        res[name] = base + S.v
+    res["sponge"] = sp
+    return res
+
+
+def hydro_stages(rc, g, dt0, xbc):
+    """The running sums of the hydrostatic t and qv tendencies after each stage (what the budget
+    terms are the differences of): t after hadvt (s1), vadv3d ind 1 (s2), the omega term (s3), the
+    relaxation (s4), the diffusion (s5); qv after hadvqv (q1), vadvqv (q2), the relaxation (q4),
+    the diffusion (q5)."""
+    r = hydro_tend(rc, g, dt0, xbc)
+    t, q = r["T"].at, r["Q"].at
+    return dict(s1=t["adh"], s2=t["adv"], s3=t["adi"], s4=t["bdy"], s5=t["dif"],
+                q1=q["adh"], q2=q["adv"], q4=q["bdy"], q5=q["dif"])

@@ -57,14 +57,16 @@ _CASES = {}
 
 def case(name, **overrides):
     """(rc, data, state) of CONFIGS[name] with the overrides, generated once and shared: a test
-    that changes the state copies it first.  'C' / 'N' are C1 / N1 cut to the 37 x 29 grid.
+    that changes the state copies it first.  'C' / 'N' are C1 / N1 cut to the 37 x 29 grid (or to the
+    jx, iy, nspgx, nspgd among the overrides).
     The state is the generated one plus the UW TKE (ibltyp = 2) and the patchy hydrometeors
     (nqx = 5) where the configuration has them."""
     key = (name,) + tuple(sorted(overrides.items()))
     if key not in _CASES:
         if name in ("C", "N"):
-            rc = dataclasses.replace(CONFIGS["C1" if name == "C" else "N1"], jx=37, iy=29, nspgx=None,
-                                     nspgd=None, **overrides)
+            cut = dict(jx=37, iy=29, nspgx=None, nspgd=None)
+            cut.update(overrides)               # another cut: jx=34, iy=23, nspgx=7, nspgd=7
+            rc = dataclasses.replace(CONFIGS["C1" if name == "C" else "N1"], **cut)
         else:
             rc = dataclasses.replace(CONFIGS[name], **overrides)
         gen = icbc.generate_crm if rc.i_crm else icbc.generate_nh if rc.idynamic == 2 else icbc.generate

@@ -28,6 +28,7 @@ import pytest
 
 from regcm_amd.dycore import BUDGET_TERMS
 from tests import support
+from tests.dyn_ref import HYDRO_INPUTS, band_mask, hydro_stages
 from tests.support import advance, case, physics_tendencies, state_names
 
 pytestmark = pytest.mark.gpu
@@ -199,9 +200,7 @@ def test_dif_and_bdy_match_the_oracle_with_the_process_off(core):
     e.tend()
     got = terms(e)
     m = interior(rc)
-    band = np.zeros_like(m)
-    for (j, i) in _cross_band(rc):
-        band[i - 1, j - 1] = True
+    band = band_mask(rc)
     assert band.sum() == 500
     for total, dif, bdy in (("TTEN", "T_DIF", "T_BDY"), ("QVTEN", "Q_DIF", "Q_BDY")):
         full = tot["full"][total]
@@ -220,180 +219,13 @@ def test_dif_and_bdy_match_the_oracle_with_the_process_off(core):
 
 
 # ------------------------------------------------------------------ 5. adh, adv, adi against the reference text
-def _cross_band(rc):
-    """{(j, i): ibnd} of the cross-point relaxation band (setup_boundaries,
-    Main/mod_atm_interface.F90:383-512; copied from tests/test_oracle_cpu.py)."""
-    jx, iy, nsp = rc.jx, rc.iy, rc.nspgx
-    icx = icy = 1
-    igbb1, igbb2, jgbl1, jgbl2 = 2, nsp - 1, 2, nsp - 1
-    igbt1, igbt2 = iy - icy - nsp + 2, iy - icy - 1
-    jgbr1, jgbr2 = jx - icx - nsp + 2, jx - icx - 1
-    ib = {}
-    for i in range(1, iy + 1):                                   # south
-        if igbb1 <= i <= igbb2:
-            for j in range(1, jx + 1):
-                if jgbl1 <= j <= jgbr2:
-                    if j <= jgbl2 and i >= j:
-                        continue
-                    if j >= jgbr1 and i >= (jgbr2 - j + 2):
-                        continue
-                    ib[(j, i)] = i - igbb1 + 2
-    for i in range(1, iy + 1):                                   # north
-        if igbt1 <= i <= igbt2:
-            for j in range(1, jx + 1):
-                if jgbl1 <= j <= jgbr2:
-                    if j <= jgbl2 and (igbt2 - i + 2) >= j:
-                        continue
-                    if j >= jgbr1 and (igbt2 - i) >= (jgbr2 - j):
-                        continue
-                    ib[(j, i)] = igbt2 - i + 2
-    for i in range(1, iy + 1):                                   # west
-        if i < igbb1 or i > igbt2:
-            continue
-        for j in range(1, jx + 1):
-            if jgbl1 <= j <= jgbl2:
-                if i < igbb2 and j > i:
-                    continue
-                if i > igbt1 and j > (igbt2 - i + 2):
-                    continue
-                ib[(j, i)] = j - jgbl1 + 2
-    for i in range(1, iy + 1):                                   # east
-        if i < igbb1 or i > igbt2:
-            continue
-        for j in range(1, jx + 1):
-            if jgbr1 <= j <= jgbr2:
-                if i < igbb2 and (jgbr2 - j + 2) > i:
-                    continue
-                if i > igbt1 and (jgbr2 - j) > (igbt2 - i):
-                    continue
-                ib[(j, i)] = jgbr2 - j + 2
-    return {(j, i): n for (j, i), n in ib.items() if 2 <= j <= jx - 2 and 2 <= i <= iy - 2}
-
-
 def _close(got, want, name):
     assert np.abs(want).max() > 0.0, name
     np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-11 * np.abs(want).max(), err_msg=name)
 
 
-HYDRO_INPUTS = ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "PSA", "PSB", "MSFX", "MSFD", "ATM2_T", "XTB_B0", "XTB_BT")
 NH_INPUTS = ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_PP", "ATM1_W", "ATM1_QV", "PSA", "MSFX", "MSFD", "ATM0_PR",
              "ATM0_PS", "ATM0_RHOF", "DPSDXM", "DPSDYM")
-
-
-def hydro_stages(rc, g, dt0, xbc):
-    """The running sums of the hydrostatic t and qv tendencies after each stage, from the state g
-    after bdyval (the staged restatement of tests/test_oracle_cpu.py::
-    test_hydrostatic_temperature_tendency_matches_numpy_restatement): t after hadvt (s1), vadv3d
-    ind 1 (s2), the omega term (s3), the relaxation (s4); qv after hadvqv (q1) and vadvqv (q2)."""
-    from regcm_amd import constants as C
-    kz = rc.kz
-    sig = rc.sigma
-    hsig = (sig[1:] + sig[:-1]) * 0.5
-    dsig = sig[1:] - sig[:-1]
-    twt1 = np.zeros(kz + 1); twt2 = np.zeros(kz + 1)
-    for k in range(2, kz + 1):
-        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
-        twt2[k] = 1.0 - twt1[k]
-    dx = rc.ds * 1000.0
-    ul = rc.uoffc * 0.5 * rc.dt / dx
-    rgas = C.rgas
-    cpd = 3.5 * rgas
-    c287 = rgas / 1000.0
-    ep1 = 28.96454 / 18.01528 - 1.0
-    minqq = 1.0e-8
-
-    def sh(a, dj, di):
-        return np.roll(a, shift=(-di, -dj), axis=(-2, -1))
-
-    u1, v1, t1, q1 = g["ATM1_U"], g["ATM1_V"], g["ATM1_T"], g["ATM1_QV"]
-    pa, pb = g["PSA"][0], g["PSB"][0]
-    msfx, msfd = g["MSFX"][0], g["MSFD"][0]
-    psd = np.zeros_like(pa)
-    psd[1:, 1:] = (pa[1:, 1:] + pa[:-1, 1:] + pa[1:, :-1] + pa[:-1, :-1]) * 0.25
-    rpsd = np.divide(1.0, psd, out=np.zeros_like(psd), where=psd > 0)
-    rpsa = np.divide(1.0, pa, out=np.zeros_like(pa), where=pa > 0)
-    umc, vmc = u1 * msfd, v1 * msfd
-    ud, vd = u1 * rpsd, v1 * rpsd
-    old_err = np.seterr(divide="ignore", invalid="ignore")
-    cr = ((sh(umc, 1, 1) + sh(umc, 1, 0) - sh(umc, 0, 1) - umc) +
-          (sh(vmc, 1, 1) + sh(vmc, 0, 1) - sh(vmc, 1, 0) - vmc)) / (2.0 * dx * msfx * msfx)
-    pten = np.zeros_like(pa)
-    for k in range(kz):
-        pten = pten - cr[k] * dsig[k]
-    qdot = np.zeros((kz + 1,) + pa.shape)
-    for k in range(2, kz + 1):
-        qdot[k - 1] = qdot[k - 2] - (pten + cr[k - 2]) * dsig[k - 2] * rpsa
-    xt = t1 * rpsa
-    xq = np.maximum(q1 * rpsa, minqq)
-    tv = xt * (1.0 + ep1 * xq)
-    u1a = sh(umc, 0, 1) + umc
-    u2a = sh(umc, 1, 1) + sh(umc, 1, 0)
-    v1a = sh(vmc, 1, 0) + vmc
-    v2a = sh(vmc, 1, 1) + sh(vmc, 0, 1)
-    f1 = 0.5 * ul * (u2a + u1a) / pa
-    f2 = 0.5 * ul * (v2a + v1a) / pa
-    xmsf = 1.0 / (msfx * msfx * (4.0 * dx))
-
-    def hadv(c):
-        w, e_, s_, n = sh(c, -1, 0), sh(c, 1, 0), sh(c, 0, -1), sh(c, 0, 1)
-        fx1 = (1.0 + f1) * w + (1.0 - f1) * c
-        fx2 = (1.0 + f1) * c + (1.0 - f1) * e_
-        fy1 = (1.0 + f2) * s_ + (1.0 - f2) * c
-        fy2 = (1.0 + f2) * c + (1.0 - f2) * n
-        return -xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1), w, e_, s_, n
-
-    fg, w, e_, s_, n = hadv(xt)
-    for (p_, m_) in ((n, s_), (e_, w)):
-        big = np.abs(p_ + m_ - 2.0 * xt) / pa > rc.t_extrema
-        fg = np.where(big & (xt > p_) & (xt > m_), np.minimum(fg, 0.0), fg)
-        fg = np.where(big & (xt < p_) & (xt < m_), np.maximum(fg, 0.0), fg)
-    s1 = 0.0 + fg                                                # after hadvt
-    s2 = s1.copy()                                               # after vadv3d ind 1
-    pbh = (hsig[:, None, None] * pb + rc.ptop) * 1000.0
-    pbf = (sig[:, None, None] * pb + rc.ptop) * 1000.0
-    for k in range(2, kz + 1):
-        dq = qdot[k - 1] * (twt1[k] * t1[k - 1] * (pbf[k - 1] / pbh[k - 1]) ** c287 +
-                            twt2[k] * t1[k - 2] * (pbf[k - 1] / pbh[k - 2]) ** c287)
-        s2[k - 2] = s2[k - 2] - dq * (1.0 / dsig[k - 2])
-        s2[k - 1] = s2[k - 1] + dq * (1.0 / dsig[k - 1])
-    dummy = 1.0 / (8.0 * dx * msfx)
-    om = np.zeros_like(t1)
-    for k in range(kz):
-        om[k] = (0.5 * (qdot[k + 1] + qdot[k]) * pa + hsig[k] * (
-            pten + ((ud[k] + sh(ud, 0, 1)[k] + sh(ud, 1, 1)[k] + sh(ud, 1, 0)[k]) * (sh(pa, 1, 0) - sh(pa, -1, 0)) +
-                    (vd[k] + sh(vd, 0, 1)[k] + sh(vd, 1, 1)[k] + sh(vd, 1, 0)[k]) * (sh(pa, 0, 1) - sh(pa, 0, -1))) *
-            dummy))
-    rovcpm = rgas / (cpd * (1.0 + 0.80 * xq))
-    s3 = s2 + (om * rovcpm * tv) / (rc.ptop * rpsa + hsig[:, None, None])     # after the omega term
-    fq, w, e_, s_, n = hadv(xq)
-    den = np.maximum(xq, 1.0e-20)
-    for (p_, m_) in ((n, s_), (e_, w)):
-        big = np.abs(p_ + m_ - 2.0 * xq) / den > rc.q_rel_extrema
-        fq = np.where(big & (xq > p_) & (xq > m_), np.minimum(fq, 0.0), fq)
-        fq = np.where(big & (xq < p_) & (xq < m_), np.maximum(fq, 0.0), fq)
-    q1s = 0.0 + fq                                               # after hadvqv
-    q2s = q1s.copy()                                             # after vadvqv
-    for k in range(2, kz + 1):
-        qcon = (sig[k - 1] - hsig[k - 1]) / (hsig[k - 2] - hsig[k - 1])
-        fk, fkm = q1[k - 1], q1[k - 2]
-        ok = (fk > minqq * pa) & (fkm > minqq * pa)
-        flux = qdot[k - 1] * np.where(ok, fk * (fkm / fk) ** qcon, 0.0)
-        q2s[k - 2] = q2s[k - 2] - flux * (1.0 / dsig[k - 2])
-        q2s[k - 1] = q2s[k - 1] + flux * (1.0 / dsig[k - 1])
-    np.seterr(**old_err)
-    # the relaxation of t on the band (iboudy = 5)
-    band = _cross_band(rc)
-    fnudge, gnudge = 0.1 / rc.dt, 1.0 / (rc.dt * 50.0)
-    anudge = np.where(hsig < 0.4, rc.high_nudge, np.where(hsig < 0.8, rc.medium_nudge, rc.low_nudge))
-    fgb = (g["XTB_B0"] + (xbc + dt0) * g["XTB_BT"]) - g["ATM2_T"]
-    relax = np.zeros_like(s3)
-    lap = sh(fgb, -1, 0) + sh(fgb, 1, 0) + sh(fgb, 0, -1) + sh(fgb, 0, 1) - 4.0 * fgb
-    for (jj, ii), ib in band.items():
-        xfun = np.exp(-((ib - 2) / anudge))
-        relax[:, ii - 1, jj - 1] = (fnudge * xfun) * fgb[:, ii - 1, jj - 1] - (gnudge * xfun) * lap[:, ii - 1, jj - 1]
-    s4 = s3 + relax
-    assert len(band) > 0
-    return dict(s1=s1, s2=s2, s3=s3, s4=s4, q1=q1s, q2=q2s)
 
 
 def off_band(rc):

@@ -9,6 +9,7 @@ import pytest
 from regcm_amd.config import CONFIGS, STATE_FIELDS, set_nproc
 from regcm_amd import icbc
 from regcm_amd.vmodes import vmodes, spinit_constants
+from tests import dyn_ref
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "c1_oracle.json")
 
@@ -631,58 +632,6 @@ def test_nh_wind_tendency_matches_numpy_restatement():
         np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-12 * np.abs(want).max(), err_msg=name)
 
 
-def _cross_band(rc):
-    """{(j, i): ibnd} of the cross-point relaxation band, restating setup_boundaries
-    (Main/mod_atm_interface.F90:383-512) for a domain that is neither a channel (bandflag) nor
-    a CRM: the south/north rows, then the west/east columns, with the corner rules."""
-    jx, iy, nsp = rc.jx, rc.iy, rc.nspgx
-    icx = icy = 1
-    igbb1, igbb2, jgbl1, jgbl2 = 2, nsp - 1, 2, nsp - 1
-    igbt1, igbt2 = iy - icy - nsp + 2, iy - icy - 1
-    jgbr1, jgbr2 = jx - icx - nsp + 2, jx - icx - 1
-    ib = {}
-    for i in range(1, iy + 1):                                   # south
-        if igbb1 <= i <= igbb2:
-            for j in range(1, jx + 1):
-                if jgbl1 <= j <= jgbr2:
-                    if j <= jgbl2 and i >= j:
-                        continue
-                    if j >= jgbr1 and i >= (jgbr2 - j + 2):
-                        continue
-                    ib[(j, i)] = i - igbb1 + 2
-    for i in range(1, iy + 1):                                   # north
-        if igbt1 <= i <= igbt2:
-            for j in range(1, jx + 1):
-                if jgbl1 <= j <= jgbr2:
-                    if j <= jgbl2 and (igbt2 - i + 2) >= j:
-                        continue
-                    if j >= jgbr1 and (igbt2 - i) >= (jgbr2 - j):
-                        continue
-                    ib[(j, i)] = igbt2 - i + 2
-    for i in range(1, iy + 1):                                   # west
-        if i < igbb1 or i > igbt2:
-            continue
-        for j in range(1, jx + 1):
-            if jgbl1 <= j <= jgbl2:
-                if i < igbb2 and j > i:
-                    continue
-                if i > igbt1 and j > (igbt2 - i + 2):
-                    continue
-                ib[(j, i)] = j - jgbl1 + 2
-    for i in range(1, iy + 1):                                   # east
-        if i < igbb1 or i > igbt2:
-            continue
-        for j in range(1, jx + 1):
-            if jgbr1 <= j <= jgbr2:
-                if i < igbb2 and (jgbr2 - j + 2) > i:
-                    continue
-                if i > igbt1 and (jgbr2 - j) > (igbt2 - i):
-                    continue
-                ib[(j, i)] = jgbr2 - j + 2
-    # the nudging loops run over the interior cross points only (jci, ici)
-    return {(j, i): n for (j, i), n in ib.items() if 2 <= j <= jx - 2 and 2 <= i <= iy - 2}
-
-
 def test_hydrostatic_temperature_tendency_matches_numpy_restatement():
     """The hydrostatic t, qv and qc tendencies of the first step against an independent NumPy restatement
     of the reference (C1 with no diffusion, points off the relaxation band): compute_omega's
@@ -696,7 +645,6 @@ def test_hydrostatic_temperature_tendency_matches_numpy_restatement():
     (on a cloud layer) as in the NH check."""
     import dataclasses
     from oracle.oracle import OracleCore
-    from regcm_amd import constants as C
     rc = dataclasses.replace(CONFIGS["C1"], ckh=0.0, adyndif=0.0)
     data = icbc.generate(rc)
     o = OracleCore(rc, data["split"])
@@ -707,143 +655,20 @@ def test_hydrostatic_temperature_tendency_matches_numpy_restatement():
         state[a1] = qc
     o.put_state(state)
     o.bdyval()
-    g = {n: o.get(n) for n in ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "PSA", "PSB", "MSFX",
-                                "MSFD", "ATM2_T", "XTB_B0", "XTB_BT")}
+    g = {n: o.get(n) for n in dyn_ref.HYDRO_INPUTS}
     _, dt0, xbc = o.get_time()
     o.tend()
     tten, qvten, qcten = o.get("TTEN"), o.get("QVTEN"), o.get("QCTEN")
     o.close()
-    kz = rc.kz
-    sig = rc.sigma
-    hsig = (sig[1:] + sig[:-1]) * 0.5
-    dsig = sig[1:] - sig[:-1]
-    twt1 = np.zeros(kz + 1); twt2 = np.zeros(kz + 1)
-    for k in range(2, kz + 1):
-        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
-        twt2[k] = 1.0 - twt1[k]
-    dx = rc.ds * 1000.0
-    ul = rc.uoffc * 0.5 * rc.dt / dx
-    rgas = C.rgas
-    cpd = 3.5 * rgas
-    c287 = rgas / 1000.0                                         # Share/mod_constants.F90:132-134
-    ep1 = 28.96454 / 18.01528 - 1.0                              # amd/amw - 1 (:303)
-    minqq = 1.0e-8
-
-    def sh(a, dj, di):                                           # sh(a)[k, i, j] = a[k, i+di, j+dj]
-        return np.roll(a, shift=(-di, -dj), axis=(-2, -1))
-
-    u1, v1, t1, q1 = g["ATM1_U"], g["ATM1_V"], g["ATM1_T"], g["ATM1_QV"]
-    pa, pb = g["PSA"][0], g["PSB"][0]
-    msfx, msfd = g["MSFX"][0], g["MSFD"][0]
-    psd = np.zeros_like(pa)
-    psd[1:, 1:] = (pa[1:, 1:] + pa[:-1, 1:] + pa[1:, :-1] + pa[:-1, :-1]) * 0.25
-    rpsd = np.divide(1.0, psd, out=np.zeros_like(psd), where=psd > 0)
-    rpsa = np.divide(1.0, pa, out=np.zeros_like(pa), where=pa > 0)
-    umc, vmc = u1 * msfd, v1 * msfd
-    ud, vd = u1 * rpsd, v1 * rpsd
-    with np.errstate(divide="ignore", invalid="ignore"):
-        cr = ((sh(umc, 1, 1) + sh(umc, 1, 0) - sh(umc, 0, 1) - umc) +
-              (sh(vmc, 1, 1) + sh(vmc, 0, 1) - sh(vmc, 1, 0) - vmc)) / (2.0 * dx * msfx * msfx)
-        pten = np.zeros_like(pa)
-        for k in range(kz):
-            pten = pten - cr[k] * dsig[k]
-        qdot = np.zeros((kz + 1,) + pa.shape)
-        for k in range(2, kz + 1):
-            qdot[k - 1] = qdot[k - 2] - (pten + cr[k - 2]) * dsig[k - 2] * rpsa
-    xt = t1 * rpsa
-    xq = np.maximum(q1 * rpsa, minqq)
-    tv = xt * (1.0 + ep1 * xq)
-    # upstream hadvt of atmx%t with the t_extrema limiter (frame-edge values, never compared,
-    # may be inf/nan: p* is zero outside the frame)
-    old_err = np.seterr(divide="ignore", invalid="ignore")
-    u1a = sh(umc, 0, 1) + umc
-    u2a = sh(umc, 1, 1) + sh(umc, 1, 0)
-    v1a = sh(vmc, 1, 0) + vmc
-    v2a = sh(vmc, 1, 1) + sh(vmc, 0, 1)
-    f1 = 0.5 * ul * (u2a + u1a) / pa
-    f2 = 0.5 * ul * (v2a + v1a) / pa
-    c, w, e, s_, n = xt, sh(xt, -1, 0), sh(xt, 1, 0), sh(xt, 0, -1), sh(xt, 0, 1)
-    fx1 = (1.0 + f1) * w + (1.0 - f1) * c
-    fx2 = (1.0 + f1) * c + (1.0 - f1) * e
-    fy1 = (1.0 + f2) * s_ + (1.0 - f2) * c
-    fy2 = (1.0 + f2) * c + (1.0 - f2) * n
-    xmsf = 1.0 / (msfx * msfx * (4.0 * dx))
-    fg = -xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1)
-    for (p_, m_) in ((n, s_), (e, w)):
-        big = np.abs(p_ + m_ - 2.0 * c) / pa > rc.t_extrema
-        fg = np.where(big & (c > p_) & (c > m_), np.minimum(fg, 0.0), fg)
-        fg = np.where(big & (c < p_) & (c < m_), np.maximum(fg, 0.0), fg)
-    tdyn = 0.0 + fg
-    # vadv3d ind 1 (idynamic = 1) on mkslice's b-level pressures
-    pbh = (hsig[:, None, None] * pb + rc.ptop) * 1000.0
-    pbf = (sig[:, None, None] * pb + rc.ptop) * 1000.0
-    for k in range(2, kz + 1):
-        dq = qdot[k - 1] * (twt1[k] * t1[k - 1] * (pbf[k - 1] / pbh[k - 1]) ** c287 +
-                            twt2[k] * t1[k - 2] * (pbf[k - 1] / pbh[k - 2]) ** c287)
-        tdyn[k - 2] = tdyn[k - 2] - dq * (1.0 / dsig[k - 2])
-        tdyn[k - 1] = tdyn[k - 1] + dq * (1.0 / dsig[k - 1])
+    # the restatement itself is tests/dyn_ref.py hydro_tend (the running sums after each process)
+    r = dyn_ref.hydro_tend(rc, g, dt0, xbc)
+    tdyn, tall = r["T"].at["adi"], r["T"].at["bdy"]              # before and after the relaxation of t
+    qdyn, cdyn = r["Q"].at["adv"], r["C"].at["adv"]
+    band = dyn_ref.band(rc)
     nsp = rc.nspgx
     J = np.arange(nsp + 1, rc.jx - nsp)
     I = np.arange(nsp + 1, rc.iy - nsp)
     sl = (slice(None), (I - 1)[:, None], (J - 1)[None, :])
-    # omega (dummy = 1/(dx8 msfx), dx8 = 8 dx, Main/mod_params.F90:1766) and the adiabatic term
-    dummy = 1.0 / (8.0 * dx * msfx)
-    om = np.zeros_like(t1)
-    for k in range(kz):
-        om[k] = (0.5 * (qdot[k + 1] + qdot[k]) * pa + hsig[k] * (
-            pten + ((ud[k] + sh(ud, 0, 1)[k] + sh(ud, 1, 1)[k] + sh(ud, 1, 0)[k]) * (sh(pa, 1, 0) - sh(pa, -1, 0)) +
-                    (vd[k] + sh(vd, 0, 1)[k] + sh(vd, 1, 1)[k] + sh(vd, 1, 0)[k]) * (sh(pa, 0, 1) - sh(pa, 0, -1))) *
-            dummy))
-    rovcpm = rgas / (cpd * (1.0 + 0.80 * xq))
-    tdyn = tdyn + (om * rovcpm * tv) / (rc.ptop * rpsa + hsig[:, None, None])
-    # qv: hadvqv of atmx%qx (q_rel_extrema limiter) + vadvqv of atm1%qx (qcon power form)
-    c, w, e, s_, n = xq, sh(xq, -1, 0), sh(xq, 1, 0), sh(xq, 0, -1), sh(xq, 0, 1)
-    fx1 = (1.0 + f1) * w + (1.0 - f1) * c
-    fx2 = (1.0 + f1) * c + (1.0 - f1) * e
-    fy1 = (1.0 + f2) * s_ + (1.0 - f2) * c
-    fy2 = (1.0 + f2) * c + (1.0 - f2) * n
-    fq = -xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1)
-    den = np.maximum(c, 1.0e-20)
-    for (p_, m_) in ((n, s_), (e, w)):
-        big = np.abs(p_ + m_ - 2.0 * c) / den > rc.q_rel_extrema
-        fq = np.where(big & (c > p_) & (c > m_), np.minimum(fq, 0.0), fq)
-        fq = np.where(big & (c < p_) & (c < m_), np.maximum(fq, 0.0), fq)
-    qdyn = 0.0 + fq
-    for k in range(2, kz + 1):
-        qcon = (sig[k - 1] - hsig[k - 1]) / (hsig[k - 2] - hsig[k - 1])   # Main/mod_params.F90:2214
-        fk, fkm = q1[k - 1], q1[k - 2]
-        ok = (fk > minqq * pa) & (fkm > minqq * pa)
-        flux = qdot[k - 1] * np.where(ok, fk * (fkm / fk) ** qcon, 0.0)
-        qdyn[k - 2] = qdyn[k - 2] - flux * (1.0 / dsig[k - 2])
-        qdyn[k - 1] = qdyn[k - 1] + flux * (1.0 / dsig[k - 1])
-    # qc: hadvqx of atmx%qc + vadv4d ind 1 of atm1%qc (no relaxation of qc: every interior point)
-    qc1 = g["ATM1_QC"]
-    xc = np.maximum(qc1 * rpsa, 0.0)
-    c, w, e, s_, n = xc, sh(xc, -1, 0), sh(xc, 1, 0), sh(xc, 0, -1), sh(xc, 0, 1)
-    fx1 = (1.0 + f1) * w + (1.0 - f1) * c
-    fx2 = (1.0 + f1) * c + (1.0 - f1) * e
-    fy1 = (1.0 + f2) * s_ + (1.0 - f2) * c
-    fy2 = (1.0 + f2) * c + (1.0 - f2) * n
-    cdyn = 0.0 - xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1)
-    for k in range(2, kz + 1):
-        fk, fkm, svv = qc1[k - 1], qc1[k - 2], qdot[k - 1]
-        thr = minqq * minqq * pa
-        ok = np.where(svv > 0.0, fkm > thr, fk > thr)
-        flux = np.where(ok, svv * (twt1[k] * fk + twt2[k] * fkm), 0.0)
-        cdyn[k - 2] = cdyn[k - 2] - flux * (1.0 / dsig[k - 2])
-        cdyn[k - 1] = cdyn[k - 1] + flux * (1.0 / dsig[k - 1])
-    np.seterr(**old_err)
-    # the band: relaxation of t toward the boundary data (iboudy = 5), at every interior point
-    band = _cross_band(rc)
-    fnudge, gnudge = 0.1 / rc.dt, 1.0 / (rc.dt * 50.0)           # Main/mod_bdycod.F90:204-215
-    anudge = np.where(hsig < 0.4, rc.high_nudge, np.where(hsig < 0.8, rc.medium_nudge, rc.low_nudge))
-    fg = (g["XTB_B0"] + (xbc + dt0) * g["XTB_BT"]) - g["ATM2_T"]  # nudge3d, :4242-4245
-    relax = np.zeros_like(tdyn)
-    lap = sh(fg, -1, 0) + sh(fg, 1, 0) + sh(fg, 0, -1) + sh(fg, 0, 1) - 4.0 * fg
-    for (jj, ii), ib in band.items():
-        xfun = np.exp(-((ib - 2) / anudge))                      # hefc, hegc (:258-267)
-        relax[:, ii - 1, jj - 1] = (fnudge * xfun) * fg[:, ii - 1, jj - 1] - (gnudge * xfun) * lap[:, ii - 1, jj - 1]
-    tall = tdyn + relax
     Jc = np.arange(2, rc.jx - 1)
     Ic = np.arange(2, rc.iy - 1)
     sc = (slice(None), (Ic - 1)[:, None], (Jc - 1)[None, :])
@@ -1010,42 +835,17 @@ def test_nh_diffusion_matches_numpy_restatement():
     fourth-order interior operator and the second-order rows on the boundary ring (the corners
     take both rows).  Checked as the difference of the first-step tendencies with ckh =
     adyndif = 1 and with both 0 (xkc = 0); everything else is the same computation."""
-    from regcm_amd import constants as C
-    (rc, g0), (_, g1) = _nh_tend_pair({"ckh": 0.0, "adyndif": 0.0, "ifrayd": 0}, {"ifrayd": 0})
+    (_, g0), (rc, g1) = _nh_tend_pair({"ckh": 0.0, "adyndif": 0.0, "ifrayd": 0}, {"ifrayd": 0})   # rc: ckh = adyndif = 1
     kz, jx, iy = rc.kz, rc.jx, rc.iy
-    dx = rc.ds * 1000.0
-    dxsq = dx * dx
-    xkhz = 1.0 * dx
-    xkhmax = 2.0 * (dxsq / (64.0 * rc.dt))
-    dydc = 1.0 * 0.4 * 0.4 * dx * 0.25
     pb = g1["PSB"][0]
     rpsb = np.divide(1.0, pb, out=np.zeros_like(pb), where=pb > 0)
-    # interior dot points' psdotb (4-point mean; calc_coeff at ci points reads only those)
-    psd = np.zeros_like(pb)
-    psd[1:, 1:] = (pb[1:, 1:] + pb[:-1, 1:] + pb[1:, :-1] + pb[:-1, :-1]) * 0.25
-    rpsd = np.divide(1.0, psd, out=np.zeros_like(psd), where=psd > 0)
-    ud, vd = g1["ATM2_U"] * rpsd[None], g1["ATM2_V"] * rpsd[None]
     wx = g1["ATM2_W"] * rpsb[None]
-    ht = g1["HT"][0]
     J = np.arange(2, jx - 1)          # jci (1-based)
     I = np.arange(2, iy - 1)
 
     def at(a, dj=0, di=0):
         return a[..., (I + di - 1)[:, None], (J + dj - 1)[None, :]]
-    if rc.diffu_hgtf == 1:
-        hg = [np.abs((at(ht) - at(ht, 0, -1)) / dx), np.abs((at(ht) - at(ht, 0, 1)) / dx),
-              np.abs((at(ht) - at(ht, -1, 0)) / dx), np.abs((at(ht) - at(ht, 1, 0)) / dx)]
-        hgmax = np.maximum(np.maximum(hg[0], hg[1]), np.maximum(hg[2], hg[3])) * C.regrav * 1.0e3
-        hgfact = xkhz / (1.0 + hgmax * hgmax)
-    else:                          # the NH default (dynparam, Main/mod_params.F90:648-652)
-        hgfact = np.full(at(ht).shape, xkhz)
-    dudx = at(ud, 1, 0) + at(ud, 1, 1) - at(ud) - at(ud, 0, 1)
-    dvdx = at(vd, 1, 0) + at(vd, 1, 1) - at(vd) - at(vd, 0, 1)
-    dudy = at(ud, 0, 1) + at(ud, 1, 1) - at(ud) - at(ud, 1, 0)
-    dvdy = at(vd, 0, 1) + at(vd, 1, 1) - at(vd) - at(vd, 1, 0)
-    dwdz = at(wx)[:kz] - at(wx)[1:kz + 1]
-    duv = np.sqrt(np.maximum((dudx - dvdy) * (dudx - dvdy) + (dvdx + dudy) * (dvdx + dudy) - dwdz * dwdz, 0.0))
-    xkc = np.minimum(hgfact[None] + dydc * duv, xkhmax) * (1.0 / dxsq) * at(pb)[None]
+    xkc = at(dyn_ref.nh_xkc(rc, g1))  # calc_coeff of this core: tests/dyn_ref.py nh_coeff
 
     def diffu(f, xk):
         """diffu_x3d / diffu_x4d3d / diffu_x3df (fac = 1) on the jci x ici points with the
@@ -1157,107 +957,19 @@ def test_hydrostatic_wind_tendency_matches_numpy_restatement():
     Share/mod_constants.F90:319-320; tvfac = 1/(1 + qc/(1 + qv))) and its gradient."""
     import dataclasses
     from oracle.oracle import OracleCore
-    from regcm_amd import constants as C
     rc = dataclasses.replace(CONFIGS["C1"], ckh=0.0, adyndif=0.0)
     assert rc.ipgf == 0
     data = icbc.generate(rc)
     o = OracleCore(rc, data["split"])
     o.put_state(data["state"])
     o.bdyval()
-    g = {n: o.get(n) for n in ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "PSA", "MSFX", "MSFD",
-                                "CORIOL", "HT")}
+    g = {n: o.get(n) for n in dyn_ref.HYDRO_INPUTS}
+    _, dt0, xbc = o.get_time()
     o.tend()
     uten, vten = o.get("UTEN"), o.get("VTEN")
     o.close()
-    kz = rc.kz
-    sig = rc.sigma
-    hsig = (sig[1:] + sig[:-1]) * 0.5
-    dsig = sig[1:] - sig[:-1]
-    twt1 = np.zeros(kz + 1); twt2 = np.zeros(kz + 1)
-    for k in range(2, kz + 1):
-        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
-        twt2[k] = 1.0 - twt1[k]
-    dx = rc.ds * 1000.0
-    ul = rc.uoffc * 0.5 * rc.dt / dx
-    rgas = C.rgas
-    ep1 = 28.96454 / 18.01528 - 1.0
-    minqq = 1.0e-8
-    ptop = rc.ptop
-
-    def sh(a, dj, di):                                           # sh(a)[k, i, j] = a[k, i+di, j+dj]
-        return np.roll(a, shift=(-di, -dj), axis=(-2, -1))
-
-    old_err = np.seterr(divide="ignore", invalid="ignore")      # frame edges: never compared
-    u1, v1, t1 = g["ATM1_U"], g["ATM1_V"], g["ATM1_T"]
-    pa, msfx, msfd = g["PSA"][0], g["MSFX"][0], g["MSFD"][0]
-    psd = np.zeros_like(pa)
-    psd[1:, 1:] = (pa[1:, 1:] + pa[:-1, 1:] + pa[1:, :-1] + pa[:-1, :-1]) * 0.25
-    rpsd = np.divide(1.0, psd, out=np.zeros_like(psd), where=psd > 0)
-    rpsa = np.divide(1.0, pa, out=np.zeros_like(pa), where=pa > 0)
-    umc, vmc = u1 * msfd, v1 * msfd
-    ud, vd = u1 * rpsd, v1 * rpsd
-    # compute_omega's qdot (hydrostatic scan) for vadvuv
-    cr = ((sh(umc, 1, 1) + sh(umc, 1, 0) - sh(umc, 0, 1) - umc) +
-          (sh(vmc, 1, 1) + sh(vmc, 0, 1) - sh(vmc, 1, 0) - vmc)) / (2.0 * dx * msfx * msfx)
-    pten = np.zeros_like(pa)
-    for k in range(kz):
-        pten = pten - cr[k] * dsig[k]
-    qdot = np.zeros((kz + 1,) + pa.shape)
-    for k in range(2, kz + 1):
-        qdot[k - 1] = qdot[k - 2] - (pten + cr[k - 2]) * dsig[k - 2] * rpsa
-    # hadvuv, hydrostatic upstream branch
-    ucmona = sh(umc, 0, 1) + 2.0 * umc + sh(umc, 0, -1)
-    ucmonb = sh(umc, 1, 1) + 2.0 * sh(umc, 1, 0) + sh(umc, 1, -1)
-    ucmonc = sh(umc, -1, 1) + 2.0 * sh(umc, -1, 0) + sh(umc, -1, -1)
-    vcmona = sh(vmc, 1, 0) + 2.0 * vmc + sh(vmc, -1, 0)
-    vcmonb = sh(vmc, 1, 1) + 2.0 * sh(vmc, 0, 1) + sh(vmc, -1, 1)
-    vcmonc = sh(vmc, 1, -1) + 2.0 * sh(vmc, 0, -1) + sh(vmc, -1, -1)
-    ff1, ff2 = ul * (sh(ud, 1, 0) + ud), ul * (sh(ud, -1, 0) + ud)
-    ff3, ff4 = ul * (sh(vd, 0, 1) + vd), ul * (sh(vd, 0, -1) + vd)
-    ucb = (1.0 + ff1) * ucmona + (1.0 - ff1) * ucmonb
-    ucc_ = (1.0 + ff2) * ucmonc + (1.0 - ff2) * ucmona
-    vcb = (1.0 + ff3) * vcmona + (1.0 - ff3) * vcmonb
-    vcc_ = (1.0 + ff4) * vcmonc + (1.0 - ff4) * vcmona
-    dm = 1.0 / (msfd * msfd * 16.0 * dx)
-    udyn = -dm * ((sh(ud, 1, 0) + ud) * ucb - (ud + sh(ud, -1, 0)) * ucc_ +
-                  (sh(ud, 0, 1) + ud) * vcb - (ud + sh(ud, 0, -1)) * vcc_)
-    vdyn = -dm * ((sh(vd, 1, 0) + vd) * ucb - (vd + sh(vd, -1, 0)) * ucc_ +
-                  (sh(vd, 0, 1) + vd) * vcb - (vd + sh(vd, 0, -1)) * vcc_)
-    for k in range(2, kz + 1):                                   # vadvuv of atm1 u, v
-        qq = 0.25 * (qdot[k - 1] + sh(qdot, 0, -1)[k - 1] + sh(qdot, -1, 0)[k - 1] + sh(qdot, -1, -1)[k - 1])
-        uu = qq * (twt1[k] * u1[k - 1] + twt2[k] * u1[k - 2])
-        vv = qq * (twt1[k] * v1[k - 1] + twt2[k] * v1[k - 2])
-        udyn[k - 2] = udyn[k - 2] - uu / dsig[k - 2]
-        udyn[k - 1] = udyn[k - 1] + uu / dsig[k - 1]
-        vdyn[k - 2] = vdyn[k - 2] - vv / dsig[k - 2]
-        vdyn[k - 1] = vdyn[k - 1] + vv / dsig[k - 1]
-    cor = g["CORIOL"][0]                                         # Coriolis
-    udyn = udyn + cor * v1
-    vdyn = vdyn - cor * u1
-    # pressure-gradient force, ipgf = 0: the log-p* part
-    xq = np.maximum(g["ATM1_QV"] * rpsa, minqq)
-    xc = np.maximum(g["ATM1_QC"] * rpsa, 0.0)
-    tv = (t1 * rpsa) * (1.0 + ep1 * xq)
-    rtbar = 0.25 * (sh(tv, -1, -1) + sh(tv, -1, 0) + sh(tv, 0, -1) + tv)
-    rtbar = rgas * rtbar * psd
-    h = hsig[:, None, None]
-    udyn = udyn - rtbar * (np.log(0.5 * (pa + sh(pa, 0, -1)) * h + ptop) -
-                           np.log(0.5 * (sh(pa, -1, 0) + sh(pa, -1, -1)) * h + ptop)) / (dx * msfd)
-    vdyn = vdyn - rtbar * (np.log(0.5 * (pa + sh(pa, -1, 0)) * h + ptop) -
-                           np.log(0.5 * (sh(pa, -1, -1) + sh(pa, 0, -1)) * h + ptop)) / (dx * msfd)
-    # geopotential (half levels, cross points) and its gradient
-    td = t1 * (1.0 + ep1 * xq)
-    tvfac = 1.0 / (1.0 + xc / (1.0 + xq))
-    phi = np.zeros_like(t1)
-    phi[kz - 1] = g["HT"][0] - rgas * (td[kz - 1] * rpsa * tvfac[kz - 1]) * np.log(
-        (hsig[kz - 1] + ptop * rpsa) / (1.0 + ptop * rpsa))
-    for lev in range(kz - 1, 0, -1):                             # 1-based lev = kz-1 .. 1
-        tvavg = ((td[lev - 1] * dsig[lev - 1] + td[lev] * dsig[lev]) /
-                 (pa * (dsig[lev - 1] + dsig[lev]))) * tvfac[lev - 1]
-        phi[lev - 1] = phi[lev] - rgas * tvavg * np.log((hsig[lev - 1] + ptop * rpsa) / (hsig[lev] + ptop * rpsa))
-    udyn = udyn - psd * (phi + sh(phi, 0, -1) - sh(phi, -1, 0) - sh(phi, -1, -1)) / (2.0 * dx * msfd)
-    vdyn = vdyn - psd * (phi + sh(phi, -1, 0) - sh(phi, 0, -1) - sh(phi, -1, -1)) / (2.0 * dx * msfd)
-    np.seterr(**old_err)
+    r = dyn_ref.hydro_tend(rc, g, dt0, xbc)                      # tests/dyn_ref.py: the sums after the last term
+    udyn, vdyn = r["U"].v, r["V"].v
     nsp = rc.nspgx
     J = np.arange(nsp + 2, rc.jx - nsp)                          # dot points off the band
     I = np.arange(nsp + 2, rc.iy - nsp)

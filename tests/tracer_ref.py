@@ -1,7 +1,7 @@
 """A NumPy statement of the reference's chain of one chemical tracer through one tend and one bdyval
 of either core on one limited-area tile (ichem = 1, ichebdy = 1), written from the Fortran text.  The
 two cores differ for a tracer only in the diffusion coefficient they hand it (the non-hydrostatic
-calc_coeff is restated here, nh_xkc) and in gnu2: the NH adiabatic term atmx%qx * cr runs over
+calc_coeff is restated in tests/dyn_ref.py, nh_xkc) and in gnu2: the NH adiabatic term atmx%qx * cr runs over
 n = 1..nqx only (Main/mod_tendency.F90:1615-1617).  Test infrastructure: tests/test_tracers_gpu.py compares the engine with it bit for bit,
 tests/test_tracers_cpu.py checks its own vectorised negative-value fix against a plain triple loop.
 
@@ -14,7 +14,7 @@ round as the Fortran does.
   hadvtr           both upstream_mode branches                 Main/mod_advection.F90:666-720
   vadv4d, ind = 2  threshold mintr * ps                        Main/mod_advection.F90:895-916, 958-961
   vadv4d, ind = 3  the PBL-top rule (ibltyp 2, iuwvadv 1)      Main/mod_advection.F90:917-957
-  calc_coeff (NH)  xkc with the vertical-velocity term         Main/mod_diffusion.F90:215-250
+  calc_coeff (NH)  tests/dyn_ref.py nh_xkc                     Main/mod_diffusion.F90:215-250
   nudge_chiten     ichebdy = 1, on atm2                        Main/chemlib/mod_che_bdyco.F90:898-982
   diffu_x4d        idiffu 1 and 2, on chib3d                   Main/mod_diffusion.F90:805-892
   chib3d           max(atm2 * rpsb, 0)                         Main/mod_slice.F90:196-200
@@ -31,6 +31,8 @@ import dataclasses
 
 import numpy as np
 
+from tests.dyn_ref import band_sides, nh_xkc  # noqa: F401  (nh_xkc: the tracer tests read it from here)
+
 MINTR = 1.0e-30                 # Share/mod_constants.F90:63
 RAW_BETA = 0.53                 # Main/mod_tendency.F90:585
 Z4 = (1.0, -4.0, 12.0)          # z4_c1..3, Main/mod_diffusion.F90
@@ -45,28 +47,12 @@ def chib3d(atm2, psb):
 
 
 def relaxation_band(rc):
-    """(side, ibnd) of the cross relaxation band ba_cr (setup_boundaries, Main/mod_atm_interface.F90:
-    383-542, ldot = .false.): side 0 none, 1 south, 2 north, 3 west, 4 east, on (i, j) planes."""
-    jx, iy, nsp = rc.jx, rc.iy, rc.nspgx
-    side = np.zeros((iy, jx), dtype=np.int8)
-    ibnd = np.full((iy, jx), -1, dtype=np.int16)
-    igbb1, igbb2, jgbl1, jgbl2 = 2, nsp - 1, 2, nsp - 1
-    igbt1, igbt2 = iy - 1 - nsp + 2, iy - 2
-    jgbr1, jgbr2 = jx - 1 - nsp + 2, jx - 2
-    for i in range(1, iy + 1):
-        for j in range(1, jx + 1):
-            if igbb1 <= i <= igbb2 and jgbl1 <= j <= jgbr2:
-                if not (j <= jgbl2 and i >= j) and not (j >= jgbr1 and i >= jgbr2 - j + 2):
-                    side[i - 1, j - 1], ibnd[i - 1, j - 1] = 1, i - igbb1 + 2
-            if igbt1 <= i <= igbt2 and jgbl1 <= j <= jgbr2:
-                if not (j <= jgbl2 and igbt2 - i + 2 >= j) and not (j >= jgbr1 and igbt2 - i >= jgbr2 - j):
-                    side[i - 1, j - 1], ibnd[i - 1, j - 1] = 2, igbt2 - i + 2
-            if igbb1 <= i <= igbt2 and jgbl1 <= j <= jgbl2:
-                if not (i < igbb2 and j > i) and not (i > igbt1 and j > igbt2 - i + 2):
-                    side[i - 1, j - 1], ibnd[i - 1, j - 1] = 3, j - jgbl1 + 2
-            if igbb1 <= i <= igbt2 and jgbr1 <= j <= jgbr2:
-                if not (i < igbb2 and jgbr2 - j + 2 > i) and not (i > igbt1 and jgbr2 - j > igbt2 - i):
-                    side[i - 1, j - 1], ibnd[i - 1, j - 1] = 4, jgbr2 - j + 2
+    """(side, ibnd) of the cross relaxation band ba_cr on (i, j) planes, from the one statement of
+    setup_boundaries (tests/dyn_ref.py band_sides): side 0 none, 1 south, 2 north, 3 west, 4 east."""
+    side = np.zeros((rc.iy, rc.jx), dtype=np.int8)
+    ibnd = np.full((rc.iy, rc.jx), -1, dtype=np.int16)
+    for (j, i), (sd, ib) in band_sides(rc, dot=False).items():
+        side[i - 1, j - 1], ibnd[i - 1, j - 1] = sd, ib
     return side, ibnd
 
 
@@ -95,41 +81,6 @@ class StepInputs:
             xmapf = 1.0 / (msfx * msfx * dx4)
         return cls(st["PSA"][0], st["PSB"][0], st["ATM1_U"] * st["MSFD"][0][None], st["ATM1_V"] * st["MSFD"][0][None],
                    xmapf, qdot, xkc, dt, xt_tend, xt_bdyval, integrating, kpbl)
-
-
-def nh_xkc(rc, st):
-    """calc_coeff of the non-hydrostatic core (Main/mod_diffusion.F90:215-250) on jci x ici, scaled as
-    its readers scale it (xkc = xkcr * rdxsq * psb): the Smagorinsky deformation of the decoupled b
-    winds (atm2 / psdotb, psdotb the four-point mean of psb, Main/mpplib/mod_mppparam.F90:13811-13862)
-    less the vertical-velocity term, hgfact = xkhz = ckh * dx (diffu_hgtf = 0) and the NH xkhmax."""
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
-    dx = rc.ds * 1000.0
-    dxsq = dx * dx
-    xkhz = rc.ckh * dx
-    dydc = rc.adyndif * 0.4 * 0.4 * dx * 0.25
-    xkhmax = 2.0 * (dxsq / (64.0 * rc.dt))
-    psb = st["PSB"][0]
-    pd = np.ones((iy, jx))
-    pd[1:, 1:] = (psb[1:, 1:] + psb[:-1, 1:] + psb[1:, :-1] + psb[:-1, :-1]) * 0.25
-    rd = 1.0 / pd
-    ub, vb = st["ATM2_U"] * rd[None], st["ATM2_V"] * rd[None]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        wb = st["ATM2_W"] * (1.0 / psb)[None]
-
-    def at(a, di=0, dj=0):
-        return a[..., 1 + di:iy - 2 + di, 1 + dj:jx - 2 + dj]
-    u00, u10, u01, u11 = at(ub), at(ub, 0, 1), at(ub, 1, 0), at(ub, 1, 1)
-    v00, v10, v01, v11 = at(vb), at(vb, 0, 1), at(vb, 1, 0), at(vb, 1, 1)
-    dudx = u10 + u11 - u00 - u01
-    dvdx = v10 + v11 - v00 - v01
-    dudy = u01 + u11 - u00 - u10
-    dvdy = v01 + v11 - v00 - v10
-    dwdz = at(wb)[:-1] - at(wb)[1:]
-    duv = np.sqrt(np.maximum((dudx - dvdy) * (dudx - dvdy) + (dvdx + dudy) * (dvdx + dudy) - dwdz * dwdz, 0.0))
-    xkcr = np.minimum(xkhz + dydc * duv, xkhmax)
-    out = np.zeros((kz, iy, jx))
-    out[:, 1:iy - 2, 1:jx - 2] = xkcr * (1.0 / dxsq) * at(psb)[None]
-    return out
 
 
 @dataclasses.dataclass
