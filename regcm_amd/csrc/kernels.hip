@@ -1176,7 +1176,7 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   if (!g.gci(j, i)) {
     ST(f.cqv, o3, qv2);
     ST(f.cqc, o3, qc2);
-    if (O::has(f.xkcs)) ST(f.xkcs, o3, xkc);
+    if (O::has(f.xkcs)) ST(f.xkcs, o3, O::idiffu(c) == 3 ? d_zero : xkc);   // idiffu = 3 writes jci x ici only
     return;
   }
   const double dt = s->dt;
@@ -1194,7 +1194,8 @@ __device__ __forceinline__ void scalars_block(const Geom& g, const Consts* __res
   const double vavg1 = DT(sVMC, 1, 0) + DT(sVMC, 0, 0);
   const double vavg2 = DT(sVMC, 1, 1) + DT(sVMC, 0, 1);
   const double ps = H1T(sPS, 0, 0);
-  const double xkcs = xkc * c->rdxsq * pb;
+  // (idiffu = 3: calc_coeff leaves diff_6th_coef * p*b, :174-177; nothing below reads it there)
+  const double xkcs = O::idiffu(c) == 3 ? c->diff6 * pb : xkc * c->rdxsq * pb;
   if (O::has(f.xkcs)) ST(f.xkcs, o3, xkcs);
   // diffu_x from a halo-2 LDS tile (Main/mod_diffusion.F90:673-735, 881-891); idiffu = 3: the
   // column term of k_diffu6, on j = jci2 and on the ring column that is the left neighbour's

@@ -28,6 +28,19 @@ Tolerances.
  - Totals: rtol 1e-10, atol 1e-11 * max|want| (the tolerance of the existing restatements: libm
    pow / log), at every point of jci x ici (t, qv, qc) and jdi x idi (u, v), the band included.
 
+ipgf = 1 ({"ipgf": 1} alone and with iboudy 1): PHI at every cross point of jce x ice and UTEN, VTEN at
+every point of jdi x idi at the totals' tolerance.  Not vacuous: the restatement with either of its
+two ipgf branches put back to the ipgf = 0 form misses UTEN / VTEN by more than 1000 x that tolerance
+at more than half of the points, and the ipgf = 0 PHI differs from the ipgf = 1 PHI by more than 1000 x
+the tolerance at every cross point.
+
+idiffu = 3: XKC bit for bit; the diffusion of t, qv, qc, u, v as the difference from a run of idiffu = 1
+with ckh = adyndif = 0 (xkc = 0) from identical state, with the counts above (the scheme makes one add
+per point, so they are upper bounds).  The support is the single column jci2 / jdi2, asserted non-zero
+at every row and zero off it.  From the restatement alone: each of the four fluxes is zeroed by its
+limiter at 1 % or more of the column's points and kept at 1 % or more, and the rows i <= 3 and
+i >= iy - 3, where the i-clamp acts, are compared and non-zero.
+
 Each term check asserts that it is not vacuous: the oracle's term is non-zero (at some level) at
 every ring point and corner (diffusion) or band point (relaxation) and zero off its support, and
 the median of |term| / bound over the support is at least 2**20, so a relative error of 1e-6 in a
@@ -86,7 +99,7 @@ def _oracle_run(grid, vkey, okey):
     g = {n: o.get(n) for n in dr.HYDRO_INPUTS}
     _, dt0, xbc = o.get_time()
     o.tend()
-    out = {n: o.get(n) for n in ("TTEN", "QVTEN", "QCTEN", "UTEN", "VTEN", "XKC", "PTEN")}
+    out = {n: o.get(n) for n in ("TTEN", "QVTEN", "QCTEN", "UTEN", "VTEN", "XKC", "PTEN", "PHI", "QDOT")}
     o.close()
     return rcv, g, (dt0, xbc), out
 
@@ -260,3 +273,110 @@ def test_totals(grid, variant):
         tol = 1e-10 * np.abs(want) + 1e-11 * np.abs(want).max()
         print(f"{grid} {variant_id(variant)} {name}: worst |err| / tolerance = {(np.abs(got - want) / tol).max():.3e}")
         np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-11 * np.abs(want).max(), err_msg=name)
+
+
+# ------------------------------------------------------------------------------ ipgf = 1
+PGF_VARIANTS = [{"ipgf": 1}, {"ipgf": 1, "iboudy": 1}]
+MUTANT_FACTOR = 1000.0
+
+
+def totals_tol(want):
+    """The totals' tolerance (libm pow / log rows) as an array: rtol 1e-10, atol 1e-11 * max|want|."""
+    return 1e-10 * np.abs(want) + 1e-11 * np.abs(want).max()
+
+
+def check_ipgf1(tag, rc, g, times, out, tiles=None):
+    """out (the oracle's or the engine's PHI, UTEN, VTEN of one tend from g) against the restated
+    ipgf = 1 branches, with the non-vacuity asserts."""
+    assert rc.ipgf == 1
+    r = dr.hydro_tend(rc, g, *times, tiles=tiles)
+    r0 = dr.hydro_tend(dataclasses.replace(rc, ipgf=0), g, *times, tiles=tiles)
+    iy, jx = rc.iy, rc.jx
+    want, got, want0 = (a[:, :iy - 1, :jx - 1] for a in (r["phi"], out["PHI"], r0["phi"]))
+    tol = totals_tol(want)
+    print(f"{tag} PHI: worst |err| / tolerance = {(np.abs(got - want) / tol).max():.3e}, "
+          f"least |ipgf 0 - ipgf 1| / tolerance = {(np.abs(want0 - want) / tol).min():.3e}")
+    assert (np.abs(want0 - want) > MUTANT_FACTOR * tol).all()
+    np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-11 * np.abs(want).max(), err_msg="PHI")
+    m = dr.domain_mask(rc, True)
+    mutants = {rv: dr.hydro_tend(rc, g, *times, revert=rv, tiles=tiles) for rv in ("rtbar", "phi")}
+    for name in ("UTEN", "VTEN"):
+        want, got = r[name][:, m], out[name][:, m]
+        tol = totals_tol(want)
+        miss = {rv: float((np.abs(got - mu[name][:, m]) > MUTANT_FACTOR * tol).mean()) for rv, mu in mutants.items()}
+        print(f"{tag} {name}: worst |err| / tolerance = {(np.abs(got - want) / tol).max():.3e}; the points a "
+              f"reverted branch misses by > {MUTANT_FACTOR:g} x tolerance: {miss}")
+        for rv, frac in miss.items():
+            assert frac > 0.5, (name, rv, frac)
+        for i, pg in enumerate(r[name[0].lower() + "_pgf"]):     # each increment carries weight of its own
+            assert (np.abs(pg[:, m]) > MUTANT_FACTOR * tol).mean() > 0.5, (name, i)
+        np.testing.assert_allclose(got, want, rtol=1e-10, atol=1e-11 * np.abs(want).max(), err_msg=name)
+
+
+@pytest.mark.parametrize("grid,variant", [(g, v) for g in GRIDS for v in PGF_VARIANTS],
+                         ids=lambda p: p if isinstance(p, str) else variant_id(p))
+def test_ipgf1_phi_and_winds(grid, variant):
+    rc, g, times, out = oracle_run(grid, variant)
+    check_ipgf1(f"{grid} {variant_id(variant)}", rc, g, times, out)
+
+
+# ------------------------------------------------------------------------------ idiffu = 3
+D6 = {"idiffu": 3}
+D6_OFF = dict(idiffu=1, **NO_DIF)
+
+
+def column_mask(rc, dot, tiles=None):
+    """[i, j] of the points the idiffu = 3 term is added at."""
+    m = np.zeros((rc.iy, rc.jx), dtype=bool)
+    for j, i1, i2 in dr.tile_columns(rc, dot, tiles):
+        m[i1 - 1:i2, j - 1] = True
+    return m
+
+
+def check_diffu6_edges(tag, rc, g, r, tiles=None):
+    """From the restatement alone: the limiter zeroes and keeps each flux of each field at 1 % or more
+    of the column's points, and the rows where the i-clamp acts are on the columns and non-zero."""
+    ub, vb, tb, qvb, qcb, _ = dr.b_slices(g)
+    msfd = g["MSFD"][0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fields = (("t", tb, tb / msfd, False), ("qv", qvb, qvb / msfd, False), ("qc", qcb, qcb / msfd, False),
+                  ("u", ub / msfd, ub / msfd, True), ("v", vb / msfd, vb / msfd, True))
+        for name, fv, lv, dot in fields:
+            fl, mask = dr.fluxes6(rc, fv, lv, dr.tile_columns(rc, dot, tiles), dot)
+            assert np.array_equal(mask, column_mask(rc, dot, tiles))
+            for fx, (raw, lim) in fl.items():
+                live = raw[:, mask] != 0.0                       # (qc is zero off its cloud layer)
+                zeroed = float(((lim[:, mask] == 0.0) & live).sum() / live.sum())
+                print(f"{tag} {name} {fx}: zeroed by the limiter at {zeroed:.3f} of the column's points")
+                assert 0.01 <= zeroed <= 0.99, (name, fx, zeroed)
+            want = dr.total(r[{"t": "t", "qv": "q", "qc": "c", "u": "u", "v": "v"}[name] + "_dif"])
+            ihi = rc.iy - 1 if dot else rc.iy - 2                # idi2 / ici2
+            rows = [i for i in range(2, ihi + 1) if i <= 3 or i >= rc.iy - 3]
+            assert len(rows) == (5 if dot else 4)
+            for i in rows:
+                assert mask[i - 1].any(), (name, i)
+                assert (np.abs(want[:, i - 1, :]).max(axis=0)[mask[i - 1]] > 0.0).all(), (name, i)
+
+
+@pytest.mark.parametrize("grid", list(GRIDS))
+def test_idiffu3_xkc_and_terms(grid):
+    rc, g1, times, full = oracle_run(grid, D6)
+    _, g0, _, off = oracle_run(grid, D6, **D6_OFF)
+    same_state(g1, g0)
+    r = dr.hydro_tend(rc, g1, *times)
+    m = dr.domain_mask(rc)
+    coef = 0.12 * 0.015625 / (2.0 * rc.dt)
+    assert np.array_equal(r["coeff"]["xkc"][:, m], np.broadcast_to(coef * g1["PSB"][0][m], (rc.kz, m.sum())))
+    assert np.array_equal(full["XKC"][:, m], r["coeff"]["xkc"][:, m])
+    assert not off["XKC"].any()
+    check_diffu6_edges(f"{grid} idiffu=3", rc, g1, r)
+    for name, key, dot in TOTALS:
+        dom, col = dr.domain_mask(rc, dot), column_mask(rc, dot)
+        assert col.sum() == (rc.iy - 2 if dot else rc.iy - 3) and (col & dom).sum() == col.sum()
+        big = np.fmax(r[key].big, np.abs(r[name]))
+        check_term(f"{grid} idiffu=3 {name} diffusion", full[name] - off[name], r[key.lower() + "_dif"], big,
+                   N_ADD[(key, "dif")], col, dom)
+    for name, _, dot in TOTALS:                                  # and the assembled totals
+        md = dr.domain_mask(rc, dot)
+        np.testing.assert_allclose(full[name][:, md], r[name][:, md], rtol=1e-10,
+                                   atol=1e-11 * np.abs(r[name][:, md]).max(), err_msg=name)

@@ -22,6 +22,16 @@ Tolerances.
  - Totals (TTEN, QVTEN, QCTEN, UTEN, VTEN; under iboudy 4 they hold the sponge): rtol 1e-10, atol
    1e-11 * max|want|, at every interior point, the band included.
 
+ipgf = 1 (alone and with iboudy 1, both grids, 2 x 2 tiles on 37 x 29): PHI (the engine's read-only
+diagnostic) at every cross point and UTEN, VTEN at every point of jdi x idi at the totals' tolerance,
+with the reverted-branch asserts of tests/test_dyn_rows_cpu.py.
+
+idiffu = 3 (both grids, 2 x 2 tiles on 37 x 29, where the term sits on each tile's last interior column
+and the interior tile's clamp does not act; the tile bounds are read from the host-side decomposition):
+XKC bit for bit; T_DIF and Q_DIF through the budget (n = 3); the diffusion of u, v and qc as the
+difference from idiffu = 1 with ckh = adyndif = 0 from identical state (n = 9, 9, 5); T_DIF / Q_DIF of the
+non-hydrostatic core on N1 cut to 37 x 29; the limiter and clamp-row asserts from the restatement.
+
 The same non-vacuity asserts as on the CPU: each term non-zero on all of its support and zero off
 it, median |term| / bound >= 2**20.
 """
@@ -31,11 +41,12 @@ import functools
 import numpy as np
 import pytest
 
-from regcm_amd.dycore import BUDGET_TERMS
+from regcm_amd.dycore import BUDGET_TERMS, tile_extent
 from tests import dyn_ref as dr
 from tests import support
 from tests.support import case, variant_id
-from tests.test_dyn_rows_cpu import GRIDS, N_ADD, NO_DIF, TOTALS, check_term, prepared, same_state, sponge_support, start
+from tests.test_dyn_rows_cpu import (D6, D6_OFF, GRIDS, N_ADD, NO_DIF, PGF_VARIANTS, TOTALS, check_diffu6_edges,
+                                     check_ipgf1, check_term, column_mask, prepared, same_state, sponge_support, start)
 
 pytestmark = pytest.mark.gpu
 
@@ -62,7 +73,7 @@ def _tend(rc, data, st, nproc, inputs):
     g = {n: e.get(n) for n in inputs}
     _, dt0, xbc = e.get_time()
     e.tend()
-    out = {n: e.get(n) for n in ("TTEN", "QVTEN", "QCTEN", "UTEN", "VTEN", "XKC", "PTEN")}
+    out = {n: e.get(n) for n in ("TTEN", "QVTEN", "QCTEN", "UTEN", "VTEN", "XKC", "PTEN", "PHI")}
     out.update({n: e.get_budget(n) for n in BUDGET_TERMS})
     e.close()
     return g, (dt0, xbc), out
@@ -183,3 +194,63 @@ def test_nh_budget_terms_match_the_restatement():
         assert (np.abs(out[dif][:, ring]).max(axis=0) > 0.0).all() and (np.abs(out[dif][:, corners]).max(axis=0) > 0.0).all()
         check_term(f"N 37x29 {dif}", out[dif], dr.diffu_x(rc, f, co["xkc"]), big, N_BUDGET, dom, dom)
         check_term(f"N 37x29 {bdy}", out[bdy], dr.nudge(rc, g[a2], g[b0], g[bt], xt, kind), big, N_BUDGET, band, dom)
+
+
+# ------------------------------------------------------------------------------ ipgf = 1
+def tiles_of(rc, nproc):
+    """[(ext, bdy)] of the nproc = (tiles in j, tiles in i) decomposition, from the host-side geometry."""
+    return [tile_extent(rc.jx, rc.iy, nproc[0], nproc[1], t) for t in range(nproc[0] * nproc[1])]
+
+
+@pytest.mark.parametrize("grid,variant,nproc", [(g, v, ONE) for g in GRIDS for v in PGF_VARIANTS] +
+                         [("37x29", v, (2, 2)) for v in PGF_VARIANTS], ids=_cid)
+def test_ipgf1_phi_and_winds(grid, variant, nproc):
+    rc, g, times, out = engine_run(grid, variant, nproc)
+    check_ipgf1(f"{grid} {_cid(nproc)} {variant_id(variant)}", rc, g, times, out)
+
+
+# ------------------------------------------------------------------------------ idiffu = 3
+@pytest.mark.parametrize("grid,nproc", [(g, ONE) for g in GRIDS] + [("37x29", (2, 2))], ids=_cid)
+def test_idiffu3_xkc_and_terms(grid, nproc):
+    rc, g1, times, full = engine_run(grid, D6, nproc)
+    _, g0, _, off = engine_run(grid, D6, nproc, **D6_OFF)
+    same_state(g1, g0)
+    tiles = tiles_of(rc, nproc)
+    r = dr.hydro_tend(rc, g1, *times, tiles=tiles)
+    tag = f"{grid} {_cid(nproc)} idiffu=3"
+    m = dr.domain_mask(rc)
+    assert np.array_equal(full["XKC"][:, m], r["coeff"]["xkc"][:, m]) and (r["coeff"]["xkc"][:, m] > 0.0).all()
+    check_diffu6_edges(tag, rc, g1, r, tiles)
+    for dot in (False, True):
+        cols = dr.tile_columns(rc, dot, tiles)
+        jmax = rc.jx if dot else rc.jx - 1
+        assert len({c[0] for c in cols}) == nproc[0] and len(cols) == nproc[0] * nproc[1]
+        # every tile column but the last has its three neighbours to the east: the j-clamp does not act
+        assert sorted(c[0] + 3 <= jmax for c in cols) == [False] * nproc[1] + [True] * ((nproc[0] - 1) * nproc[1])
+    dom, col = dr.domain_mask(rc), column_mask(rc, False, tiles)
+    for key, total, dif in (("T", "TTEN", "T_DIF"), ("Q", "QVTEN", "Q_DIF")):
+        check_term(f"{tag} {dif}", full[dif], r[key.lower() + "_dif"], np.fmax(r[key].big, np.abs(r[total])), N_BUDGET,
+                   col, dom)
+    for name, key, dot in TOTALS[2:]:
+        check_term(f"{tag} {name} diffusion", full[name] - off[name], r[key.lower() + "_dif"],
+                   np.fmax(r[key].big, np.abs(r[name])), N_ADD[(key, "dif")], column_mask(rc, dot, tiles),
+                   dr.domain_mask(rc, dot))
+    for name, _, dot in TOTALS:
+        md = dr.domain_mask(rc, dot)
+        np.testing.assert_allclose(full[name][:, md], r[name][:, md], rtol=1e-10,
+                                   atol=1e-11 * np.abs(r[name][:, md]).max(), err_msg=name)
+
+
+def test_nh_idiffu3_budget_terms_match_the_restatement():
+    """T_DIF / Q_DIF of the non-hydrostatic core at idiffu = 3 on N1 cut to 37 x 29: the constant
+    coefficient diff_6th_coef * p*b and the one column jci2, as test_nh_budget_terms_match_the_restatement
+    holds the idiffu = 1 form."""
+    rc, data, st = case("N", idiffu=3)
+    st = prepared(rc, st, patch=False)
+    g, _, out = _tend(rc, data, st, ONE, NH_INPUTS + ("MSFD",))
+    co = dr.nh_coeff(rc, g)
+    dom, col = dr.domain_mask(rc), column_mask(rc, False)
+    _, _, tb, qvb, _, _ = dr.b_slices(g)
+    for key, dif, f in (("T", "T_DIF", tb), ("Q", "Q_DIF", qvb)):
+        big = sum(np.abs(out[n]) for n in BUDGET_TERMS if n.startswith(key + "_"))
+        check_term(f"N 37x29 idiffu=3 {dif}", out[dif], dr.diffu_x(rc, f, co["xkc"], g["MSFD"][0]), big, N_BUDGET, col, dom)
