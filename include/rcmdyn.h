@@ -571,6 +571,72 @@ int rcmdyn_get_tracer_budget(rcmdyn_t* h, int32_t term, int32_t itr, double* dst
                              int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
 int rcmdyn_reset_tracer_budget(rcmdyn_t* h);
 
+/* Device output stream: the dyn-owned fields of mod_output's ATM stream and the dyn-owned parts of
+ * SRF / SHF (Main/mod_output.F90:224-660, 923-1154), formed on the device from the state as it
+ * stands at the call, written compact over each tile's own jci1:jci2 x ici1:ici2 in fp64 or fp32
+ * (the stream files store 4-byte reals) and handed to the host without stalling later steps.  Off
+ * by default and outside the captured step: with the stage off no launch of it is issued.  Every
+ * expression is the reference's, in its order; the fp32 form is one (float) rounding of the
+ * finished fp64 value.  The lines cited define each field (idynamic 1 and 2):
+ *   OUT_PS      :226   sfs%psa (cb)
+ *   OUT_PS_PA   :933-941  surface pressure in Pa (NH: atm0%ps + ptop * 1000 + pp(kz) / psa)
+ *   OUT_T       :234
+ *   OUT_U, OUT_V  :255-258, the four-point dot -> cross mean over psa, with the ghost line of
+ *               atm1%u, atm1%v the reference exchanges at :250-251
+ *   OUT_W       :277   NH only
+ *   OUT_PP      :291   NH only
+ *   OUT_QV      :301, :305  specific humidity
+ *   OUT_QC, OUT_QI, OUT_QR, OUT_QS  :314, :336, :325, :347; the last three with nqx = 5 only
+ *   OUT_TKE     :576   levels 1..kz, ibltyp = 2 only
+ *   OUT_PH      :388 (the full-level sigma(k), as the text has it), NH :409-414
+ *   OUT_ZH      :396-403, hydrostatic only (the NH value is the constant atm0%z the host holds)
+ *   OUT_UA100, OUT_VA100  :1057-1150 (2-D): the hydrostatic branch rebuilds its heights from the
+ *               current state, the NH branch reads ATM0_Z; a column with no half level above
+ *               100 m gets zero (the text's loop leaves the stream buffer's previous record)
+ *   OUT_RH      :366-368 (percent)
+ *   OUT_PF      :378
+ *   OUT_ZF      :452   hydrostatic only
+ *   OUT_OMEGA   :268   RCMDYN_OMEGA * 10 (hPa/s), hydrostatic only: the NH step does not fill that
+ *               export (the host has the NH omega in ATMS_WPX3D)
+ * Leftover fields.  When output runs after a step, atm1%pr (Main/mod_tendency.F90:1038, 1057),
+ * atms%zq, atms%pf3d (mkslice) and omega still hold what the last tend left at its start, so
+ * OUT_RH, OUT_PF, OUT_ZF and levels 1..kz-1 of OUT_ZH mix new and old state (:400 adds the old
+ * zq(k+1) to a layer built from the new t); the engine reproduces that mix.  They are served from
+ * the mkslice export of the last rcmdyn_tend_pre_physics issued with the stage on (which then also
+ * keeps atm1%pr) and are refused with the slice fields' 'no slice fields yet' message until then: in
+ * a job stepping with rcmdyn_step only, and at lcount = 0, the host still holds its own values.
+ * OUT_OMEGA is refused while rcmdyn_set_diagnostics is off.  A field the configuration lacks is
+ * refused by name.
+ * Left on the host: uvrotate (wind_antirotate has one branch per projection; the host applies it
+ * to the fetched u, v), CAPE / CIN (getcape), every physics-owned variable of the streams, the
+ * idiag terms (rcmdyn_get_budget serves them) and NetCDF itself. */
+enum rcmdyn_output_field {
+  RCMDYN_OUT_PS = 0, RCMDYN_OUT_PS_PA, RCMDYN_OUT_T, RCMDYN_OUT_U, RCMDYN_OUT_V, RCMDYN_OUT_W, RCMDYN_OUT_PP,
+  RCMDYN_OUT_QV, RCMDYN_OUT_QC, RCMDYN_OUT_QI, RCMDYN_OUT_QR, RCMDYN_OUT_QS, RCMDYN_OUT_TKE, RCMDYN_OUT_PH,
+  RCMDYN_OUT_ZH, RCMDYN_OUT_UA100, RCMDYN_OUT_VA100, RCMDYN_OUT_RH, RCMDYN_OUT_PF, RCMDYN_OUT_ZF,
+  RCMDYN_OUT_OMEGA,
+  RCMDYN_NOUT
+};
+/* rcmdyn_set_output: prec is 4 (float) or 8 (double), refused otherwise with the switch as it was.
+ * The first switch-on allocates the compact device buffers and the pinned host buffers.  The step
+ * graphs are not touched.  A switch or a changed prec forgets the last snapshot.
+ * rcmdyn_output_atm: mask has bit (1 << field) set for every requested field.  Settles a lazy tend,
+ * exchanges the 1-deep ghost line of atm1%u, atm1%v where tiles or a period need it (collective
+ * over the ranks of a job, like rcmdyn_reductions: every rank calls it with the same mask), forms
+ * the fields in one launch per tile on the compute stream and starts the device -> pinned copy on
+ * a copy stream behind it, then returns without waiting.  A second call first waits for the
+ * previous copy.  Refused, with nothing launched, while the stage is off, for an empty mask or an
+ * unknown bit, and for a field that is refused (above).
+ * rcmdyn_get_output: one field of the last rcmdyn_output_atm into dst (floats or doubles by prec),
+ * layout and global bounds as in rcmdyn_get (2-D fields with k1 = k2 = 1); only the interior
+ * cross points of the owned tiles that lie in the box are written.  Waits for that copy only,
+ * never for steps issued after rcmdyn_output_atm; a failure of a step issued before it is
+ * reported as rcmdyn_get does.  Refused for a field that was not in the last mask. */
+int rcmdyn_set_output(rcmdyn_t* h, int32_t on, int32_t prec);
+int rcmdyn_output_atm(rcmdyn_t* h, uint32_t mask);
+int rcmdyn_get_output(rcmdyn_t* h, int32_t field, void* dst,
+                      int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

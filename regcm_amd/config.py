@@ -115,6 +115,12 @@ CUMTRAN_FIELDS = ["DOTRAN", "KTOP", "CLDFRA"]
 CUMTRAN_FIELD = {n: i for i, n in enumerate(CUMTRAN_FIELDS)}
 TRACER_DIAG_TERMS = ["ADVH", "ADVV", "BDY", "DIFH", "CONV"]
 TRACER_DIAG_TERM = {n: i for i, n in enumerate(TRACER_DIAG_TERMS)}
+# enum rcmdyn_output_field: the output stream's fields (mod_output's ATM / SRF / SHF variables the
+# dyn core owns); the 2-D ones among them
+OUTPUT_FIELDS = ["PS", "PS_PA", "T", "U", "V", "W", "PP", "QV", "QC", "QI", "QR", "QS", "TKE", "PH", "ZH",
+                 "UA100", "VA100", "RH", "PF", "ZF", "OMEGA"]
+OUTPUT_FIELD = {n: i for i, n in enumerate(OUTPUT_FIELDS)}
+OUTPUT_2D = {"PS", "PS_PA", "UA100", "VA100"}
 TWO_D = {"PSA", "PSB", "MSFX", "MSFD", "CORIOL", "HT", "XPSB_B0", "XPSB_BT", "PSC",
          "PTEN", "PSDOTA", "ATM0_PS", "DPSDXM", "DPSDYM", "EF", "DDX", "DDY", "DMDX", "DMDY",
          "EX", "CRX", "CRY", "ATMS_PS2D", "ATMS_RHOX2D", "XPSB_B1", "ATM0_PSDOT", "KPBL"}

@@ -34,6 +34,7 @@
 #include "tke.hpp"
 #include "fieldtab.hpp"
 #include "massck.hpp"
+#include "output.hpp"
 #include "optset.hpp"
 #include "pointops.hpp"   // the policies OptDefault / OptGeneric the tendency kernels are instantiated on
 
@@ -946,6 +947,15 @@ struct rcmdyn_engine {
 
   void destroy() {
     if (stream) (void)hipStreamSynchronize(stream);
+    if (ostream) {
+      (void)hipStreamSynchronize(ostream);
+      (void)hipEventDestroy(ev_out);
+      (void)hipEventDestroy(ev_copied);
+      (void)hipStreamDestroy(ostream);
+      if (oflags) (void)hipHostFree(oflags);
+      for (auto& t : tiles)
+        if (t.ohost) (void)hipHostFree(t.ohost);
+    }
     invalidate_graphs();
     for (auto& e : fev)
       if (e) (void)hipEventDestroy(e);
@@ -1389,9 +1399,14 @@ struct rcmdyn_engine {
       a.ep2 = AMW / AMD;                                  // Share/mod_constants.F90:306
       a.rhmin = cfg.rhmin; a.rhmax = cfg.rhmax;
       for (int n = 0; n < hc.nsp; n++) { a.a2qx[n] = t.a2qx[n][c]; a.qxb3d[n] = t.atmsx[n]; }
+      if (outon) {                                        // atm1%pr of this moment for OUT_RH
+        a.opr = t.opr;
+        if (cfg.idynamic == 2) a.a1pp = nhf[&t - tiles.data()].a1pp;
+      }
       KLAUNCH(k_slice, grid3(g.jde2 - g.jde1 + 1, g.ide2 - g.ide1 + 1, 1), BLK, 0, stream, g, dc, a);
     });
     tracer_slice();
+    if (outon) opr_filled = true;
   }
 
   void get(int f, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
@@ -1413,6 +1428,160 @@ struct rcmdyn_engine {
       if (!d) throw std::runtime_error("rcmdyn_get: unknown field");
       const Geom& g = t.g;
       gather_box(t, d, field_levels(f), dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
+    }
+  }
+
+  // ------------------------------------------------------------------ output stream
+  // The fields of mod_output's ATM / SRF / SHF streams that the dyn core owns (output.hip), off by
+  // default and outside the captured step.  rcmdyn_output_atm forms the requested fields on the
+  // compute stream into each tile's compact buffer (jci1:jci2 x ici1:ici2, floats or doubles) and
+  // copies it to its pinned twin on a stream of its own behind an event, with the step's sticky
+  // error flags of that moment; rcmdyn_get_output waits for that copy alone.  The copy has its
+  // own stream because a decomposed step issues work on the engine's second stream, which would
+  // otherwise queue behind the copy.
+  bool outon = false;
+  int out_prec = 8;
+  uint32_t out_mask = 0;          // the fields of the last rcmdyn_output_atm (0: no snapshot)
+  long long out_lcount = 0;       // the clock of that snapshot
+  bool opr_filled = false;        // a slice ran with the stage on: Tile::opr holds atm1%pr
+  hipStream_t ostream = nullptr;
+  hipEvent_t ev_out = nullptr, ev_copied = nullptr;
+  StepState* oflags = nullptr;    // pinned: the device clock and flags at the snapshot
+  static constexpr const char* OUT_NAME[RCMDYN_NOUT] = {
+      "OUT_PS", "OUT_PS_PA", "OUT_T", "OUT_U", "OUT_V", "OUT_W", "OUT_PP", "OUT_QV", "OUT_QC", "OUT_QI", "OUT_QR",
+      "OUT_QS", "OUT_TKE", "OUT_PH", "OUT_ZH", "OUT_UA100", "OUT_VA100", "OUT_RH", "OUT_PF", "OUT_ZF", "OUT_OMEGA"};
+  int out_levels(int f) const { return out_is_2d(f) ? 1 : cfg.kz; }
+  static size_t out_cells(const Geom& g) { return (size_t)(g.jci2 - g.jci1 + 1) * (g.ici2 - g.ici1 + 1); }
+  // why this engine refuses an output field now, null when it serves it
+  const char* out_refusal(int f) const {
+    const bool nh = cfg.idynamic == 2;
+    switch (f) {
+      case RCMDYN_OUT_W: case RCMDYN_OUT_PP: return lacks(fieldtab::NH);
+      case RCMDYN_OUT_QI: case RCMDYN_OUT_QR: case RCMDYN_OUT_QS: return lacks(fieldtab::NQX5);
+      case RCMDYN_OUT_TKE: return lacks(fieldtab::UW);
+      case RCMDYN_OUT_ZH:
+        if (nh) return "the non-hydrostatic height of the half levels is the constant atm0%z (ATM0_Z)";
+        break;
+      case RCMDYN_OUT_ZF:
+        if (nh) return lacks(fieldtab::HYD_Z);
+        break;
+      case RCMDYN_OUT_OMEGA:
+        // the NH step never fills the RCMDYN_OMEGA export (its omega is ATMS_WPX3D of the slice)
+        if (nh) return "the diagnostics export holds no omega on the non-hydrostatic core (ATMS_WPX3D has it)";
+        return diag ? nullptr : WAITS_FOR[fieldtab::DIAG];
+      default: break;
+    }
+    // the leftovers of the last mkslice: zq and pf3d of its export, atm1%pr of one run with the stage on
+    if (f == RCMDYN_OUT_ZH || f == RCMDYN_OUT_ZF || f == RCMDYN_OUT_PF) return have(fieldtab::SLICE) ? nullptr : WAITS_FOR[fieldtab::SLICE];
+    if (f == RCMDYN_OUT_RH) return have(fieldtab::SLICE) && opr_filled ? nullptr : WAITS_FOR[fieldtab::SLICE];
+    return nullptr;
+  }
+  void wait_output_copy() {
+    if (ev_copied) HIPCHK(hipEventSynchronize(ev_copied));
+  }
+  void set_output(int on, int prec) {
+    if (on && prec != 4 && prec != 8)
+      throw std::runtime_error("rcmdyn_set_output: prec = " + std::to_string(prec) + " is neither 4 (float) nor 8 (double)");
+    wait_output_copy();
+    if (on && !ostream) {
+      HIPCHK(hipStreamCreateWithFlags(&ostream, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&ev_copied, hipEventDisableTiming));
+      HIPCHK(hipHostMalloc((void**)&oflags, sizeof(StepState), hipHostMallocDefault));
+      std::memset(oflags, 0, sizeof(StepState));
+      // room for every field in doubles: 4 planes and RCMDYN_NOUT - 4 fields of kz levels
+      for (auto& t : tiles) {
+        const size_t n = out_cells(t.g) * (4 + (size_t)(RCMDYN_NOUT - 4) * cfg.kz);
+        t.odev = dalloc(t, n);
+        HIPCHK(hipHostMalloc(&t.ohost, n * sizeof(double), hipHostMallocDefault));
+        std::memset(t.ohost, 0, n * sizeof(double));
+        t.opr = dalloc(t, t.g.plane * (size_t)cfg.kz);
+      }
+    }
+    const bool b = on != 0;
+    if (b != outon || (b && prec != out_prec)) out_mask = 0;
+    if (!b) opr_filled = false;          // k_slice stops writing atm1%pr: what is held goes stale
+    outon = b;
+    if (b) out_prec = prec;
+  }
+  void output_atm(uint32_t mask) {
+    if (!outon) throw std::runtime_error("rcmdyn_output_atm: the output stage is off (rcmdyn_set_output)");
+    if (mask == 0) throw std::runtime_error("rcmdyn_output_atm: mask = 0 names no field");
+    if (mask >> RCMDYN_NOUT)
+      throw std::runtime_error("rcmdyn_output_atm: mask = " + std::to_string(mask) + " has a bit beyond the last field (" +
+                               std::to_string(RCMDYN_NOUT - 1) + ")");
+    for (int f = 0; f < RCMDYN_NOUT; f++)
+      if (((mask >> f) & 1u))
+        if (const char* why = out_refusal(f)) throw std::runtime_error(std::string("rcmdyn_output_atm: ") + OUT_NAME[f] + ": " + why);
+    settle();                       // a lazy tend replays its graph first
+    wait_output_copy();             // the previous snapshot leaves the buffers first
+    constexpr uint32_t WINDS = 1u << RCMDYN_OUT_U | 1u << RCMDYN_OUT_V | 1u << RCMDYN_OUT_UA100 | 1u << RCMDYN_OUT_VA100;
+    // the ghost line of Main/mod_output.F90:250-251: the mean reads atm1%u, atm1%v at j + 1, i + 1
+    if (mask & WINDS) xch({{FK::A1U, cfg.kz}, {FK::A1V, cfg.kz}}, 1, 0);
+    out_mask = 0;
+    const size_t esz = (size_t)out_prec;
+    each([&](Tile& t) {
+      const Geom& g = t.g;
+      if (g.jci2 < g.jci1 || g.ici2 < g.ici1) return;
+      OutArgs a{};
+      long off = 0;
+      for (int f = 0; f < RCMDYN_NOUT; f++) {
+        t.ooff[f] = a.off[f] = off;
+        if ((mask >> f) & 1u) off += (long)(out_cells(g) * out_levels(f));
+      }
+      const int c = t.cur, q = thp(t);
+      a.psa = t.psa_[c]; a.a1t = t.a1t[q]; a.a1u = t.a1u[c]; a.a1v = t.a1v[c]; a.a1qv = t.a1qv[q]; a.a1qc = t.a1qc[q];
+      a.a1tke = t.a1tke;
+      for (int n = 0; n < hc.nsp; n++) a.a1qx[n] = t.a1qx[n][c];
+      if (cfg.idynamic == 2) {
+        const NHFields& h = nhf[&t - tiles.data()];
+        a.a1pp = h.a1pp; a.a1w = h.a1w; a.ps0 = h.ps0; a.pf0 = h.pf0; a.z0 = h.z0;
+      }
+      a.pr = t.opr; a.pf3d = t.atms[RCMDYN_ATMS_PF3D - RCMDYN_ATMS_UBX3D]; a.zq = t.atms[RCMDYN_ATMS_ZQ - RCMDYN_ATMS_UBX3D];
+      a.omega = t.omega;
+      a.out = t.odev; a.mask = mask;
+      a.ep2 = AMW / AMD; a.rhmin = cfg.rhmin; a.rhmax = cfg.rhmax;
+      const dim3 grid = grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, cfg.kz);
+      if (out_prec == 4) KLAUNCH(k_output<float>, grid, BLK, 0, stream, g, dc, a);
+      else KLAUNCH(k_output<double>, grid, BLK, 0, stream, g, dc, a);
+    });
+    HIPCHK(hipEventRecord(ev_out, stream));
+    HIPCHK(hipStreamWaitEvent(ostream, ev_out, 0));
+    for (auto& t : tiles) {
+      size_t n = 0;
+      for (int f = 0; f < RCMDYN_NOUT; f++)
+        if ((mask >> f) & 1u) n += out_cells(t.g) * out_levels(f);
+      if (n) HIPCHK(hipMemcpyAsync(t.ohost, t.odev, n * esz, hipMemcpyDeviceToHost, ostream));
+    }
+    HIPCHK(hipMemcpyAsync(oflags, ds, sizeof(StepState), hipMemcpyDeviceToHost, ostream));
+    HIPCHK(hipEventRecord(ev_copied, ostream));
+    out_mask = mask;
+    out_lcount = hs.lcount;
+  }
+  void get_output(int f, void* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+    if (!outon) throw std::runtime_error("rcmdyn_get_output: the output stage is off (rcmdyn_set_output)");
+    if (f < 0 || f >= RCMDYN_NOUT) throw std::runtime_error("rcmdyn_get_output: unknown field " + std::to_string(f));
+    if (!((out_mask >> f) & 1u))
+      throw std::runtime_error(std::string("rcmdyn_get_output: ") + OUT_NAME[f] + " was not in the mask of the last rcmdyn_output_atm");
+    wait_output_copy();
+    // the steps issued before the snapshot: their sticky flags travelled with it
+    if (oflags->nanflag || oflags->slflag) {
+      out_mask = 0;
+      fail(oflags->slflag, out_lcount, "by step ");
+    }
+    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
+    const int nk = out_levels(f);
+    for (auto& t : tiles) {
+      const Geom& g = t.g;
+      const long ncj = g.jci2 - g.jci1 + 1, nci = g.ici2 - g.ici1 + 1;
+      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
+        for (int i = std::max(i1, g.ici1); i <= std::min(i2, g.ici2); i++)
+          for (int j = std::max(j1, g.jci1); j <= std::min(j2, g.jci2); j++) {
+            const size_t d = ((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1);
+            const size_t s = (size_t)t.ooff[f] + ((size_t)(k - 1) * nci + (i - g.ici1)) * ncj + (j - g.jci1);
+            if (out_prec == 4) ((float*)dst)[d] = ((const float*)t.ohost)[s];
+            else ((double*)dst)[d] = ((const double*)t.ohost)[s];
+          }
     }
   }
 
@@ -3767,6 +3936,15 @@ int rcmdyn_get_tracer_budget(rcmdyn_t* h, int32_t term, int32_t itr, double* dst
 
 int rcmdyn_reset_tracer_budget(rcmdyn_t* h) {
   return guard(h, [&] { h->reset_tracer_budget(); });
+}
+
+int rcmdyn_set_output(rcmdyn_t* h, int32_t on, int32_t prec) {
+  return guard(h, [&] { h->set_output(on, prec); });
+}
+int rcmdyn_output_atm(rcmdyn_t* h, uint32_t mask) { return guard(h, [&] { h->output_atm(mask); }); }
+int rcmdyn_get_output(rcmdyn_t* h, int32_t field, void* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
+                      int32_t k2) {
+  return guard(h, [&] { h->get_output(field, dst, j1, j2, i1, i2, k1, k2); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

@@ -251,6 +251,13 @@ struct Tile {
   double *phy[7] = {};
   double *atms[22] = {};
   double *phyx[NQXH] = {}, *atmsx[NQXH] = {};   // nqx = 5: qxphy and the qxb3d export of qi, qr, qs
+  // output stream (rcmdyn_set_output; output.hip): atm1%pr as the last mkslice's tend left it
+  // (k_slice's optional output), the compact device buffer of the fields and its pinned host twin
+  // (odev is among allocs, ohost is freed by destroy), and where each field of the last
+  // rcmdyn_output_atm starts in them (elements)
+  double* opr = nullptr;
+  void *odev = nullptr, *ohost = nullptr;
+  long ooff[RCMDYN_NOUT] = {};
   // device bdyin: the raw record put by the host (u, v, t, qv, ps, pp, w) and the coupled
   // boundary data at the interval end (b1, same order), allocated on the first put of a
   // record field; NH: atm0%psdot (Pa) for the coupling of u, v

@@ -66,6 +66,10 @@ __global__ __launch_bounds__(256) void k_slice(Geom g, const Consts* __restrict_
     }
     // tb3d, qxb3d (:185-189) on jx1:jx2 (cross points and ghosts), tv3d (:199-202)
     if (!ce) continue;
+    // atm1%pr for the output stream (Main/mod_tendency.F90:1038; NH :1049, 1057 with rpsa of :839)
+    if (a.opr)
+      F3(a.opr, j, i, k) = nh ? F3(a.pr0, j, i, k) + F3(a.a1pp, j, i, k) * (d_one / F2(a.psa, j, i))
+                              : (c->hsigma[k] * F2(a.psa, j, i) + ptop) * d_1000;
     const double tb = F3(a.a2t, j, i, k) * rpsb;
     const double qvb = dmax(F3(a.a2qv, j, i, k) * rpsb, MINQQ);
     const double qcb = dmax(F3(a.a2qc, j, i, k) * rpsb, d_zero);

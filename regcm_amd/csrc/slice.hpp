@@ -16,6 +16,10 @@ struct SliceArgs {
   // nqx = 5: qxb3d of qi, qr, qs (Main/mod_slice.F90:193-195), from atm2 (null for nqx = 2)
   const double* a2qx[NQXH];
   double* qxb3d[NQXH];
+  // output stream (null unless rcmdyn_set_output is on): atm1%pr of this tend's start
+  // (Main/mod_tendency.F90:1038, 1057), from a1pp = atm1%pp on the NH core
+  const double* a1pp;
+  double* opr;
 };
 
 __global__ void k_slice(Geom g, const Consts* __restrict__ c, SliceArgs a);

@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from .config import CUMTRAN_FIELD, FIELD, TRACER_DIAG_TERM, TRACER_FIELD, RcmdynConfig, build_config, field_levels
+from .config import CUMTRAN_FIELD, FIELD, OUTPUT_2D, OUTPUT_FIELD, OUTPUT_FIELDS, TRACER_DIAG_TERM, TRACER_FIELD, RcmdynConfig, build_config, field_levels
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RCMDYN_LIB selects an instrumented build (tools/phases.py); default: the in-tree engine
@@ -37,6 +37,7 @@ EXPORTED = [
     "rcmdyn_set_tracers", "rcmdyn_put_tracer", "rcmdyn_get_tracer", "rcmdyn_put_tracer_nudge",
     "rcmdyn_set_cumtran", "rcmdyn_put_cumtran", "rcmdyn_get_cumtran",
     "rcmdyn_set_tracer_budget", "rcmdyn_get_tracer_budget", "rcmdyn_reset_tracer_budget",
+    "rcmdyn_set_output", "rcmdyn_output_atm", "rcmdyn_get_output",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
@@ -109,6 +110,9 @@ def lib():
     L.rcmdyn_set_tracer_budget.argtypes = [P, i32, ctypes.c_double, ctypes.c_double]
     L.rcmdyn_get_tracer_budget.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
     L.rcmdyn_reset_tracer_budget.argtypes = [P]
+    L.rcmdyn_set_output.argtypes = [P, i32, i32]
+    L.rcmdyn_output_atm.argtypes = [P, ctypes.c_uint32]
+    L.rcmdyn_get_output.argtypes = [P, i32, ctypes.c_void_p, i32, i32, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -421,6 +425,37 @@ class DynCore:
     def reset_tracer_budget(self):
         """Zeroes every accumulator (the host does it after writing them at alarm_out_che)."""
         self._check(lib().rcmdyn_reset_tracer_budget(self.h))
+
+    def set_output(self, on: bool = True, prec: int = 8):
+        """The output stream (mod_output's dyn-owned ATM / SRF / SHF fields, formed on the device):
+        prec = 8 hands doubles to the host, prec = 4 the stream files' 4-byte reals."""
+        self._check(lib().rcmdyn_set_output(self.h, 1 if on else 0, prec))
+        if on:
+            self._out_prec = prec
+
+    def output_atm(self, fields):
+        """Snapshot of the named fields (OUTPUT_FIELDS names or numbers; or a ready bit mask as an
+        int) from the state as it stands: forms them on the device and starts their copy to the
+        host; returns without waiting.  Steps issued afterwards do not change what get_output
+        returns.  Collective over the ranks of a job."""
+        if isinstance(fields, int):
+            mask = fields
+        else:
+            mask = 0
+            for f in fields:
+                mask |= 1 << (OUTPUT_FIELD[f] if isinstance(f, str) else int(f))
+        self._check(lib().rcmdyn_output_atm(self.h, mask))
+
+    def get_output(self, name) -> np.ndarray:
+        """One field of the last output_atm as a (kz, iy, jx) array, (1, iy, jx) for the 2-D fields,
+        float32 or float64 by set_output's prec: zero outside the interior cross points.  Waits for
+        that snapshot's copy only."""
+        f = OUTPUT_FIELD[name] if isinstance(name, str) else int(name)
+        nk = 1 if 0 <= f < len(OUTPUT_FIELDS) and OUTPUT_FIELDS[f] in OUTPUT_2D else self.rc.kz
+        out = np.zeros((nk, self.rc.iy, self.rc.jx), dtype=np.float32 if getattr(self, "_out_prec", 8) == 4 else np.float64)
+        self._check(lib().rcmdyn_get_output(self.h, f, out.ctypes.data_as(ctypes.c_void_p),
+                                            1, self.rc.jx, 1, self.rc.iy, 1, nk))
+        return out
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

@@ -72,6 +72,13 @@ module mod_gpu_dyn
   integer(c_int32_t), parameter, public :: &
     trdiag_advh = 0, trdiag_advv = 1, trdiag_bdy = 2, trdiag_difh = 3, trdiag_conv = 4, rcmdyn_ntrdiag = 5
 
+  ! fields of the output stream (enum rcmdyn_output_field): the dyn-owned variables of mod_output's
+  ! ATM, SRF and SHF streams; rcmdyn_output_atm takes ibset(0, out_x) of every requested one
+  integer(c_int32_t), parameter, public :: &
+    out_ps = 0, out_ps_pa = 1, out_t = 2, out_u = 3, out_v = 4, out_w = 5, out_pp = 6, out_qv = 7, &
+    out_qc = 8, out_qi = 9, out_qr = 10, out_qs = 11, out_tke = 12, out_ph = 13, out_zh = 14, &
+    out_ua100 = 15, out_va100 = 16, out_rh = 17, out_pf = 18, out_zf = 19, out_omega = 20, rcmdyn_nout = 21
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -386,6 +393,29 @@ module mod_gpu_dyn
       import :: c_int, c_ptr
       type(c_ptr), value :: h
     end function
+    ! the output stream on (1) or off (0, the default); prec = 4: the host gets reals of 4 bytes,
+    ! prec = 8: of 8
+    integer(c_int) function rcmdyn_set_output(h, on, prec) bind(c, name='rcmdyn_set_output')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on, prec
+    end function
+    ! forms the fields of mask (bit out_x per field) from the state as it stands and starts their
+    ! copy to the host; does not wait
+    integer(c_int) function rcmdyn_output_atm(h, mask) bind(c, name='rcmdyn_output_atm')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: mask
+    end function
+    ! one field (out_ps .. out_omega) of the last rcmdyn_output_atm into dst(j1:j2,i1:i2,k1:k2), an
+    ! array of real(c_float) or real(c_double) by prec, passed as c_loc(dst)
+    integer(c_int) function rcmdyn_get_output(h, field, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_output')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: field, j1, j2, i1, i2, k1, k2
+      type(c_ptr), value :: dst
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -410,6 +440,7 @@ module mod_gpu_dyn
   public :: rcmdyn_set_tracers, rcmdyn_put_tracer, rcmdyn_get_tracer, rcmdyn_put_tracer_nudge
   public :: rcmdyn_set_cumtran, rcmdyn_put_cumtran, rcmdyn_get_cumtran
   public :: rcmdyn_set_tracer_budget, rcmdyn_get_tracer_budget, rcmdyn_reset_tracer_budget
+  public :: rcmdyn_set_output, rcmdyn_output_atm, rcmdyn_get_output
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains

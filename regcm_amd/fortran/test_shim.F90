@@ -3,7 +3,7 @@
 ! tests/test_fortran_shim.py).  It runs a script of C-ABI calls that the test writes, the
 ! calls a RegCM host makes around the dyn step (Main/mod_regcm_interface.F90:150-228:
 ! the state put, the init bdyval, nsteps x (tend + bdyval) or the physics split of tend,
-! bdyin after read_icbc, the 3-hourly sums, restarts, the mass check's log), and writes every
+! bdyin after read_icbc, the 3-hourly sums, restarts, the mass check's log, the output stream), and writes every
 ! result it reads back to a stream file, so the test can compare it with the Python host running
 ! the same script.
 !
@@ -20,6 +20,8 @@ program test_shim
   integer(c_int32_t) :: cpus(2), ext(8), bdy(4)
   integer(c_int) :: ierr
   real(c_double), pointer, contiguous :: a3(:,:,:), a2(:,:)
+  real(c_float), pointer, contiguous :: o4(:,:,:)
+  real(c_double), pointer, contiguous :: o8(:,:,:)
   real(c_double) :: d3(3), d4(4), ms
   character(len=512) :: fin, fout
   character(kind=c_char) :: info(1024)
@@ -192,6 +194,30 @@ program test_shim
       ierr = rcmdyn_get_massck(h, avg, n, k1, cnt)
       if ( ierr == 0 ) write(11) k1, cnt, avg(1:6*k1)
       deallocate(avg)
+    case ( 28 )
+      ! the output stream on / off, handing out reals of m bytes
+      read(10) n, m
+      ierr = rcmdyn_set_output(h, n, m)
+    case ( 29 )
+      ! a snapshot of the fields of the mask
+      read(10) n
+      ierr = rcmdyn_output_atm(h, n)
+    case ( 30 )
+      ! one output field into o4 / o8(j1:j2,i1:i2,k1:k2), by the size m of its reals
+      read(10) fid, m, j1, j2, i1, i2, k1, k2
+      if ( m == 4 ) then
+        allocate(o4(j1:j2,i1:i2,k1:k2))
+        o4 = 0.0_c_float
+        ierr = rcmdyn_get_output(h, fid, c_loc(o4), j1, j2, i1, i2, k1, k2)
+        if ( ierr == 0 ) write(11) o4
+        deallocate(o4)
+      else
+        allocate(o8(j1:j2,i1:i2,k1:k2))
+        o8 = 0.0_c_double
+        ierr = rcmdyn_get_output(h, fid, c_loc(o8), j1, j2, i1, i2, k1, k2)
+        if ( ierr == 0 ) write(11) o8
+        deallocate(o8)
+      end if
     case default
       write(0,*) 'test_shim: unknown op ', op
       error stop 3

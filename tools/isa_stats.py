@@ -9,7 +9,7 @@ import sys
 
 
 def instance(sym):
-    """k_name<args> of a mangled kernel symbol: the namespace's types, bool and int literals and
+    """k_name<args> of a mangled kernel symbol: the namespace's types, float / double, bool and int literals and
     packs, which is what the kernels here are instantiated on; anything else prints as '?'."""
     m = re.search(r'(\d+)(k_[a-z0-9_]+)', sym)
     if not m or int(m.group(1)) != len(m.group(2)):
@@ -35,6 +35,9 @@ def instance(sym):
         elif (a := re.match(r'Li(n?)(\d+)E', rest)):
             args.append(('-' if a.group(1) else '') + a.group(2))
             rest = rest[a.end():]
+        elif rest[0] in 'fd':                    # a builtin type argument: float, double
+            args.append('float' if rest[0] == 'f' else 'double')
+            rest = rest[1:]
         else:
             args.append('?')
             break
