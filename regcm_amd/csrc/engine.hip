@@ -36,6 +36,7 @@
 #include "massck.hpp"
 #include "output.hpp"
 #include "optset.hpp"
+#include "window.hpp"
 #include "pointops.hpp"   // the policies OptDefault / OptGeneric the tendency kernels are instantiated on
 
 using namespace rcm;
@@ -554,23 +555,20 @@ struct rcmdyn_engine {
     c.ipptls = cfg.ipptls; c.nqx = cfg.nqx; c.nsp = cfg.nqx - 2;
   }
 
-  double* dalloc(Tile& t, size_t n) {
-    if (dry) return nullptr;
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, n * sizeof(double)));
-    HIPCHK(hipMemset(p, 0, n * sizeof(double)));
-    t.allocs.push_back(p);
-    return (double*)p;
-  }
+  // n zeroed T of device memory on an owner list: Tile::allocs lives as long as the tile,
+  // Tile::tr_allocs until rcmdyn_set_tracers(0).  Null on a dry engine.
   template <class T>
-  T* talloc(Tile& t, size_t n) {
+  T* zalloc(std::vector<void*>& owner, size_t n) {
     if (dry) return nullptr;
     void* p = nullptr;
     HIPCHK(hipMalloc(&p, n * sizeof(T)));
+    owner.push_back(p);
     HIPCHK(hipMemset(p, 0, n * sizeof(T)));
-    t.allocs.push_back(p);
     return (T*)p;
   }
+  double* dalloc(Tile& t, size_t n) { return zalloc<double>(t.allocs, n); }
+  template <class T> T* talloc(Tile& t, size_t n) { return zalloc<T>(t.allocs, n); }
+  template <class T> T* tr_alloc(Tile& t, size_t n) { return zalloc<T>(t.tr_allocs, n); }
 
   void setup_tile(Tile& t, int index) {
     t.index = index;
@@ -1238,67 +1236,67 @@ struct rcmdyn_engine {
       "no slice fields yet (rcmdyn_tend_pre_physics)", "tendency diagnostics are off (rcmdyn_set_diagnostics)"};
   static_assert(fieldtab::DIAG == 5 && sizeof(WAITS_FOR) / sizeof(WAITS_FOR[0]) == 6, "one text per fieldtab::Lazy");
 
-  // the global index a frame point past either end of a period stands for: a band's columns
-  // (i_band) and the CRM's rows (i_crm) wrap, any other index is itself
-  int wrap_j(int j) const { return !cfg.i_band ? j : (j < 1 ? j + cfg.jx : (j > cfg.jx ? j - cfg.jx : j)); }
-  int wrap_i(int i) const { return !cfg.i_crm ? i : (i < 1 ? i + cfg.iy : (i > cfg.iy ? i - cfg.iy : i)); }
-
-  // The host box src (j fastest, then i, then k) into a tile's buffer d of nk levels: every frame
-  // point of the tile whose global index lies in the box, the ghost ring included, and the frame
-  // points past either end of a period from the wrapped index.  (rcmdyn_put, rcmdyn_put_rh0adj)
-  void scatter_box(const Tile& t, double* d, int nk, const double* src, int j1, int j2, int i1, int i2, int k1,
-                   int k2) {
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
-    const Geom& g = t.g;
-    std::vector<double> h((size_t)nk * g.plane);
-    HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-    for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-      for (int i = g.i0; i <= g.i0 + g.ni - 1; i++) {
-        const int iw = wrap_i(i);
-        if (iw < i1 || iw > i2) continue;
-        for (int j = g.j0; j <= g.j0 + g.nj - 1; j++) {
-          const int jw = wrap_j(j);
-          if (jw < j1 || jw > j2) continue;
-          h[(size_t)(k - 1) * g.plane + g.ix(j, i)] = src[((size_t)(k - k1) * ni + (iw - i1)) * nj + (jw - j1)];
-        }
-      }
-    HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+  // ------------------------------------------------------------------ host windows
+  // Every put and get hands a host box to or from the tiles' frames (window.hpp has the index
+  // arithmetic): a band's columns (i_band) and the CRM's rows (i_crm) wrap.
+  Period period() const { return Period{cfg.jx, cfg.iy, cfg.i_band != 0, cfg.i_crm != 0}; }
+  static Staging frame(const Geom& g, int nk) { return Staging{g.j0, g.i0, g.nj, g.ni, g.pitch, g.plane, nk, 0}; }
+  // a pending lazy tend or its corrections are launched, and the stream is idle
+  void quiesce() {
+    settle();
+    HIPCHK(hipStreamSynchronize(stream));
   }
-  // The other way: a tile's buffer d of nk levels into the host box dst, the tile's points
-  // [ja, jb] x [ia, ib] that lie in the box.  (rcmdyn_get, rcmdyn_get_budget, rcmdyn_get_condtq)
-  void gather_box(const Tile& t, const double* d, int nk, double* dst, int j1, int j2, int i1, int i2, int k1,
-                  int k2, int ja, int jb, int ia, int ib) {
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
-    const Geom& g = t.g;
-    std::vector<double> h((size_t)nk * g.plane);
-    HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-    for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-      for (int i = std::max(i1, ia); i <= std::min(i2, ib); i++)
-        for (int j = std::max(j1, ja); j <= std::min(j2, jb); j++)
-          dst[((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1)] = h[(size_t)(k - 1) * g.plane + g.ix(j, i)];
+  // The host box src into the buffer ptr(tile) of nk levels of every tile: every frame point whose
+  // global index lies in the box, the ghost ring included, and the frame points past either end of
+  // a period from the wrapped index.
+  template <class P>
+  void put_window(const double* src, const Box& b, int nk, P ptr) {
+    quiesce();
+    for (auto& t : tiles) {
+      double* d = ptr(t);
+      std::vector<double> h((size_t)nk * t.g.plane);
+      HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
+      scatter(h.data(), frame(t.g, nk), period(), src, b);
+      HIPCHK(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    }
+  }
+  // The other way, at a host read point (check_now): of every tile the owned dot points, or the
+  // interior cross points alone, that lie in the box.
+  enum class Range { Owned, Interior };
+  template <class P>
+  void get_window(double* dst, const Box& b, int nk, P ptr, Range range = Range::Owned) {
+    quiesce();
+    check_now();
+    for (auto& t : tiles) {
+      const double* d = ptr(t);
+      const Geom& g = t.g;
+      std::vector<double> h((size_t)nk * g.plane);
+      HIPCHK(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
+      if (range == Range::Owned) gather(dst, b, h.data(), frame(g, nk), g.jde1, g.jde2, g.ide1, g.ide2);
+      else gather(dst, b, h.data(), frame(g, nk), g.jci1, g.jci2, g.ici1, g.ici2);
+    }
   }
 
-  void put(int f, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void put(int f, const double* src, const Box& b) {
     settle();
     const fieldtab::Row* r = fieldtab::row(f);
     if (!r || r->acc == fieldtab::RO) throw std::runtime_error("rcmdyn_put: field is read-only or unknown");
     if (const char* m = lacks(r->need)) throw std::runtime_error(std::string("rcmdyn_put: ") + m);
     if (f == RCMDYN_KPBL) {
-      // vadv4d ind = 3 stops on a PBL top above the model (Main/mod_advection.F90:923-925)
-      const size_t n = (size_t)(j2 - j1 + 1) * (i2 - i1 + 1) * std::max(1, k2 - k1 + 1);
+      // vadv4d ind = 3 stops on a PBL top above the model (Main/mod_advection.F90:923-925); a 2-D
+      // field: never fewer than one plane
+      const size_t n = Box{b.j1, b.j2, b.i1, b.i2, b.k1, std::max(b.k1, b.k2)}.cells();
       for (size_t q = 0; q < n; q++) {
         if (src[q] > cfg.kz) throw std::runtime_error("rcmdyn_put: kpbl is greater than kz");
         if (src[q] != std::floor(src[q])) throw std::runtime_error("rcmdyn_put: kpbl must hold integers");
       }
     }
     if (!have(r->lazy)) enable(r->lazy);
-    HIPCHK(hipStreamSynchronize(stream));
-    const int nk = field_levels(f);
-    for (auto& t : tiles) {
+    put_window(src, b, field_levels(f), [&](Tile& t) {
       double* d = field_ptr(t, f);
       if (!d) throw std::runtime_error("rcmdyn_put: unknown field");
-      scatter_box(t, d, nk, src, j1, j2, i1, i2, k1, k2);
-    }
+      return d;
+    });
     ghosts_stale = true;
     switch (r->after) {
       case fieldtab::NOTHING: break;
@@ -1409,26 +1407,24 @@ struct rcmdyn_engine {
     if (outon) opr_filled = true;
   }
 
-  void get(int f, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get(int f, double* dst, const Box& b) {
     settle();
     // A get names the option (nqx = 5, ibltyp = 2) or the event (the group's first put, the
     // slice, the diagnostics switch) a field waits for, then what the NH slice leaves out.  It
     // does not test NH and HYD_PS: a buffer this engine does not hold, the bdyin record before
     // its first put among them, is an 'unknown field' below, and XPSB_B1 reads as it was stored.
-    if (const fieldtab::Row* r = fieldtab::row(f)) {
+    const fieldtab::Row* r = fieldtab::row(f);
+    if (r) {
       const char* m = r->need == fieldtab::NQX5 || r->need == fieldtab::UW ? lacks(r->need) : nullptr;
       if (!m && !have(r->lazy)) m = WAITS_FOR[r->lazy];
       if (!m && r->need == fieldtab::HYD_Z) m = lacks(r->need);
       if (m) throw std::runtime_error(std::string("rcmdyn_get: ") + m);
     }
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    for (auto& t : tiles) {
+    get_window(dst, b, r ? field_levels(f) : 0, [&](Tile& t) {   // no row: field_ptr is null
       double* d = field_ptr(t, f);
       if (!d) throw std::runtime_error("rcmdyn_get: unknown field");
-      const Geom& g = t.g;
-      gather_box(t, d, field_levels(f), dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
-    }
+      return d;
+    });
   }
 
   // ------------------------------------------------------------------ output stream
@@ -1558,7 +1554,7 @@ struct rcmdyn_engine {
     out_mask = mask;
     out_lcount = hs.lcount;
   }
-  void get_output(int f, void* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_output(int f, void* dst, const Box& b) {
     if (!outon) throw std::runtime_error("rcmdyn_get_output: the output stage is off (rcmdyn_set_output)");
     if (f < 0 || f >= RCMDYN_NOUT) throw std::runtime_error("rcmdyn_get_output: unknown field " + std::to_string(f));
     if (!((out_mask >> f) & 1u))
@@ -1569,19 +1565,12 @@ struct rcmdyn_engine {
       out_mask = 0;
       fail(oflags->slflag, out_lcount, "by step ");
     }
-    const long nj = j2 - j1 + 1, ni = i2 - i1 + 1;
-    const int nk = out_levels(f);
     for (auto& t : tiles) {
       const Geom& g = t.g;
-      const long ncj = g.jci2 - g.jci1 + 1, nci = g.ici2 - g.ici1 + 1;
-      for (int k = std::max(k1, 1); k <= std::min(k2, nk); k++)
-        for (int i = std::max(i1, g.ici1); i <= std::min(i2, g.ici2); i++)
-          for (int j = std::max(j1, g.jci1); j <= std::min(j2, g.jci2); j++) {
-            const size_t d = ((size_t)(k - k1) * ni + (i - i1)) * nj + (j - j1);
-            const size_t s = (size_t)t.ooff[f] + ((size_t)(k - 1) * nci + (i - g.ici1)) * ncj + (j - g.jci1);
-            if (out_prec == 4) ((float*)dst)[d] = ((const float*)t.ohost)[s];
-            else ((double*)dst)[d] = ((const double*)t.ohost)[s];
-          }
+      const int ncj = g.jci2 - g.jci1 + 1, nci = g.ici2 - g.ici1 + 1;
+      const Staging s{g.jci1, g.ici1, ncj, nci, ncj, (long)ncj * nci, out_levels(f), t.ooff[f]};
+      if (out_prec == 4) gather((float*)dst, b, (const float*)t.ohost, s, g.jci1, g.jci2, g.ici1, g.ici2);
+      else gather((double*)dst, b, (const double*)t.ohost, s, g.jci1, g.jci2, g.ici1, g.ici2);
     }
   }
 
@@ -1595,8 +1584,7 @@ struct rcmdyn_engine {
       if (!(rw > 0.0) || !std::isfinite(rw))
         throw std::runtime_error("rcmdyn_set_budget: rw must be finite and positive");
     }
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     if (on && !tiles.empty() && !tiles[0].bud[0])
       for (auto& t : tiles)
         for (double*& d : t.bud) d = dalloc(t, t.g.plane * (size_t)cfg.kz);
@@ -1605,16 +1593,11 @@ struct rcmdyn_engine {
     budget = b;
     if (b) bud_rw = rw;
   }
-  void get_budget(int term, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_budget(int term, double* dst, const Box& b) {
     settle();
     if (!budget) throw std::runtime_error("rcmdyn_get_budget: the tendency budget is off (rcmdyn_set_budget)");
     if (term < 0 || term >= RCMDYN_NBUDGET) throw std::runtime_error("rcmdyn_get_budget: unknown budget term");
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    for (auto& t : tiles) {
-      const Geom& g = t.g;
-      gather_box(t, t.bud[term], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
-    }
+    get_window(dst, b, cfg.kz, [&](Tile& t) { return t.bud[term]; });
   }
   void reset_budget() {
     settle();
@@ -1636,8 +1619,7 @@ struct rcmdyn_engine {
       if (!(conf > 0.0) || !(conf <= 1.0))
         throw std::runtime_error("rcmdyn_set_condtq: conf must be in (0, 1]");
     }
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     const bool b = on != 0;
     if (b == condtq && (!b || conf == ct_conf)) return;
     if (b && !tiles.empty() && !tiles[0].rh0adj)
@@ -1650,50 +1632,36 @@ struct rcmdyn_engine {
     condtq = b;
     if (b) ct_conf = conf;
   }
-  void put_rh0adj(const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void put_rh0adj(const double* src, const Box& b) {
     if (!condtq) throw std::runtime_error("rcmdyn_put_rh0adj: condtq is off (rcmdyn_set_condtq)");
-    const size_t n = (size_t)std::max(0, j2 - j1 + 1) * std::max(0, i2 - i1 + 1) * std::max(0, k2 - k1 + 1);
-    for (size_t q = 0; q < n; q++)
+    for (size_t q = 0, n = b.cells(); q < n; q++)
       if (!(src[q] >= 0.0) || !(src[q] <= 0.99999))
         throw std::runtime_error("rcmdyn_put_rh0adj: rh0adj must lie in [0, 0.99999]");
-    settle();                                        // a pending lazy tend reads the previous values
-    HIPCHK(hipStreamSynchronize(stream));
     // as rcmdyn_put scatters a *PHY field: the ghost ring and the wrapped columns of a band (rows
     // in CRM mode) included, since the hydrostatic step computes the forecasts of the ring as
-    // their owners do
-    for (auto& t : tiles) scatter_box(t, t.rh0adj, cfg.kz, src, j1, j2, i1, i2, k1, k2);
+    // their owners do (a pending lazy tend reads the previous values first)
+    put_window(src, b, cfg.kz, [](Tile& t) { return t.rh0adj; });
     // tend waits for a put that covers every point condtq runs at, on every level: the interior
     // cross points (gci) of each tile and of its ring, the wrapped ones by their wrapped index.
     // None then reads the zeros of the allocation or the values of an earlier switch-on.  Smaller
     // boxes update the buffer before and after that put.
-    bool all = k1 <= 1 && k2 >= cfg.kz;
+    const Period p = period();
+    bool all = b.k1 <= 1 && b.k2 >= cfg.kz;
     for (const auto& t : tiles) {
       const Geom& g = t.g;
-      for (int i = g.icx1(); all && i <= g.icx2(); i++) {
-        const int iw = wrap_i(i);
-        for (int j = g.jcx1(); all && j <= g.jcx2(); j++) {
-          const int jw = wrap_j(j);
-          if (g.gci(j, i) && (jw < j1 || jw > j2 || iw < i1 || iw > i2)) all = false;
-        }
-      }
+      for (int i = g.icx1(); all && i <= g.icx2(); i++)
+        for (int j = g.jcx1(); all && j <= g.jcx2(); j++)
+          if (g.gci(j, i) && !b.holds(p.j(j), p.i(i))) all = false;
     }
     if (all) rh0_put = true;
   }
-  void get_condtq(int term, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_condtq(int term, double* dst, const Box& b) {
     settle();
     if (!condtq) throw std::runtime_error("rcmdyn_get_condtq: condtq is off (rcmdyn_set_condtq)");
     if (term < 0 || term >= RCMDYN_NCONDTQ) throw std::runtime_error("rcmdyn_get_condtq: unknown term");
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    for (auto& t : tiles) {
-      const Geom& g = t.g;
-      // the increments live on the tile's interior cross points (the ring's are its neighbours')
-      if (term == RCMDYN_CONDTQ_RH0ADJ)
-        gather_box(t, t.rh0adj, cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
-      else
-        gather_box(t, t.cti[term - RCMDYN_CONDTQ_T], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jci1, g.jci2, g.ici1,
-                   g.ici2);
-    }
+    // the increments live on the tile's interior cross points (the ring's are its neighbours')
+    if (term == RCMDYN_CONDTQ_RH0ADJ) get_window(dst, b, cfg.kz, [](Tile& t) { return t.rh0adj; });
+    else get_window(dst, b, cfg.kz, [&](Tile& t) { return t.cti[term - RCMDYN_CONDTQ_T]; }, Range::Interior);
   }
 
   // ------------------------------------------------------------------ chemical tracers
@@ -1757,14 +1725,6 @@ struct rcmdyn_engine {
     tr_relax = false;
     ntr = 0;
   }
-  template <class T>
-  T* tr_alloc(Tile& t, size_t n) {
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, n * sizeof(T)));
-    t.tr_allocs.push_back(p);
-    HIPCHK(hipMemset(p, 0, n * sizeof(T)));
-    return (T*)p;
-  }
   void set_tracers(int n, int ichebdy) {
     if (n < 0 || n > RCMDYN_MAXTR)
       throw std::runtime_error("rcmdyn_set_tracers: ntr must lie in 0 .. RCMDYN_MAXTR = " + std::to_string(RCMDYN_MAXTR));
@@ -1777,8 +1737,7 @@ struct rcmdyn_engine {
       if (cfg.isladvec == 1)
         throw std::runtime_error("rcmdyn_set_tracers: isladvec = 1 is not built for tracers (slhadv_x of chi)");
     }
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     if (n == ntr) return;
     invalidate_graphs();
     free_tracers();
@@ -1850,27 +1809,20 @@ struct rcmdyn_engine {
     if (itr < 1 || itr > ntr)
       throw std::runtime_error(std::string(who) + ": itr must lie in 1 .. ntr = " + std::to_string(ntr));
   }
-  void put_tracer(int field, int itr, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void put_tracer(int field, int itr, const double* src, const Box& b) {
     tracer_check("rcmdyn_put_tracer", field, itr);
     if (field == RCMDYN_TR_CHIB3D) throw std::runtime_error("rcmdyn_put_tracer: TR_CHIB3D is read-only (the mkslice export)");
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
-    for (auto& t : tiles) scatter_box(t, tracer_ptr(t, field, itr - 1), cfg.kz, src, j1, j2, i1, i2, k1, k2);
+    put_window(src, b, cfg.kz, [&](Tile& t) { return tracer_ptr(t, field, itr - 1); });
     if (field == RCMDYN_TR_B0 || field == RCMDYN_TR_BT) tr_bdy_dirty = true;
     else ghosts_stale = true;
   }
-  void get_tracer(int field, int itr, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_tracer(int field, int itr, double* dst, const Box& b) {
     tracer_check("rcmdyn_get_tracer", field, itr);
     if (field == RCMDYN_TR_PHY) throw std::runtime_error("rcmdyn_get_tracer: TR_PHY is put-only (the host's chiphy)");
     settle();
     if (field == RCMDYN_TR_CHIB3D && !tiles.empty() && !tiles[0].trs3d[itr - 1])
       throw std::runtime_error("rcmdyn_get_tracer: no slice fields yet (rcmdyn_tend_pre_physics)");
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    for (auto& t : tiles) {
-      const Geom& g = t.g;
-      gather_box(t, tracer_ptr(t, field, itr - 1), cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
-    }
+    get_window(dst, b, cfg.kz, [&](Tile& t) { return tracer_ptr(t, field, itr - 1); });
   }
   void put_tracer_nudge(const double* cefc, const double* cegc) {
     if (ntr == 0) throw std::runtime_error("rcmdyn_put_tracer_nudge: no tracers are declared (rcmdyn_set_tracers)");
@@ -1882,8 +1834,7 @@ struct rcmdyn_engine {
         throw std::runtime_error("rcmdyn_put_tracer_nudge: the tables must be finite");
       nz = nz || cefc[q] != 0.0 || cegc[q] != 0.0;
     }
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();
     HIPCHK(hipMemcpy(tr_cefc, cefc, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(tr_cegc, cegc, n * sizeof(double), hipMemcpyHostToDevice));
     if (nz != tr_relax) invalidate_graphs();         // the term's switch is a kernel argument
@@ -1901,8 +1852,7 @@ struct rcmdyn_engine {
       if (ntr == 0) throw std::runtime_error("rcmdyn_set_cumtran: no tracers are declared (rcmdyn_set_tracers)");
       if (ncum < 1) throw std::runtime_error("rcmdyn_set_cumtran: ncum must be at least 1 (dtcum / dtsec in steps)");
     }
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     const bool b = on != 0;
     if (b == cumtran && (!b || ncum == cum_ncum)) return;
     if (b && !cumtran)
@@ -1921,11 +1871,14 @@ struct rcmdyn_engine {
     if (!cumtran) throw std::runtime_error(std::string(who) + ": cumtran is off (rcmdyn_set_cumtran)");
     if (field < 0 || field >= RCMDYN_NCUMFIELDS) throw std::runtime_error(std::string(who) + ": unknown cumtran field");
   }
-  void put_cumtran(int field, const double* src, int j1, int j2, int i1, int i2, int k1, int k2) {
+  // a one-level field is level 1 whatever k1, k2 say
+  Box cum_box(int field, const Box& b) const {
+    return cum_levels(field) == 1 ? Box{b.j1, b.j2, b.i1, b.i2, 1, 1} : b;
+  }
+  void put_cumtran(int field, const double* src, const Box& host) {
     cumtran_check("rcmdyn_put_cumtran", field);
-    const int nk = cum_levels(field);
-    const size_t n = (size_t)std::max(0, j2 - j1 + 1) * std::max(0, i2 - i1 + 1) * (nk == 1 ? 1 : std::max(0, k2 - k1 + 1));
-    for (size_t q = 0; q < n; q++) {
+    const Box b = cum_box(field, host);
+    for (size_t q = 0, n = b.cells(); q < n; q++) {
       const double v = src[q];
       if (field == RCMDYN_CUM_DOTRAN && v != 0.0 && v != 1.0)
         throw std::runtime_error("rcmdyn_put_cumtran: CUM_DOTRAN must hold 0 or 1");
@@ -1934,21 +1887,12 @@ struct rcmdyn_engine {
       if (field == RCMDYN_CUM_CLDFRA && (!(v >= 0.0) || !(v <= 1.0)))
         throw std::runtime_error("rcmdyn_put_cumtran: CUM_CLDFRA must be finite and lie in [0, 1]");
     }
-    settle();                                        // a pending lazy tend reads the previous values
-    HIPCHK(hipStreamSynchronize(stream));
-    for (auto& t : tiles) scatter_box(t, t.cum[field], nk, src, j1, j2, i1, i2, nk == 1 ? 1 : k1, nk == 1 ? 1 : k2);
+    // (a pending lazy tend reads the previous values first)
+    put_window(src, b, cum_levels(field), [&](Tile& t) { return t.cum[field]; });
   }
-  void get_cumtran(int field, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_cumtran(int field, double* dst, const Box& host) {
     cumtran_check("rcmdyn_get_cumtran", field);
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    const int nk = cum_levels(field);
-    for (auto& t : tiles) {
-      const Geom& g = t.g;
-      gather_box(t, t.cum[field], nk, dst, j1, j2, i1, i2, nk == 1 ? 1 : k1, nk == 1 ? 1 : k2, g.jde1, g.jde2, g.ide1,
-                 g.ide2);
-    }
+    get_window(dst, cum_box(field, host), cum_levels(field), [&](Tile& t) { return t.cum[field]; });
   }
   TrCum cum_args(const Tile& t) const {
     return TrCum{t.cum[0], t.cum[1], t.cum[2], trbudget ? t.trbudtab + RCMDYN_TRDIAG_CONV * ntr : nullptr, trb_cfdout,
@@ -1968,8 +1912,7 @@ struct rcmdyn_engine {
       if (!std::isfinite(rw)) throw std::runtime_error("rcmdyn_set_tracer_budget: rw must be finite");
       if (!std::isfinite(cfdout)) throw std::runtime_error("rcmdyn_set_tracer_budget: cfdout must be finite");
     }
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     const bool b = on != 0;
     if (b == trbudget && (!b || (rw == trb_rw && cfdout == trb_cfdout))) return;
     if (b && !trbudget)
@@ -1987,23 +1930,16 @@ struct rcmdyn_engine {
     trbudget = b;
     if (b) { trb_rw = rw; trb_cfdout = cfdout; }
   }
-  void get_tracer_budget(int term, int itr, double* dst, int j1, int j2, int i1, int i2, int k1, int k2) {
+  void get_tracer_budget(int term, int itr, double* dst, const Box& b) {
     if (!trbudget) throw std::runtime_error("rcmdyn_get_tracer_budget: the tracer budget is off (rcmdyn_set_tracer_budget)");
     if (term < 0 || term >= RCMDYN_NTRDIAG) throw std::runtime_error("rcmdyn_get_tracer_budget: unknown budget term");
     if (itr < 1 || itr > ntr)
       throw std::runtime_error("rcmdyn_get_tracer_budget: itr must lie in 1 .. ntr = " + std::to_string(ntr));
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
-    check_now();
-    for (auto& t : tiles) {
-      const Geom& g = t.g;
-      gather_box(t, t.trbud[term * ntr + itr - 1], cfg.kz, dst, j1, j2, i1, i2, k1, k2, g.jde1, g.jde2, g.ide1, g.ide2);
-    }
+    get_window(dst, b, cfg.kz, [&](Tile& t) { return t.trbud[term * ntr + itr - 1]; });
   }
   void reset_tracer_budget() {
     if (!trbudget) throw std::runtime_error("rcmdyn_reset_tracer_budget: the tracer budget is off (rcmdyn_set_tracer_budget)");
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();
     for (auto& t : tiles)
       for (double* d : t.trbud) HIPCHK(hipMemset(d, 0, (size_t)t.g.plane * cfg.kz * sizeof(double)));
   }
@@ -2055,8 +1991,7 @@ struct rcmdyn_engine {
   void set_massck(int on, int cap) {
     if (on && (cap < 1 || cap > 65536))
       throw std::runtime_error("rcmdyn_set_massck: cap must be between 1 and 65536 records");
-    settle();                                        // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();                                       // a lazy tend replays its graph first
     const bool b = on != 0;
     if (b == massck && (!b || cap == mck_cap)) return;   // the same switch: the log is kept
     invalidate_graphs();
@@ -3533,9 +3468,8 @@ struct rcmdyn_engine {
   void kernel_times(int nsteps, int cap, char* names, int32_t* launches, double* avg, int32_t* count) {
     condtq_ready("rcmdyn_kernel_times");
     prepare();
-    settle();
+    quiesce();
     KernelProf kp;
-    HIPCHK(hipStreamSynchronize(stream));
     {
       struct Scope { KernelProf*& p; ~Scope() { p = nullptr; } } profiling{prof = &kp};   // however the steps end
       for (int s = 0; s < nsteps; s++) step_once();
@@ -3563,8 +3497,7 @@ struct rcmdyn_engine {
   }
 
   void set_time(long long lcount, double dt, double xbctime) {
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();
     pending.clear();
     gpending.clear();
     StepState st;
@@ -3596,8 +3529,7 @@ struct rcmdyn_engine {
   }
 
   void diagnostics(double out[4]) {
-    settle();
-    HIPCHK(hipStreamSynchronize(stream));
+    quiesce();
     check_now();
     StepState st;
     HIPCHK(hipMemcpy(&st, ds, sizeof(st), hipMemcpyDeviceToHost));
@@ -3773,12 +3705,12 @@ int rcmdyn_tile_extent_cfg(const rcmdyn_config* cfg, int32_t tile, int32_t ext[8
 
 int rcmdyn_put(rcmdyn_t* h, int32_t field, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->put(field, src, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->put(field, src, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_get(rcmdyn_t* h, int32_t field, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
                int32_t k2) {
-  return guard(h, [&] { h->get(field, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get(field, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_set_time(rcmdyn_t* h, int64_t lcount, double dt, double xbctime) {
@@ -3851,8 +3783,7 @@ int rcmdyn_last_step_ms(rcmdyn_t* h, double* ms) { return guard(h, [&] { *ms = h
 
 int rcmdyn_set_diagnostics(rcmdyn_t* h, int32_t on) {
   return guard(h, [&] {
-    h->settle();                                     // a lazy tend replays its graph first
-    HIPCHK(hipStreamSynchronize(h->stream));
+    h->quiesce();                                    // a lazy tend replays its graph first
     if (h->diag != (on != 0)) {
       h->diag = (on != 0);
       h->invalidate_graphs();
@@ -3866,7 +3797,7 @@ int rcmdyn_set_budget(rcmdyn_t* h, int32_t on, int32_t idgq, double rw) {
 
 int rcmdyn_get_budget(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                       int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->get_budget(term, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_budget(term, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_reset_budget(rcmdyn_t* h) { return guard(h, [&] { h->reset_budget(); }); }
@@ -3885,12 +3816,12 @@ int rcmdyn_set_condtq(rcmdyn_t* h, int32_t on, double conf) {
 
 int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
                       int32_t k2) {
-  return guard(h, [&] { h->put_rh0adj(src, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->put_rh0adj(src, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                       int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->get_condtq(term, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_condtq(term, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_set_tracers(rcmdyn_t* h, int32_t ntr, int32_t ichebdy) {
@@ -3899,12 +3830,12 @@ int rcmdyn_set_tracers(rcmdyn_t* h, int32_t ntr, int32_t ichebdy) {
 
 int rcmdyn_put_tracer(rcmdyn_t* h, int32_t field, int32_t itr, const double* src, int32_t j1, int32_t j2, int32_t i1,
                       int32_t i2, int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->put_tracer(field, itr, src, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->put_tracer(field, itr, src, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_get_tracer(rcmdyn_t* h, int32_t field, int32_t itr, double* dst, int32_t j1, int32_t j2, int32_t i1,
                       int32_t i2, int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->get_tracer(field, itr, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_tracer(field, itr, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_put_tracer_nudge(rcmdyn_t* h, const double* cefc, const double* cegc) {
@@ -3917,12 +3848,12 @@ int rcmdyn_set_cumtran(rcmdyn_t* h, int32_t on, int32_t ncum) {
 
 int rcmdyn_put_cumtran(rcmdyn_t* h, int32_t field, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                        int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->put_cumtran(field, src, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->put_cumtran(field, src, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_get_cumtran(rcmdyn_t* h, int32_t field, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
                        int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->get_cumtran(field, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_cumtran(field, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_set_tracer_budget(rcmdyn_t* h, int32_t on, double rw, double cfdout) {
@@ -3931,7 +3862,7 @@ int rcmdyn_set_tracer_budget(rcmdyn_t* h, int32_t on, double rw, double cfdout) 
 
 int rcmdyn_get_tracer_budget(rcmdyn_t* h, int32_t term, int32_t itr, double* dst, int32_t j1, int32_t j2, int32_t i1,
                              int32_t i2, int32_t k1, int32_t k2) {
-  return guard(h, [&] { h->get_tracer_budget(term, itr, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_tracer_budget(term, itr, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_reset_tracer_budget(rcmdyn_t* h) {
@@ -3944,7 +3875,7 @@ int rcmdyn_set_output(rcmdyn_t* h, int32_t on, int32_t prec) {
 int rcmdyn_output_atm(rcmdyn_t* h, uint32_t mask) { return guard(h, [&] { h->output_atm(mask); }); }
 int rcmdyn_get_output(rcmdyn_t* h, int32_t field, void* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
                       int32_t k2) {
-  return guard(h, [&] { h->get_output(field, dst, j1, j2, i1, i2, k1, k2); });
+  return guard(h, [&] { h->get_output(field, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

@@ -47,10 +47,19 @@ IQV = 1    # the reference's index of water vapour (Main/mpplib/mod_runparams.F9
 MASSCK_COLUMNS = ("lcount", "dt", "drymass", "dryadv", "qmass", "qadv")
 # enum rcmdyn_condtq_term, in order: the held rh0adj, the last tend's condensation increments
 CONDTQ_TERMS = ["RH0ADJ", "T", "QV", "QC"]
+# the host box every put and get ends with: j1, j2, i1, i2, k1, k2
+BOX = [ctypes.c_int32] * 6
 
 
 class EngineError(RuntimeError):
     pass
+
+
+def _number(table, key) -> int:
+    """A term or field by name (table: the names in order, or a name -> number dict) or by number."""
+    if not isinstance(key, str):
+        return int(key)
+    return table[key] if isinstance(table, dict) else table.index(key)
 
 
 def lib():
@@ -71,8 +80,8 @@ def lib():
     L.rcmdyn_set_nproc.argtypes = [i32, i32, i32, ctypes.POINTER(i32)]
     L.rcmdyn_tile_extent.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.rcmdyn_tile_extent_cfg.argtypes = [ctypes.POINTER(RcmdynConfig), i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    L.rcmdyn_put.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
-    L.rcmdyn_get.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put.argtypes = [P, i32, dp, *BOX]
+    L.rcmdyn_get.argtypes = [P, i32, dp, *BOX]
     L.rcmdyn_set_time.argtypes = [P, ctypes.c_int64, ctypes.c_double, ctypes.c_double]
     L.rcmdyn_get_time.argtypes = [P, ctypes.POINTER(ctypes.c_int64), dp, dp]
     L.rcmdyn_tend.argtypes = [P]
@@ -93,26 +102,26 @@ def lib():
     L.rcmdyn_overlap_shares.argtypes = [ctypes.POINTER(RcmdynConfig), ctypes.POINTER(i32), i32]
     L.rcmdyn_kernel_times.argtypes = [P, i32, i32, ctypes.c_char_p, ctypes.POINTER(i32), dp, ctypes.POINTER(i32)]
     L.rcmdyn_set_budget.argtypes = [P, i32, i32, ctypes.c_double]
-    L.rcmdyn_get_budget.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_budget.argtypes = [P, i32, dp, *BOX]
     L.rcmdyn_reset_budget.argtypes = [P]
     L.rcmdyn_set_massck.argtypes = [P, i32, i32]
     L.rcmdyn_get_massck.argtypes = [P, dp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64)]
     L.rcmdyn_set_condtq.argtypes = [P, i32, ctypes.c_double]
-    L.rcmdyn_put_rh0adj.argtypes = [P, dp, i32, i32, i32, i32, i32, i32]
-    L.rcmdyn_get_condtq.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put_rh0adj.argtypes = [P, dp, *BOX]
+    L.rcmdyn_get_condtq.argtypes = [P, i32, dp, *BOX]
     L.rcmdyn_set_tracers.argtypes = [P, i32, i32]
-    L.rcmdyn_put_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
-    L.rcmdyn_get_tracer.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put_tracer.argtypes = [P, i32, i32, dp, *BOX]
+    L.rcmdyn_get_tracer.argtypes = [P, i32, i32, dp, *BOX]
     L.rcmdyn_put_tracer_nudge.argtypes = [P, dp, dp]
     L.rcmdyn_set_cumtran.argtypes = [P, i32, i32]
-    L.rcmdyn_put_cumtran.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
-    L.rcmdyn_get_cumtran.argtypes = [P, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put_cumtran.argtypes = [P, i32, dp, *BOX]
+    L.rcmdyn_get_cumtran.argtypes = [P, i32, dp, *BOX]
     L.rcmdyn_set_tracer_budget.argtypes = [P, i32, ctypes.c_double, ctypes.c_double]
-    L.rcmdyn_get_tracer_budget.argtypes = [P, i32, i32, dp, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_tracer_budget.argtypes = [P, i32, i32, dp, *BOX]
     L.rcmdyn_reset_tracer_budget.argtypes = [P]
     L.rcmdyn_set_output.argtypes = [P, i32, i32]
     L.rcmdyn_output_atm.argtypes = [P, ctypes.c_uint32]
-    L.rcmdyn_get_output.argtypes = [P, i32, ctypes.c_void_p, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_get_output.argtypes = [P, i32, ctypes.c_void_p, *BOX]
     _lib = L
     return L
 
@@ -220,18 +229,27 @@ class DynCore:
         except Exception:
             pass
 
-    def put(self, name: str, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+    def _put_box(self, fn, arr, j1, i1, k1, *lead):
+        """fn(h, *lead, src, box) with a (nk, ni, nj) array as the box that starts at the global
+        indices (j1, i1, k1)."""
         a = np.ascontiguousarray(arr, dtype=np.float64)
         nk, ni, nj = a.shape
-        self._check(lib().rcmdyn_put(self.h, FIELD[name], a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                     j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+        self._check(fn(self.h, *lead, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                       j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+
+    def _get_box(self, fn, nk, *lead, dtype=np.float64) -> np.ndarray:
+        """fn(h, *lead, dst, box) over the whole domain and nk levels: a zero-filled (nk, iy, jx) array
+        with what the call wrote."""
+        out = np.zeros((nk, self.rc.iy, self.rc.jx), dtype=dtype)
+        self._check(fn(self.h, *lead, out.ctypes.data_as(fn.argtypes[1 + len(lead)]),
+                       1, self.rc.jx, 1, self.rc.iy, 1, nk))
+        return out
+
+    def put(self, name: str, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+        self._put_box(lib().rcmdyn_put, arr, j1, i1, k1, FIELD[name])
 
     def get(self, name: str) -> np.ndarray:
-        nk = field_levels(name, self.rc.kz, self.rc.nsplit)
-        out = np.zeros((nk, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get(self.h, FIELD[name], out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                     1, self.rc.jx, 1, self.rc.iy, 1, nk))
-        return out
+        return self._get_box(lib().rcmdyn_get, field_levels(name, self.rc.kz, self.rc.nsplit), FIELD[name])
 
     def put_state(self, st: dict):
         for name, arr in st.items():
@@ -297,11 +315,7 @@ class DynCore:
     def get_budget(self, term) -> np.ndarray:
         """One accumulator, by name (BUDGET_TERMS) or number, as a (kz, iy, jx) array: zero
         outside the interior cross points."""
-        n = BUDGET_TERMS.index(term) if isinstance(term, str) else int(term)
-        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get_budget(self.h, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
-        return out
+        return self._get_box(lib().rcmdyn_get_budget, self.rc.kz, _number(BUDGET_TERMS, term))
 
     def reset_budget(self):
         """Zeroes the ten accumulators (the host does it after writing them to the ATM file)."""
@@ -334,20 +348,13 @@ class DynCore:
         """cldfrac's adjusted humidity threshold, a (kz, ni, nj) array of values in [0, 0.99999]
         starting at the global indices (j1, i1, k1).  tend waits for one put since the switch-on
         that covers the interior cross points of the tiles and their rings on every level."""
-        a = np.ascontiguousarray(arr, dtype=np.float64)
-        nk, ni, nj = a.shape
-        self._check(lib().rcmdyn_put_rh0adj(self.h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+        self._put_box(lib().rcmdyn_put_rh0adj, arr, j1, i1, k1)
 
     def get_condtq(self, term) -> np.ndarray:
         """One term by name (CONDTQ_TERMS) or number as a (kz, iy, jx) array: the held rh0adj, or
         the last tend's coupled condensation increment of t, qv or qc (zero outside the interior
         cross points)."""
-        n = CONDTQ_TERMS.index(term) if isinstance(term, str) else int(term)
-        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get_condtq(self.h, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
-        return out
+        return self._get_box(lib().rcmdyn_get_condtq, self.rc.kz, _number(CONDTQ_TERMS, term))
 
     def set_tracers(self, ntr: int, ichebdy: int = 1):
         """Declares ntr chemical tracers (the reference's ichem = 1 chain of tend and bdyval);
@@ -357,19 +364,11 @@ class DynCore:
     def put_tracer(self, name, itr: int, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
         """One field (TRACER_FIELDS name or number) of tracer itr = 1..ntr, a (kz, ni, nj) array
         coupled with p*, starting at the global indices (j1, i1, k1)."""
-        f = TRACER_FIELD[name] if isinstance(name, str) else int(name)
-        a = np.ascontiguousarray(arr, dtype=np.float64)
-        nk, ni, nj = a.shape
-        self._check(lib().rcmdyn_put_tracer(self.h, f, itr, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+        self._put_box(lib().rcmdyn_put_tracer, arr, j1, i1, k1, _number(TRACER_FIELD, name), itr)
 
     def get_tracer(self, name, itr: int) -> np.ndarray:
         """One field of tracer itr as a (kz, iy, jx) array."""
-        f = TRACER_FIELD[name] if isinstance(name, str) else int(name)
-        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get_tracer(self.h, f, itr, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
-        return out
+        return self._get_box(lib().rcmdyn_get_tracer, self.rc.kz, _number(TRACER_FIELD, name), itr)
 
     def put_tracer_nudge(self, cefc: np.ndarray, cegc: np.ndarray):
         """nudge_chiten's tables as (kz, nspgx) arrays, [k - 1, ib - 1] = cefc(ib, k); zero until put."""
@@ -390,22 +389,13 @@ class DynCore:
         """One input (CUMTRAN_FIELDS name or number): DOTRAN (0 / 1) and KTOP (integers in 0 .. kz)
         as (ni, nj) or (1, ni, nj) arrays, CLDFRA (in [0, 1]) as a (kz, ni, nj) array, starting at
         the global indices (j1, i1, k1)."""
-        f = CUMTRAN_FIELD[name] if isinstance(name, str) else int(name)
-        a = np.ascontiguousarray(arr, dtype=np.float64)
-        if a.ndim == 2:
-            a = a[None]
-        nk, ni, nj = a.shape
-        self._check(lib().rcmdyn_put_cumtran(self.h, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                             j1, j1 + nj - 1, i1, i1 + ni - 1, k1, k1 + nk - 1))
+        a = np.asarray(arr)
+        self._put_box(lib().rcmdyn_put_cumtran, a[None] if a.ndim == 2 else a, j1, i1, k1, _number(CUMTRAN_FIELD, name))
 
     def get_cumtran(self, name) -> np.ndarray:
         """One held input as a (1, iy, jx) array (DOTRAN, KTOP) or a (kz, iy, jx) array (CLDFRA)."""
-        f = CUMTRAN_FIELD[name] if isinstance(name, str) else int(name)
-        nk = self.rc.kz if f == CUMTRAN_FIELD["CLDFRA"] else 1
-        out = np.zeros((nk, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get_cumtran(self.h, f, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                             1, self.rc.jx, 1, self.rc.iy, 1, nk))
-        return out
+        f = _number(CUMTRAN_FIELD, name)
+        return self._get_box(lib().rcmdyn_get_cumtran, self.rc.kz if f == CUMTRAN_FIELD["CLDFRA"] else 1, f)
 
     def set_tracer_budget(self, on: bool = True, rw: float = 1.0, cfdout: float = 1.0):
         """The tracer budget (ichdiag > 0): every later tend adds each stage term times rw (the
@@ -416,11 +406,7 @@ class DynCore:
     def get_tracer_budget(self, term, itr: int) -> np.ndarray:
         """One accumulator (TRACER_DIAG_TERMS name or number) of tracer itr as a (kz, iy, jx) array:
         zero outside the interior cross points."""
-        n = TRACER_DIAG_TERM[term] if isinstance(term, str) else int(term)
-        out = np.zeros((self.rc.kz, self.rc.iy, self.rc.jx))
-        self._check(lib().rcmdyn_get_tracer_budget(self.h, n, itr, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                   1, self.rc.jx, 1, self.rc.iy, 1, self.rc.kz))
-        return out
+        return self._get_box(lib().rcmdyn_get_tracer_budget, self.rc.kz, _number(TRACER_DIAG_TERM, term), itr)
 
     def reset_tracer_budget(self):
         """Zeroes every accumulator (the host does it after writing them at alarm_out_che)."""
@@ -443,19 +429,17 @@ class DynCore:
         else:
             mask = 0
             for f in fields:
-                mask |= 1 << (OUTPUT_FIELD[f] if isinstance(f, str) else int(f))
+                mask |= 1 << _number(OUTPUT_FIELD, f)
         self._check(lib().rcmdyn_output_atm(self.h, mask))
 
     def get_output(self, name) -> np.ndarray:
         """One field of the last output_atm as a (kz, iy, jx) array, (1, iy, jx) for the 2-D fields,
         float32 or float64 by set_output's prec: zero outside the interior cross points.  Waits for
         that snapshot's copy only."""
-        f = OUTPUT_FIELD[name] if isinstance(name, str) else int(name)
+        f = _number(OUTPUT_FIELD, name)
         nk = 1 if 0 <= f < len(OUTPUT_FIELDS) and OUTPUT_FIELDS[f] in OUTPUT_2D else self.rc.kz
-        out = np.zeros((nk, self.rc.iy, self.rc.jx), dtype=np.float32 if getattr(self, "_out_prec", 8) == 4 else np.float64)
-        self._check(lib().rcmdyn_get_output(self.h, f, out.ctypes.data_as(ctypes.c_void_p),
-                                            1, self.rc.jx, 1, self.rc.iy, 1, nk))
-        return out
+        return self._get_box(lib().rcmdyn_get_output, nk, f,
+                             dtype=np.float32 if getattr(self, "_out_prec", 8) == 4 else np.float64)
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""
