@@ -802,10 +802,14 @@ struct rcmdyn_engine {
   // The dynamic LDS the launches request grows with the tile: the serial moisture fix's
   // (negfix_lds / negfix_sweep_lds, a row of the plane) and k_split_project's (4 x kz x SPC).
   // Check the owned tiles' requests against the device's limit at create, so a tile too large
-  // for them is refused here rather than failing a launch inside a step.
+  // for them is refused here rather than failing a launch inside a step.  The hydrostatic
+  // k_columns asks for col_lds() (4 x kz x COLW, twice k_split_project's) whatever the tile.
   void check_lds() {
     int maxs = 0;
     HIPCHK(hipDeviceGetAttribute(&maxs, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+    if (cfg.idynamic != 2 && col_lds() > (size_t)maxs)
+      throw std::runtime_error("rcmdyn: k_columns at kz = " + std::to_string(cfg.kz) + " needs " + std::to_string(col_lds()) +
+                               " bytes of LDS per block, the device allows " + std::to_string(maxs));
     for (int t = 0; t < cfg.tile_count; t++) {
       const Geom& g = all[cfg.tile_first + t];
       const size_t need = sizeof(double) * (size_t)std::max(negfix_lds(g), 4 * cfg.kz * SPC);

@@ -6,7 +6,7 @@ sponges, and the assembled hydrostatic totals.  One tend from the state after th
 Grids: C1 cut to 37 x 29 (nspgx = nspgd = 7: two 32-wide block columns with the second partial,
 four 8-row block rows with the last partial) and to 34 x 23 with the same band depth (the last cross
 column alone in its block, the two sides' nspgx-deep zones 9 rows apart with 8 rows between).  Variants:
-default (iboudy 5, idiffu 1), iboudy 1, iboudy 4, idiffu 2, diffu_hgtf 0.
+default (iboudy 5, idiffu 1), iboudy 1, iboudy 4, idiffu 2, diffu_hgtf 0, and the default at kz 14 and 41.
 
 Tolerances.
  - XKC and PTEN (with its nudge2d / sponge2d term): bit for bit.  No transcendental but the exp of
@@ -56,7 +56,8 @@ from tests import dyn_ref as dr
 from tests.support import case, oracle, variant_id
 
 GRIDS = {"37x29": {}, "34x23": dict(jx=34, iy=23, nspgx=7, nspgd=7)}
-VARIANTS = [{}, {"iboudy": 1}, {"iboudy": 4}, {"idiffu": 2}, {"diffu_hgtf": 0}]
+LEVELS = [{"kz": 14}, {"kz": 41}]          # the sigma tables beside C1's 18 levels (23 is C2's to C4's)
+VARIANTS = [{}, {"iboudy": 1}, {"iboudy": 4}, {"idiffu": 2}, {"diffu_hgtf": 0}] + LEVELS
 NO_DIF = dict(ckh=0.0, adyndif=0.0)
 TOTALS = (("TTEN", "T", False), ("QVTEN", "Q", False), ("QCTEN", "C", False), ("UTEN", "U", True), ("VTEN", "V", True))
 N_ADD = {("T", "dif"): 5, ("Q", "dif"): 5, ("C", "dif"): 5, ("U", "dif"): 9, ("V", "dif"): 9,

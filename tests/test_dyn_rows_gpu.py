@@ -9,7 +9,8 @@ tiles (the second-order rows belong to the domain edge: an interior tile boundar
 fourth-order form), and N1 cut to 37 x 29 for the non-hydrostatic budget terms.
 
 Tolerances.
- - XKC and PTEN: bit for bit (iboudy 5, 1, 4; diffu_hgtf 0, 1).
+ - XKC and PTEN: bit for bit (iboudy 5, 1, 4; diffu_hgtf 0, 1; kz 14 and 41 beside C1's 18, on both
+   grids and as 2 x 2 tiles).
  - T_DIF, Q_DIF, T_BDY, Q_BDY against the restatement's terms: a budget term is the rounded
    difference of the running sum around the process, and the running sum takes one rounded addition
    per increment: n = 3 (two line adds at a corner, or xf fls0 and xg (...); the difference), bound
@@ -45,14 +46,15 @@ from regcm_amd.dycore import BUDGET_TERMS, tile_extent
 from tests import dyn_ref as dr
 from tests import support
 from tests.support import case, variant_id
-from tests.test_dyn_rows_cpu import (D6, D6_OFF, GRIDS, N_ADD, NO_DIF, PGF_VARIANTS, TOTALS, check_diffu6_edges,
+from tests.test_dyn_rows_cpu import (D6, D6_OFF, GRIDS, LEVELS, N_ADD, NO_DIF, PGF_VARIANTS, TOTALS, check_diffu6_edges,
                                      check_ipgf1, check_term, column_mask, prepared, same_state, sponge_support, start)
 
 pytestmark = pytest.mark.gpu
 
 ONE = (1, 1)
 CASES = ([(g, v, ONE) for g in GRIDS for v in ({}, {"iboudy": 1}, {"iboudy": 4}, {"idiffu": 2}, {"diffu_hgtf": 0})] +
-         [("37x29", v, (2, 2)) for v in ({}, {"iboudy": 4}, {"idiffu": 2})])
+         [("37x29", v, (2, 2)) for v in ({}, {"iboudy": 4}, {"idiffu": 2})] +
+         [(g, v, ONE) for g in GRIDS for v in LEVELS] + [("37x29", v, (2, 2)) for v in LEVELS])
 N_BUDGET = 3
 NH_INPUTS = ("ATM2_U", "ATM2_V", "ATM2_W", "ATM2_T", "ATM2_QV", "ATM2_QC", "PSB", "HT", "XTB_B0", "XTB_BT", "XQB_B0",
              "XQB_BT")

@@ -110,6 +110,71 @@ def test_narrow_tiles_per_substep_exchange_plans_match():
     check_plans(plans(rc, data["split"], 1, 7, 2), 1, 7)
 
 
+SPX = 9            # the depth of the fused split step's one exchange (kernels.hpp: SPH + 1)
+
+
+def message_sig(segs):
+    """The signature the engine gives a message of the (levels, width, height) boxes in segs (layout())."""
+    h = 1469598103934665603
+    for seg in segs:
+        for v in seg:
+            h = ((h ^ v) * 1099511628211) & ((1 << 64) - 1)
+    return h & 0x7fffffffffffffff
+
+
+def split_message(count, sig, ns):
+    """Which split-step exchange a message of count doubles and signature sig belongs to: "delh" (one
+    plane, one line deep), "uv" (uu and vv, one line deep), "dhsum" (its ns planes, one line deep), "wide" (the
+    fused step's 3 ns slots of deld and delh, p*a and psdota, SPX deep), or None."""
+    forms = {"delh": ([1], 1), "uv": ([1, 1], 1), "dhsum": ([ns], 1), "wide": ([3 * ns, 3 * ns, 1, 1], SPX)}
+    for name, (levels, depth) in forms.items():
+        length, rest = divmod(count, sum(levels) * depth)
+        if rest == 0 and sig in (message_sig([(nk, depth, length) for nk in levels]),
+                                 message_sig([(nk, length, depth) for nk in levels])):
+            return name
+    return None
+
+
+def split_calls(plan, ns):
+    """{exchange: the number of exchange calls all of whose messages are that exchange's} of one rank's plan."""
+    calls = defaultdict(set)
+    for call, kind, _, _, _, count, sig in plan.tolist():
+        if kind == 1:
+            calls[call].add(split_message(count, sig, ns))
+    out = defaultdict(int)
+    for kinds in calls.values():
+        if len(kinds) == 1:
+            out[next(iter(kinds))] += 1
+    return out
+
+
+@pytest.mark.parametrize("nsplit", [3, 4])
+def test_unfused_split_step_plans_hold_the_substep_messages(nsplit):
+    """nsplit >= 3 leaves the fused split step on any tiling (2 aam(l) = 4 (nsplit - l + 1) exceeds its 8
+    sub-steps): every step of a 2 x 2 job then issues, for each of the 2 nsplit (nsplit + 1) sub-steps, the
+    exchange of delh's slot and that of uu / vv, and once the exchange of dhsum, and no wide exchange.  The
+    nsplit = 2 plan holds the one wide exchange per step and none of the others.  Counted as the difference of
+    a two-step and a one-step plan, on every rank; the plans match rank to rank."""
+    base = CONFIGS["C1"]
+    counts = {}
+    for ns in (2, nsplit):
+        rc = dataclasses.replace(base, nsplit=ns)
+        split = icbc.generate(rc)["split"]
+        one, two = plans(rc, split, 2, 2, 1), plans(rc, split, 2, 2, 2)
+        check_plans(two, 2, 2)
+        per_step = []
+        for a, b in zip(one, two):
+            ca, cb = split_calls(a, ns), split_calls(b, ns)
+            per_step.append({k: cb[k] - ca[k] for k in ("delh", "uv", "dhsum", "wide")})
+            assert ca["delh"] == per_step[-1]["delh"] and ca["wide"] == per_step[-1]["wide"]    # the first step alike
+        assert all(p == per_step[0] for p in per_step), per_step
+        counts[ns] = per_step[0]
+    sub = 2 * nsplit * (nsplit + 1)
+    assert sub == {3: 24, 4: 40}[nsplit]
+    assert counts[nsplit] == {"delh": sub, "uv": sub, "dhsum": 1, "wide": 0}, counts
+    assert counts[2] == {"delh": 0, "uv": 0, "dhsum": 0, "wide": 1}, counts
+
+
 @pytest.mark.parametrize("name,nranks,nsteps", [("N1", 4, 3), ("N2", 8, 3)])
 def test_nonhydrostatic_plans_match(name, nranks, nsteps):
     """NH: the day-alarm all-reduce, the acoustic sub-step exchanges and the 6-deep estore halo

@@ -342,6 +342,28 @@ def test_fortran_host_hydrostatic(c1_data):
 
 
 @pytest.mark.gpu
+def test_fortran_host_three_modes_fourteen_levels():
+    """nsplit = 3 at kz = 14 on C1 cut to 37 x 29: the [MAXSPLIT][MAXKZ] arrays of the config (zmatx,
+    zmatxr, am, tau, varpa1) with a third row and rows shorter than C1's pass through the shim's bind(c)
+    type, and DSTOR / HSTOR travel with three levels.  tend + bdyval, then rcmdyn_step; the state, bit for
+    bit, with the third mode's level of DSTOR and HSTOR non-zero."""
+    from tests.support import case
+    rc, data, st = case("C", kz=14, nsplit=3)
+    cfg = build_config(rc, data["split"])
+    assert cfg.kz == 14 and cfg.nsplit == 3 and cfg.zmatx[2][13] != 0.0 and cfg.zmatx[3][0] == 0.0
+    s = Script(cfg)
+    _start(s, rc, st).add(TEND).add(BDYVAL).add(STEP, 2).add(GET_TIME)
+    _gets(s, rc, STATE_FIELDS)
+    s.add(DESTROY)
+    py, fo = s.run_python(), s.run_fortran()
+    assert_same(py, fo)
+    assert py[0][0] == 3
+    for name in ("DSTOR", "HSTOR"):
+        a = py[1 + STATE_FIELDS.index(name)]
+        assert a.shape[0] == 3 and all(a[l].any() for l in range(3)), name
+
+
+@pytest.mark.gpu
 def test_fortran_host_step_ms(c1_data):
     """rcmdyn_last_step_ms reads back through the shim (a timing, so only its range is checked)."""
     rc, data = c1_data

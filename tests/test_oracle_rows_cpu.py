@@ -417,8 +417,9 @@ def _splitf_np(g, cfg, s, msfx, msfd):
     return out
 
 
-@pytest.mark.parametrize("variant", [{}, {"band": True}, {"nsplit": 3}, {"nsplit": 1}],
-                         ids=["lam", "band", "nsplit3", "nsplit1"])
+@pytest.mark.parametrize("variant", [{}, {"band": True}, {"nsplit": 3}, {"nsplit": 1}, {"nsplit": 4}, {"kz": 14},
+                                     {"kz": 41, "nsplit": 3}, {"band": True, "nsplit": 3}],
+                         ids=["lam", "band", "nsplit3", "nsplit1", "nsplit4", "kz14", "kz41-nsplit3", "band-nsplit3"])
 def test_splitf_spstep_match_numpy_restatement(variant):
     """From the state at splitf's entry (probe 2), the NumPy splitf/spstep gives the state the
     whole tend leaves (p*, t, u, v corrected; dstor, hstor; psdota) bit for bit."""
