@@ -637,6 +637,70 @@ int rcmdyn_output_atm(rcmdyn_t* h, uint32_t mask);
 int rcmdyn_get_output(rcmdyn_t* h, int32_t field, void* dst,
                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
 
+/* Device output stream of the tracers: the fields of the CHE file that the dyn core owns
+ * (fill_chem_outvars, Main/chemlib/mod_che_output.F90), formed on the device per tracer, written
+ * compact over each tile's own jci1:jci2 x ici1:ici2 in fp64 or fp32 and handed to the host without
+ * stalling later steps.  Off by default and outside the captured step: with the stage off no launch
+ * of it is issued.  The fp32 form is one (float) rounding of the finished fp64 value.  The lines
+ * cited define each field (idynamic 1 and 2, the idynamic /= 3 branch):
+ *   CHE_MIXRAT  :74-79    chia(j,i,k,itr) / cpsb(j,i), kz levels; cpsb is sfs%psb
+ *               (Main/mod_che_interface.F90:128); a division, not a product with a reciprocal
+ *   CHE_BURDEN  :81-83    dtrace(j,i,itr) * 1.0e6, 2-D; dtrace is Main/chemlib/mod_che_tend.F90:561-571:
+ *               from zero, over k = 1 .. kz in that order, dtrace + chib3d * cdzq * crhob3d (left to
+ *               right, no contraction).  cdzq is atms%dzq: mkslice's on the hydrostatic core
+ *               (ATMS_DZQ), the constant atm0%dzf = atm0%zf(k) - atm0%zf(k+1) on the NH core
+ *               (Main/mod_atm_interface.F90:977, Main/mod_params.F90:2636; from ATM0_ZF)
+ *   CHE_ADVH, CHE_ADVV, CHE_BDY, CHE_DIFH, CHE_CONV  :131-158, 178-184  the accumulator of the same
+ *               name of enum rcmdyn_tracer_diag divided by cpsb, kz levels.  CHE_CONV is the
+ *               device's share (cumtran): the host adds its cumulus scheme's share itself.
+ * Leftover field.  The reference forms dtrace inside the last tend's physics call, so CHE_BURDEN
+ * is served from the mkslice export of the last rcmdyn_tend_pre_physics (TR_CHIB3D, ATMS_DZQ,
+ * ATMS_RHOB3D) and is refused with the slice fields' 'no slice fields yet' message until then.
+ * The five budget fields are refused by name while the tracer budget is off.
+ * Read-and-zero.  fill_chem_outvars zeroes every c*diag(:,:,:,itr) whenever ichdiag > 0, whether
+ * or not the variable is written: with the tracer budget on, rcmdyn_output_che zeroes all five sums
+ * of every tracer in itr1..itr2 in the kernel pass that reads them, whatever the mask.  The sums of
+ * the tracers outside the range are untouched.  The pass sits on the compute stream in issue order:
+ * steps issued afterwards accumulate from zero.  With the budget off nothing is zeroed.
+ *
+ * rcmdyn_set_output_che: prec is 4 (float) or 8 (double); nbatch (1 .. ntr) is the largest number
+ * of tracers one rcmdyn_output_che takes and sizes the buffers: two sets of a compact device
+ * buffer and a pinned host buffer per tile, each with room for all RCMDYN_NCHE fields of nbatch
+ * tracers.  Refused, with the switch as it was, without tracers and for a prec or nbatch out of
+ * range.  A switch or a changed prec / nbatch forgets both snapshots; switching off frees the
+ * buffers; rcmdyn_set_tracers with another count switches the stage off and frees them.  The step
+ * graphs are not touched.
+ * rcmdyn_output_che: mask has bit (1 << field) set for every requested field; the tracers are
+ * itr1 .. itr2 (from 1), at most nbatch of them.  Settles a lazy tend, forms the fields in one
+ * launch per tile on the compute stream into the buffer set that is not the previous call's, and
+ * starts its device -> pinned copy, with the step's sticky error flags of that moment, on a copy
+ * stream behind an event; returns without waiting.  A call waits only for the copy issued two
+ * calls back, so the host can issue batch b + 1 before it fetches and writes batch b
+ * (Main/mod_output.F90:1379-1382 writes the record one tracer at a time).  No exchange: every
+ * input is read at the thread's own point; every rank owns its tiles.  Refused, with nothing
+ * launched and nothing zeroed, while the stage is off, for an empty mask or an unknown bit, for
+ * itr1 < 1, itr2 > ntr, itr1 > itr2 or more than nbatch tracers, and for a field that is refused
+ * (above).
+ * rcmdyn_get_output_che: one field of one tracer into dst (floats or doubles by prec), layout and
+ * global bounds as in rcmdyn_get (CHE_BURDEN with k1 = k2 = 1); only the interior cross points of
+ * the owned tiles that lie in the box are written.  Serves the newer of the two held snapshots
+ * that holds itr with field in its mask and waits for that snapshot's copy only, never for steps
+ * issued after it; a failure of a step issued before it is reported as rcmdyn_get does.  Refused
+ * for a field or tracer that neither held snapshot has.
+ * The copy stream is the stage's own, not rcmdyn_output_atm's, so a long CHE batch does not hold
+ * back a short ATM record.  The two stages cannot wait on each other: each copy stream waits only
+ * for an event recorded on the compute stream, the compute stream waits for neither copy stream,
+ * and the host waits only for copy events that are already recorded. */
+enum rcmdyn_che_field {
+  RCMDYN_CHE_MIXRAT = 0, RCMDYN_CHE_BURDEN, RCMDYN_CHE_ADVH, RCMDYN_CHE_ADVV, RCMDYN_CHE_BDY, RCMDYN_CHE_DIFH,
+  RCMDYN_CHE_CONV,
+  RCMDYN_NCHE
+};
+int rcmdyn_set_output_che(rcmdyn_t* h, int32_t on, int32_t prec, int32_t nbatch);
+int rcmdyn_output_che(rcmdyn_t* h, uint32_t mask, int32_t itr1, int32_t itr2);
+int rcmdyn_get_output_che(rcmdyn_t* h, int32_t field, int32_t itr, void* dst,
+                          int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+
 /* Per-kernel device time (measurement hook, mirrors rocprofv3 --kernel-trace --stats):
  * runs nsteps steps (tend + bdyval, eagerly, no graph) with a HIP event pair around every
  * kernel launch on the engine's stream.  For each distinct kernel (at most cap) fills

@@ -121,6 +121,10 @@ OUTPUT_FIELDS = ["PS", "PS_PA", "T", "U", "V", "W", "PP", "QV", "QC", "QI", "QR"
                  "UA100", "VA100", "RH", "PF", "ZF", "OMEGA"]
 OUTPUT_FIELD = {n: i for i, n in enumerate(OUTPUT_FIELDS)}
 OUTPUT_2D = {"PS", "PS_PA", "UA100", "VA100"}
+# enum rcmdyn_che_field: the tracers' output stream (the CHE file's variables the dyn core owns), per
+# tracer; BURDEN is 2-D, the last five are TRACER_DIAG_TERMS over p*
+CHE_FIELDS = ["MIXRAT", "BURDEN", "ADVH", "ADVV", "BDY", "DIFH", "CONV"]
+CHE_FIELD = {n: i for i, n in enumerate(CHE_FIELDS)}
 TWO_D = {"PSA", "PSB", "MSFX", "MSFD", "CORIOL", "HT", "XPSB_B0", "XPSB_BT", "PSC",
          "PTEN", "PSDOTA", "ATM0_PS", "DPSDXM", "DPSDYM", "EF", "DDX", "DDY", "DMDX", "DMDY",
          "EX", "CRX", "CRY", "ATMS_PS2D", "ATMS_RHOX2D", "XPSB_B1", "ATM0_PSDOT", "KPBL"}

@@ -35,6 +35,7 @@
 #include "fieldtab.hpp"
 #include "massck.hpp"
 #include "output.hpp"
+#include "che_output.hpp"
 #include "optset.hpp"
 #include "window.hpp"
 #include "pointops.hpp"   // the policies OptDefault / OptGeneric the tendency kernels are instantiated on
@@ -967,6 +968,7 @@ struct rcmdyn_engine {
     if (hgerr) (void)hipHostFree(hgerr);
     if (derr) (void)hipFree(derr);
     free_tracers();
+    che_destroy();
     for (auto& t : tiles)
       for (void* p : t.allocs) (void)hipFree(p);
     tiles.clear();
@@ -1709,6 +1711,7 @@ struct rcmdyn_engine {
       }
   }
   void free_tracers() {
+    che_free();                                      // the CHE output stage goes with its tracers
     for (auto& t : tiles) {
       for (void* p : t.tr_allocs) (void)hipFree(p);
       t.tr_allocs.clear();
@@ -1948,6 +1951,190 @@ struct rcmdyn_engine {
       for (double* d : t.trbud) HIPCHK(hipMemset(d, 0, (size_t)t.g.plane * cfg.kz * sizeof(double)));
   }
   TrBudget trbud_args(const Tile& t) const { return TrBudget{t.trbudtab, trb_rw, ntr}; }
+
+  // ------------------------------------------------------------------ CHE output stream
+  // The tracer fields of the CHE file that the dyn core owns (che_output.hip), off by default and
+  // outside the captured step.  rcmdyn_output_che forms the requested fields of a batch of tracers
+  // on the compute stream into one of two buffer sets (a compact device buffer and its pinned twin
+  // per tile) and copies it on the stage's copy stream behind an event, with the step's sticky
+  // error flags of that moment; the sets alternate, so a call waits only for the copy issued two
+  // calls back, and rcmdyn_get_output_che waits for the copy of the snapshot it serves alone.  The
+  // stream is the stage's own: a CHE batch is many times an ATM record, which would queue behind it
+  // on rcmdyn_output_atm's.  Neither stage can wait on the other: a copy stream waits only for an
+  // event recorded on the compute stream, the compute stream for no copy stream, the host for copy
+  // events already recorded.  The buffers are freed with the tracers and at a switch-off.
+  struct CheSlot {
+    hipEvent_t ev_out = nullptr, ev_copied = nullptr;
+    StepState* flags = nullptr;       // pinned: the device clock and flags at the snapshot
+    std::vector<void*> dev, host;     // per tile
+    uint32_t mask = 0;                // the fields of the snapshot (0: none)
+    int itr1 = 0, itr2 = 0;           // its tracers
+    long long lcount = 0;             // its clock
+    unsigned long seq = 0;            // its place in the order of the calls
+  };
+  bool cheon = false;
+  int che_prec = 8, che_nbatch = 0;
+  unsigned long che_seq = 0;
+  hipStream_t cstream = nullptr;
+  CheSlot che[2];
+  static constexpr const char* CHE_NAME[RCMDYN_NCHE] = {"CHE_MIXRAT", "CHE_BURDEN", "CHE_ADVH", "CHE_ADVV",
+                                                        "CHE_BDY",    "CHE_DIFH",   "CHE_CONV"};
+  // elements one tracer of a snapshot with this mask takes on a tile, and where field f starts in them
+  size_t che_stride(const Geom& g, uint32_t mask, int upto = RCMDYN_NCHE) const {
+    size_t n = 0;
+    if (g.jci2 < g.jci1 || g.ici2 < g.ici1) return n;
+    for (int f = 0; f < upto; f++)
+      if ((mask >> f) & 1u) n += out_cells(g) * che_levels(f, cfg.kz);
+    return n;
+  }
+  void che_free() {
+    for (CheSlot& s : che) {
+      if (s.ev_copied) (void)hipEventSynchronize(s.ev_copied);
+      for (void* p : s.dev) (void)hipFree(p);
+      for (void* p : s.host) (void)hipHostFree(p);
+      s.dev.clear(); s.host.clear();
+      s.mask = 0;
+    }
+    cheon = false;
+  }
+  void che_destroy() {
+    che_free();
+    if (!cstream) return;
+    (void)hipStreamSynchronize(cstream);
+    for (CheSlot& s : che) {
+      (void)hipEventDestroy(s.ev_out);
+      (void)hipEventDestroy(s.ev_copied);
+      (void)hipHostFree(s.flags);
+      s = CheSlot{};
+    }
+    (void)hipStreamDestroy(cstream);
+    cstream = nullptr;
+  }
+  void set_output_che(int on, int prec, int nbatch) {
+    if (on) {
+      if (ntr == 0) throw std::runtime_error("rcmdyn_set_output_che: no tracers are declared (rcmdyn_set_tracers)");
+      if (prec != 4 && prec != 8)
+        throw std::runtime_error("rcmdyn_set_output_che: prec = " + std::to_string(prec) + " is neither 4 (float) nor 8 (double)");
+      if (nbatch < 1 || nbatch > ntr)
+        throw std::runtime_error("rcmdyn_set_output_che: nbatch = " + std::to_string(nbatch) + " must lie in 1 .. ntr = " +
+                                 std::to_string(ntr));
+      if (cheon && prec == che_prec && nbatch == che_nbatch) return;      // the same switch: the snapshots are kept
+    }
+    che_free();                       // waits for both copies; both snapshots are forgotten
+    if (!on) return;
+    if (!cstream) {
+      HIPCHK(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
+      for (CheSlot& s : che) {
+        HIPCHK(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&s.ev_copied, hipEventDisableTiming));
+        HIPCHK(hipHostMalloc((void**)&s.flags, sizeof(StepState), hipHostMallocDefault));
+        std::memset(s.flags, 0, sizeof(StepState));
+      }
+    }
+    try {
+      // room for every field of nbatch tracers: one plane and RCMDYN_NCHE - 1 fields of kz levels
+      for (CheSlot& s : che)
+        for (auto& t : tiles) {
+          const size_t bytes = std::max<size_t>(che_stride(t.g, (1u << RCMDYN_NCHE) - 1) * nbatch * prec, 8);
+          void *d = nullptr, *p = nullptr;
+          HIPCHK(hipMalloc(&d, bytes));
+          s.dev.push_back(d);
+          HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+          s.host.push_back(p);
+        }
+    } catch (...) {
+      che_free();
+      throw;
+    }
+    cheon = true;
+    che_prec = prec;
+    che_nbatch = nbatch;
+  }
+  void output_che(uint32_t mask, int itr1, int itr2) {
+    if (!cheon) throw std::runtime_error("rcmdyn_output_che: the CHE output stage is off (rcmdyn_set_output_che)");
+    if (mask == 0) throw std::runtime_error("rcmdyn_output_che: mask = 0 names no field");
+    if (mask >> RCMDYN_NCHE)
+      throw std::runtime_error("rcmdyn_output_che: mask = " + std::to_string(mask) + " has a bit beyond the last field (" +
+                               std::to_string(RCMDYN_NCHE - 1) + ")");
+    if (itr1 < 1 || itr2 > ntr || itr1 > itr2)
+      throw std::runtime_error("rcmdyn_output_che: itr1 = " + std::to_string(itr1) + ", itr2 = " + std::to_string(itr2) +
+                               " must satisfy 1 <= itr1 <= itr2 <= ntr = " + std::to_string(ntr));
+    if (itr2 - itr1 + 1 > che_nbatch)
+      throw std::runtime_error("rcmdyn_output_che: itr1 .. itr2 holds " + std::to_string(itr2 - itr1 + 1) +
+                               " tracers, more than nbatch = " + std::to_string(che_nbatch) + " (rcmdyn_set_output_che)");
+    for (int f = RCMDYN_CHE_ADVH; f < RCMDYN_NCHE; f++)
+      if (((mask >> f) & 1u) && !trbudget)
+        throw std::runtime_error(std::string("rcmdyn_output_che: ") + CHE_NAME[f] +
+                                 ": the tracer budget is off (rcmdyn_set_tracer_budget)");
+    const bool burden = (mask >> RCMDYN_CHE_BURDEN) & 1u;
+    if (burden && !tiles.empty() && !(have(fieldtab::SLICE) && tiles[0].trs3d[0]))
+      throw std::runtime_error(std::string("rcmdyn_output_che: CHE_BURDEN: ") + WAITS_FOR[fieldtab::SLICE]);
+    settle();                         // a lazy tend replays its graph first
+    CheSlot& s = che[che_seq & 1];
+    HIPCHK(hipEventSynchronize(s.ev_copied));      // the copy issued two calls back leaves the set first
+    s.mask = 0;
+    const int nb = itr2 - itr1 + 1;
+    const bool nh = cfg.idynamic == 2;
+    each([&](Tile& t) {
+      const Geom& g = t.g;
+      if (g.jci2 < g.jci1 || g.ici2 < g.ici1) return;
+      const size_t ti = &t - tiles.data();
+      CheArgs a{};
+      for (int f = 0; f < RCMDYN_NCHE; f++) a.off[f] = (long)che_stride(g, mask, f);
+      a.stride = (long)che_stride(g, mask);
+      a.psb = t.psb_[t.cur];
+      a.tab = tr_args(t).tab;
+      a.acc = trbudget ? t.trbudtab : nullptr;
+      if (burden) {
+        a.chib3d = t.trsout;
+        a.rhob3d = t.atms[RCMDYN_ATMS_RHOB3D - RCMDYN_ATMS_UBX3D];
+        if (nh) a.zf0 = nhf[ti].zf0;
+        else a.dzq = t.atms[RCMDYN_ATMS_DZQ - RCMDYN_ATMS_UBX3D];
+      }
+      a.out = s.dev[ti];
+      a.mask = mask; a.itr0 = itr1 - 1; a.nb = nb; a.ntr = ntr;
+      const dim3 grid = grid3(g.jci2 - g.jci1 + 1, g.ici2 - g.ici1 + 1, cfg.kz * nb);
+      if (che_prec == 4) KLAUNCH(k_output_che<float>, grid, BLK, 0, stream, g, cfg.kz, a);
+      else KLAUNCH(k_output_che<double>, grid, BLK, 0, stream, g, cfg.kz, a);
+    });
+    HIPCHK(hipEventRecord(s.ev_out, stream));
+    HIPCHK(hipStreamWaitEvent(cstream, s.ev_out, 0));
+    for (size_t ti = 0; ti < tiles.size(); ti++) {
+      const size_t n = che_stride(tiles[ti].g, mask) * nb;
+      if (n) HIPCHK(hipMemcpyAsync(s.host[ti], s.dev[ti], n * (size_t)che_prec, hipMemcpyDeviceToHost, cstream));
+    }
+    HIPCHK(hipMemcpyAsync(s.flags, ds, sizeof(StepState), hipMemcpyDeviceToHost, cstream));
+    HIPCHK(hipEventRecord(s.ev_copied, cstream));
+    s.mask = mask; s.itr1 = itr1; s.itr2 = itr2;
+    s.lcount = hs.lcount;
+    s.seq = ++che_seq;
+  }
+  void get_output_che(int f, int itr, void* dst, const Box& b) {
+    if (!cheon) throw std::runtime_error("rcmdyn_get_output_che: the CHE output stage is off (rcmdyn_set_output_che)");
+    if (f < 0 || f >= RCMDYN_NCHE) throw std::runtime_error("rcmdyn_get_output_che: unknown field " + std::to_string(f));
+    CheSlot* s = nullptr;
+    for (CheSlot& c : che)
+      if (((c.mask >> f) & 1u) && itr >= c.itr1 && itr <= c.itr2 && (!s || c.seq > s->seq)) s = &c;
+    if (!s)
+      throw std::runtime_error(std::string("rcmdyn_get_output_che: ") + CHE_NAME[f] + " of tracer " + std::to_string(itr) +
+                               " is in neither of the two held snapshots of rcmdyn_output_che");
+    HIPCHK(hipEventSynchronize(s->ev_copied));
+    // the steps issued before the snapshot: their sticky flags travelled with it
+    if (s->flags->nanflag || s->flags->slflag) {
+      const int sl = s->flags->slflag;
+      const long long lc = s->lcount;
+      for (CheSlot& c : che) c.mask = 0;
+      fail(sl, lc, "by step ");
+    }
+    for (size_t ti = 0; ti < tiles.size(); ti++) {
+      const Geom& g = tiles[ti].g;
+      const int ncj = g.jci2 - g.jci1 + 1, nci = g.ici2 - g.ici1 + 1;
+      const long off = (long)(che_stride(g, s->mask) * (size_t)(itr - s->itr1) + che_stride(g, s->mask, f));
+      const Staging st{g.jci1, g.ici1, ncj, nci, ncj, (long)ncj * nci, che_levels(f, cfg.kz), off};
+      if (che_prec == 4) gather((float*)dst, b, (const float*)s->host[ti], st, g.jci1, g.jci2, g.ici1, g.ici2);
+      else gather((double*)dst, b, (const double*)s->host[ti], st, g.jci1, g.jci2, g.ici1, g.ici2);
+    }
+  }
 
   // tend's tracer launches after the forecast's exchange: the fix and filter, the serial chains,
   // then (cumtran on) the cumulus mixing of the filtered levels, ahead of the step's clock advance
@@ -3880,6 +4067,17 @@ int rcmdyn_output_atm(rcmdyn_t* h, uint32_t mask) { return guard(h, [&] { h->out
 int rcmdyn_get_output(rcmdyn_t* h, int32_t field, void* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1,
                       int32_t k2) {
   return guard(h, [&] { h->get_output(field, dst, Box{j1, j2, i1, i2, k1, k2}); });
+}
+
+int rcmdyn_set_output_che(rcmdyn_t* h, int32_t on, int32_t prec, int32_t nbatch) {
+  return guard(h, [&] { h->set_output_che(on, prec, nbatch); });
+}
+int rcmdyn_output_che(rcmdyn_t* h, uint32_t mask, int32_t itr1, int32_t itr2) {
+  return guard(h, [&] { h->output_che(mask, itr1, itr2); });
+}
+int rcmdyn_get_output_che(rcmdyn_t* h, int32_t field, int32_t itr, void* dst, int32_t j1, int32_t j2, int32_t i1,
+                          int32_t i2, int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_output_che(field, itr, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
 
 int rcmdyn_kernel_times(rcmdyn_t* h, int32_t nsteps, int32_t cap, char* names, int32_t* launches, double* avg_ms,

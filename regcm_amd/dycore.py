@@ -17,7 +17,7 @@ from typing import Optional
 
 import numpy as np
 
-from .config import CUMTRAN_FIELD, FIELD, OUTPUT_2D, OUTPUT_FIELD, OUTPUT_FIELDS, TRACER_DIAG_TERM, TRACER_FIELD, RcmdynConfig, build_config, field_levels
+from .config import CHE_FIELD, CUMTRAN_FIELD, FIELD, OUTPUT_2D, OUTPUT_FIELD, OUTPUT_FIELDS, TRACER_DIAG_TERM, TRACER_FIELD, RcmdynConfig, build_config, field_levels
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RCMDYN_LIB selects an instrumented build (tools/phases.py); default: the in-tree engine
@@ -38,6 +38,7 @@ EXPORTED = [
     "rcmdyn_set_cumtran", "rcmdyn_put_cumtran", "rcmdyn_get_cumtran",
     "rcmdyn_set_tracer_budget", "rcmdyn_get_tracer_budget", "rcmdyn_reset_tracer_budget",
     "rcmdyn_set_output", "rcmdyn_output_atm", "rcmdyn_get_output",
+    "rcmdyn_set_output_che", "rcmdyn_output_che", "rcmdyn_get_output_che",
 ]
 
 # enum rcmdyn_budget_term, in order: the tendency budget of t and qv (idiag = 1)
@@ -122,6 +123,9 @@ def lib():
     L.rcmdyn_set_output.argtypes = [P, i32, i32]
     L.rcmdyn_output_atm.argtypes = [P, ctypes.c_uint32]
     L.rcmdyn_get_output.argtypes = [P, i32, ctypes.c_void_p, *BOX]
+    L.rcmdyn_set_output_che.argtypes = [P, i32, i32, i32]
+    L.rcmdyn_output_che.argtypes = [P, ctypes.c_uint32, i32, i32]
+    L.rcmdyn_get_output_che.argtypes = [P, i32, i32, ctypes.c_void_p, *BOX]
     _lib = L
     return L
 
@@ -440,6 +444,36 @@ class DynCore:
         nk = 1 if 0 <= f < len(OUTPUT_FIELDS) and OUTPUT_FIELDS[f] in OUTPUT_2D else self.rc.kz
         return self._get_box(lib().rcmdyn_get_output, nk, f,
                              dtype=np.float32 if getattr(self, "_out_prec", 8) == 4 else np.float64)
+
+    def set_output_che(self, on: bool = True, prec: int = 8, nbatch: int = 1):
+        """The tracers' output stream (the CHE file's dyn-owned fields, formed on the device): prec as
+        in set_output; nbatch (1 .. ntr) is the largest number of tracers one output_che takes and
+        sizes the two buffer sets."""
+        self._check(lib().rcmdyn_set_output_che(self.h, 1 if on else 0, prec, nbatch))
+        if on:
+            self._che_prec = prec
+
+    def output_che(self, fields, itr1: int, itr2: int):
+        """Snapshot of the named fields (CHE_FIELDS names or numbers; or a ready bit mask as an int)
+        of the tracers itr1 .. itr2 from the state as it stands: forms them on the device and starts
+        their copy to the host; returns without waiting.  With the tracer budget on it zeroes all
+        five sums of these tracers, whatever the fields.  The engine holds the snapshots of the last
+        two calls."""
+        if isinstance(fields, int):
+            mask = fields
+        else:
+            mask = 0
+            for f in fields:
+                mask |= 1 << _number(CHE_FIELD, f)
+        self._check(lib().rcmdyn_output_che(self.h, mask, itr1, itr2))
+
+    def get_output_che(self, name, itr: int) -> np.ndarray:
+        """One field of tracer itr from the newer held snapshot that has it, as a (kz, iy, jx) array,
+        (1, iy, jx) for BURDEN, float32 or float64 by set_output_che's prec: zero outside the
+        interior cross points.  Waits for that snapshot's copy only."""
+        f = _number(CHE_FIELD, name)
+        return self._get_box(lib().rcmdyn_get_output_che, 1 if f == CHE_FIELD["BURDEN"] else self.rc.kz, f, itr,
+                             dtype=np.float32 if getattr(self, "_che_prec", 8) == 4 else np.float64)
 
     def kernel_times(self, nsteps: int, cap: int = 64) -> dict:
         """{kernel name: (launches, average ms per launch)} over nsteps eager steps."""

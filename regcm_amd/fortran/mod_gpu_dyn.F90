@@ -79,6 +79,12 @@ module mod_gpu_dyn
     out_qc = 8, out_qi = 9, out_qr = 10, out_qs = 11, out_tke = 12, out_ph = 13, out_zh = 14, &
     out_ua100 = 15, out_va100 = 16, out_rh = 17, out_pf = 18, out_zf = 19, out_omega = 20, rcmdyn_nout = 21
 
+  ! fields of the tracers' output stream (enum rcmdyn_che_field): the dyn-owned variables of the CHE
+  ! file, per tracer; rcmdyn_output_che takes ibset(0, che_x) of every requested one
+  integer(c_int32_t), parameter, public :: &
+    che_mixrat = 0, che_burden = 1, che_advh = 2, che_advv = 3, che_bdy = 4, che_difh = 5, che_conv = 6, &
+    rcmdyn_nche = 7
+
   type, bind(c), public :: rcmdyn_config
     integer(c_int32_t) :: abi_version
     integer(c_int32_t) :: jx, iy, kz
@@ -416,6 +422,30 @@ module mod_gpu_dyn
       integer(c_int32_t), value :: field, j1, j2, i1, i2, k1, k2
       type(c_ptr), value :: dst
     end function
+    ! the tracers' output stream on (1) or off (0, the default); prec = 4: the host gets reals of 4
+    ! bytes, prec = 8: of 8; nbatch (1 .. ntr): the most tracers one rcmdyn_output_che takes
+    integer(c_int) function rcmdyn_set_output_che(h, on, prec, nbatch) bind(c, name='rcmdyn_set_output_che')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on, prec, nbatch
+    end function
+    ! forms the fields of mask (bit che_x per field) of the tracers itr1 .. itr2 from the state as it
+    ! stands and starts their copy to the host; does not wait.  With the tracer budget on it zeroes
+    ! the five sums of these tracers.  The engine holds the snapshots of the last two calls.
+    integer(c_int) function rcmdyn_output_che(h, mask, itr1, itr2) bind(c, name='rcmdyn_output_che')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: mask, itr1, itr2
+    end function
+    ! one field (che_mixrat .. che_conv) of tracer itr from the newer held snapshot that has it into
+    ! dst(j1:j2,i1:i2,k1:k2), an array of real(c_float) or real(c_double) by prec, passed as c_loc(dst)
+    integer(c_int) function rcmdyn_get_output_che(h, field, itr, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_output_che')
+      import :: c_int, c_ptr, c_int32_t
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: field, itr, j1, j2, i1, i2, k1, k2
+      type(c_ptr), value :: dst
+    end function
     ! per-kernel device time over nsteps eager steps (names: 48 characters per kernel)
     integer(c_int) function rcmdyn_kernel_times(h, nsteps, cap, names, launches, avg_ms, count) &
         bind(c, name='rcmdyn_kernel_times')
@@ -441,6 +471,7 @@ module mod_gpu_dyn
   public :: rcmdyn_set_cumtran, rcmdyn_put_cumtran, rcmdyn_get_cumtran
   public :: rcmdyn_set_tracer_budget, rcmdyn_get_tracer_budget, rcmdyn_reset_tracer_budget
   public :: rcmdyn_set_output, rcmdyn_output_atm, rcmdyn_get_output
+  public :: rcmdyn_set_output_che, rcmdyn_output_che, rcmdyn_get_output_che
   public :: rcmdyn_comm_unique_id, gpu_dyn_check, gpu_put3d, gpu_get3d, gpu_put2d, gpu_get2d
 
   contains

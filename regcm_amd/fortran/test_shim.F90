@@ -3,7 +3,7 @@
 ! tests/test_fortran_shim.py).  It runs a script of C-ABI calls that the test writes, the
 ! calls a RegCM host makes around the dyn step (Main/mod_regcm_interface.F90:150-228:
 ! the state put, the init bdyval, nsteps x (tend + bdyval) or the physics split of tend,
-! bdyin after read_icbc, the 3-hourly sums, restarts, the mass check's log, the output stream), and writes every
+! bdyin after read_icbc, the 3-hourly sums, restarts, the mass check's log, the output streams), and writes every
 ! result it reads back to a stream file, so the test can compare it with the Python host running
 ! the same script.
 !
@@ -31,7 +31,8 @@ program test_shim
   integer(c_int64_t), allocatable :: plan(:)
   integer(c_int32_t), allocatable :: launches(:), shares(:)
   real(c_double), allocatable :: avg(:)
-  real(c_double) :: dt, xbc
+  real(c_double) :: dt, xbc, rw, cfd
+  integer(c_int32_t) :: itr
   logical :: soft
 
   call get_command_argument(1, fin)
@@ -215,6 +216,45 @@ program test_shim
         allocate(o8(j1:j2,i1:i2,k1:k2))
         o8 = 0.0_c_double
         ierr = rcmdyn_get_output(h, fid, c_loc(o8), j1, j2, i1, i2, k1, k2)
+        if ( ierr == 0 ) write(11) o8
+        deallocate(o8)
+      end if
+    case ( 31 )
+      ! n chemical tracers (m: ichebdy)
+      read(10) n, m
+      ierr = rcmdyn_set_tracers(h, n, m)
+    case ( 32 )
+      ! one field of tracer itr from a3(j1:j2,i1:i2,k1:k2)
+      read(10) fid, itr, j1, j2, i1, i2, k1, k2
+      allocate(a3(j1:j2,i1:i2,k1:k2))
+      read(10) a3
+      ierr = rcmdyn_put_tracer(h, fid, itr, a3, j1, j2, i1, i2, k1, k2)
+      deallocate(a3)
+    case ( 33 )
+      ! the tracer budget on / off with its two factors
+      read(10) n, rw, cfd
+      ierr = rcmdyn_set_tracer_budget(h, n, rw, cfd)
+    case ( 34 )
+      ! the tracers' output stream on / off: reals of m bytes, batches of k1 tracers
+      read(10) n, m, k1
+      ierr = rcmdyn_set_output_che(h, n, m, k1)
+    case ( 35 )
+      ! a snapshot of the fields of the mask for the tracers j1 .. j2
+      read(10) n, j1, j2
+      ierr = rcmdyn_output_che(h, n, j1, j2)
+    case ( 36 )
+      ! one field of tracer itr into o4 / o8(j1:j2,i1:i2,k1:k2), by the size m of its reals
+      read(10) fid, itr, m, j1, j2, i1, i2, k1, k2
+      if ( m == 4 ) then
+        allocate(o4(j1:j2,i1:i2,k1:k2))
+        o4 = 0.0_c_float
+        ierr = rcmdyn_get_output_che(h, fid, itr, c_loc(o4), j1, j2, i1, i2, k1, k2)
+        if ( ierr == 0 ) write(11) o4
+        deallocate(o4)
+      else
+        allocate(o8(j1:j2,i1:i2,k1:k2))
+        o8 = 0.0_c_double
+        ierr = rcmdyn_get_output_che(h, fid, itr, c_loc(o8), j1, j2, i1, i2, k1, k2)
         if ( ierr == 0 ) write(11) o8
         deallocate(o8)
       end if
