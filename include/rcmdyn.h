@@ -459,6 +459,67 @@ int rcmdyn_put_rh0adj(rcmdyn_t* h, const double* src,
 int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst,
                       int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
 
+/* SUBEX on the device (ipptls = 1): cldfrac with subex_cldfrac (Main/mod_micro_interface.F90:
+ * 211-362, Main/cloudlib/mod_cloud_subex.F90:46-107) and the rain columns of subex (Main/microlib/
+ * mod_micro_subex.F90:99-393), off by default.  When on, the engine forms the large-scale cloud
+ * fraction fcc, the cloud fraction and in-cloud liquid water merged with cucloud's, rh0adj, and the
+ * autoconversion / accretion / evaporation of rain from the top level down, from the mkslice
+ * export of the same tend (tb3d, pb3d, pf3d, qxb3d qv / qc, rhob3d, rhb3d) and p*b.  The rain
+ * columns' coupled increments of t, qv, qc (LSC_T, LSC_QV, LSC_QC: the text's update of a zero
+ * tendency, the idynamic 1 / 2 form with * psb) enter the tend as pc_physic tendencies: a
+ * pointwise pass forms TPHY + LSC_T, QVPHY + LSC_QV, QCPHY + LSC_QC and the tendency kernels read
+ * those sums (the increments themselves where no *PHY was put).  The reference accumulates in
+ * place in the order its schemes run; the sum here rounds once more where the host's TPHY carries
+ * schemes from both before and after the microphysics, and has the same bits otherwise.
+ * With condtq on as well, condtq reads the device's rh0adj of the same tend: no rcmdyn_put_rh0adj
+ * is needed (it is refused, the host's values would be overwritten), and rcmdyn_get_condtq(RH0ADJ)
+ * returns the device's field.  rh0adj and the increments travel one point wide to the tiles' rings:
+ * the first tend on 2 x 2 tiles gives the bits of one tile, later steps those of the same tiles fed
+ * by the host route (tiles and one tile part at the reference's tile-dependent negative-moisture
+ * sweep, with or without subex).
+ *
+ * Whole mode: rcmdyn_tend / rcmdyn_step run the mkslice export and the subex kernels where the
+ * reference calls physical_parametrizations (after mkslice, before the tendencies), inside the
+ * replayed graphs.  Split mode: rcmdyn_tend_pre_physics, then rcmdyn_physics_subex, then
+ * rcmdyn_tend_post_physics, so the host can fetch CLDFRA / CLDLWC for its radiation in between; if
+ * the host did not call rcmdyn_physics_subex, rcmdyn_tend_post_physics runs it first.  It runs
+ * once per tend: a second call before the post phase does nothing.
+ *
+ * rcmdyn_set_subex: rhmax, rhmin (the run's clamps, rhmin < rhmax), tc0 (K), larcticcorr (0 / 1),
+ * iconvlwp (0 / 1) and rem (1: also remrat and rembc for the chemistry, the reference's ichem =
+ * 1).  icldfrac, icldmstrat and lsecind are the host's settings of options that are not built:
+ * icldfrac other than 0, icldmstrat = 1 (needs th700 and iveg) and lsecind = 1 (the aerosol second
+ * indirect effect, needs ccn) are refused by name, as is ipptls other than 1; the switch then
+ * stays as it was.  Buffers are allocated at the switch-on and freed at the switch-off; the
+ * accumulators and tables of an earlier switch-on are gone.  Waits for the device like
+ * rcmdyn_set_budget; the order of this call, rcmdyn_set_condtq and rcmdyn_set_tracers is free.
+ *
+ * Fields (enum rcmdyn_subex_field), cross points, layout and bounds as in rcmdyn_put / rcmdyn_get:
+ *   RH0, QCK1, CGUL, CEVAP, CACCR   put, 2-D: the tables of Main/mod_params.F90:2455-2480.  A run
+ *                         with subex on fails, naming the first one missing, until a put of each
+ *                         has covered every interior cross point; values must be finite
+ *   CU_CLDFRA, CU_CLDLWC  put, kz levels: cucloud's cloud fraction (finite, in [0, 1]) and liquid
+ *                         water, zero until put
+ *   RAINNC, LSMRNC        put and get, 2-D: the accumulated large-scale rain (kg/m2) and its rate
+ *                         sum; the host zeroes them by a put, as the reference does at output
+ *   FCC, CLDFRA, CLDLWC, RH0ADJ, LSC_T, LSC_QV, LSC_QC (kz levels), TRRATE (2-D)   get only
+ *   REMRAT, REMBC         get only, kz levels, with rem on
+ * Gets write the interior cross points of dst only. */
+enum rcmdyn_subex_field {
+  RCMDYN_SUBEX_RH0 = 0, RCMDYN_SUBEX_QCK1, RCMDYN_SUBEX_CGUL, RCMDYN_SUBEX_CEVAP, RCMDYN_SUBEX_CACCR,
+  RCMDYN_SUBEX_CU_CLDFRA, RCMDYN_SUBEX_CU_CLDLWC, RCMDYN_SUBEX_RAINNC, RCMDYN_SUBEX_LSMRNC,
+  RCMDYN_SUBEX_FCC, RCMDYN_SUBEX_CLDFRA, RCMDYN_SUBEX_CLDLWC, RCMDYN_SUBEX_RH0ADJ,
+  RCMDYN_SUBEX_LSC_T, RCMDYN_SUBEX_LSC_QV, RCMDYN_SUBEX_LSC_QC, RCMDYN_SUBEX_TRRATE,
+  RCMDYN_SUBEX_REMRAT, RCMDYN_SUBEX_REMBC, RCMDYN_NSUBEX
+};
+int rcmdyn_set_subex(rcmdyn_t* h, int32_t on, double rhmax, double rhmin, double tc0, int32_t larcticcorr,
+                     int32_t iconvlwp, int32_t rem, int32_t icldfrac, int32_t icldmstrat, int32_t lsecind);
+int rcmdyn_put_subex(rcmdyn_t* h, int32_t field, const double* src,
+                     int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_get_subex(rcmdyn_t* h, int32_t field, double* dst,
+                     int32_t j1, int32_t j2, int32_t i1, int32_t i2, int32_t k1, int32_t k2);
+int rcmdyn_physics_subex(rcmdyn_t* h);
+
 /* Chemical and aerosol tracers (the reference's ichem = 1): the chi chain of tend and bdyval on
  * the device.  tend decouples (atmx%chi = atm1%chi * rpsa, no floor), advects (hadvtr; vadv4d
  * with itrvadv = 2, threshold mintr * ps, or 3 under ibltyp = 2 with iuwvadv = 1), relaxes

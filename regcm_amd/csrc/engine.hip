@@ -38,6 +38,7 @@
 #include "che_output.hpp"
 #include "optset.hpp"
 #include "window.hpp"
+#include "subex.hpp"
 #include "pointops.hpp"   // the policies OptDefault / OptGeneric the tendency kernels are instantiated on
 
 using namespace rcm;
@@ -250,7 +251,9 @@ enum class FK {
   // iuwvadv = 1: the PBL-top level (2-D)
   KPBL,
   // chemical tracers (rcmdyn_set_tracers): chia, chib, the forecast, chib0, chibt of tracer XField::n
-  TRA1, TRA2, TRCQ, TRB0, TRBT
+  TRA1, TRA2, TRCQ, TRB0, TRBT,
+  // SUBEX on the device (rcmdyn_set_subex): rh0adj and the rain columns' increments for the rings
+  SBX_RH0ADJ, SBX_LSCT, SBX_LSCQV, SBX_LSCQC
 };
 inline FK fkq(FK base, int n) { return (FK)((int)base + n); }
 
@@ -403,7 +406,10 @@ struct rcmdyn_engine {
   // conf, and whether one put of the host covered rh0adj wherever condtq runs since the switch-on
   bool condtq = false, rh0_put = false;
   double ct_conf = 1.0;
-  Condtq condtq_args(const Tile& t) const { return Condtq{t.rh0adj, t.cti[0], t.cti[1], t.cti[2], ct_conf}; }
+  // with subex on as well, condtq reads the device's rh0adj of the same tend
+  Condtq condtq_args(const Tile& t) const {
+    return Condtq{subex ? t.sbx[RCMDYN_SUBEX_RH0ADJ] : t.rh0adj, t.cti[0], t.cti[1], t.cti[2], ct_conf};
+  }
   // The extra argument blocks of a tendency launch (kernels.hpp): fn(blocks...) with those that
   // are switched on, Budget before Condtq.  fn is a generic lambda that issues the launch of the
   // instance its arguments name, so a further switch is one more rung here for every kernel.
@@ -419,7 +425,7 @@ struct rcmdyn_engine {
   template <class... B>
   static const char* tend_name(const char* plain, const char* bud) { return pack_has<Budget, B...> ? bud : plain; }
   void condtq_ready(const char* who) const {
-    if (condtq && !rh0_put)
+    if (condtq && !rh0_put && !subex)
       throw std::runtime_error(std::string(who) + ": condtq is on and no rh0adj was put since that covers the tiles' interior "
                                "cross points and their rings on every level (rcmdyn_put_rh0adj)");
   }
@@ -763,7 +769,7 @@ struct rcmdyn_engine {
     f.psdotb = t.psdotb; f.qdot = t.qdot;
     f.tten = t.tten; f.qvten = t.qvten; f.qcten = t.qcten; f.uten = t.uten; f.vten = t.vten;
     f.cqv = t.cqv; f.cqc = t.cqc; f.fqv = t.fqv; f.fqc = t.fqc; f.depplane = t.depplane;
-    f.tphy = t.phy[0]; f.qvphy = t.phy[1]; f.qcphy = t.phy[2]; f.uphy = t.phy[3]; f.vphy = t.phy[4];
+    f.tphy = phy_tqc(t, 0); f.qvphy = phy_tqc(t, 1); f.qcphy = phy_tqc(t, 2); f.uphy = t.phy[3]; f.vphy = t.phy[4];
     f.ppphy = t.phy[5]; f.wphy = t.phy[6];
     f.slqv = t.slqv; f.slqc = t.slqc;
     f.d6u = t.d6[0]; f.d6v = t.d6[1]; f.d6t = t.d6[2]; f.d6qv = t.d6[3]; f.d6qc = t.d6[4];
@@ -968,6 +974,8 @@ struct rcmdyn_engine {
     if (hgerr) (void)hipHostFree(hgerr);
     if (derr) (void)hipFree(derr);
     free_tracers();
+    free_subex();
+    if (sbx_chis) (void)hipFree(sbx_chis);
     che_destroy();
     for (auto& t : tiles)
       for (void* p : t.allocs) (void)hipFree(p);
@@ -1112,6 +1120,8 @@ struct rcmdyn_engine {
       case FK::D6U: return t.d6[0]; case FK::D6V: return t.d6[1]; case FK::D6T: return t.d6[2];
       case FK::D6QV: return t.d6[3]; case FK::D6QC: return t.d6[4];
       case FK::KPBL: return t.kpbl;
+      case FK::SBX_RH0ADJ: return t.sbx[RCMDYN_SUBEX_RH0ADJ]; case FK::SBX_LSCT: return t.sbx[RCMDYN_SUBEX_LSC_T];
+      case FK::SBX_LSCQV: return t.sbx[RCMDYN_SUBEX_LSC_QV]; case FK::SBX_LSCQC: return t.sbx[RCMDYN_SUBEX_LSC_QC];
       default: break;
     }
     if (f >= FK::A1QX0 && f <= FK::D6QX2) {
@@ -1378,12 +1388,18 @@ struct rcmdyn_engine {
   }
 
   // mkslice export (slice.hip) for the host physics, run by rcmdyn_tend_pre_physics
-  void run_slice() {
+  // the export's buffers, allocated by the first slice (a capture that holds one allocates them
+  // before it begins)
+  void slice_allocs() {
     for (auto& t : tiles) {
       if (t.atms[0]) continue;
       for (int q = 0; q < fieldtab::NATMS; q++) t.atms[q] = dalloc(t, field_size(t, RCMDYN_ATMS_UBX3D + q));
       for (int n = 0; n < hc.nsp; n++) t.atmsx[n] = dalloc(t, field_size(t, RCMDYN_ATMS_QXB3D_QI + n));
     }
+    tracer_slice_allocs();
+  }
+  void run_slice() {
+    slice_allocs();
     each([&](Tile& t) {
       const Geom& g = t.g;
       const int c = t.cur;
@@ -1640,6 +1656,9 @@ struct rcmdyn_engine {
   }
   void put_rh0adj(const double* src, const Box& b) {
     if (!condtq) throw std::runtime_error("rcmdyn_put_rh0adj: condtq is off (rcmdyn_set_condtq)");
+    if (subex)
+      throw std::runtime_error("rcmdyn_put_rh0adj: subex is on (rcmdyn_set_subex): condtq reads the rh0adj the device's cldfrac "
+                               "forms in the same tend, a put would never be read");
     for (size_t q = 0, n = b.cells(); q < n; q++)
       if (!(src[q] >= 0.0) || !(src[q] <= 0.99999))
         throw std::runtime_error("rcmdyn_put_rh0adj: rh0adj must lie in [0, 0.99999]");
@@ -1666,8 +1685,191 @@ struct rcmdyn_engine {
     if (!condtq) throw std::runtime_error("rcmdyn_get_condtq: condtq is off (rcmdyn_set_condtq)");
     if (term < 0 || term >= RCMDYN_NCONDTQ) throw std::runtime_error("rcmdyn_get_condtq: unknown term");
     // the increments live on the tile's interior cross points (the ring's are its neighbours')
-    if (term == RCMDYN_CONDTQ_RH0ADJ) get_window(dst, b, cfg.kz, [](Tile& t) { return t.rh0adj; });
+    if (term == RCMDYN_CONDTQ_RH0ADJ)
+      get_window(dst, b, cfg.kz, [&](Tile& t) { return subex ? t.sbx[RCMDYN_SUBEX_RH0ADJ] : t.rh0adj; });
     else get_window(dst, b, cfg.kz, [&](Tile& t) { return t.cti[term - RCMDYN_CONDTQ_T]; }, Range::Interior);
+  }
+
+  // ------------------------------------------------------------------ SUBEX on the device
+  // cldfrac with subex_cldfrac and the rain columns of subex (rcmdyn_set_subex; subex.hpp,
+  // subex.hip) in physical_parametrizations' place: after the mkslice export of a tend and before
+  // its tendency kernels.  A whole tend runs the export and the kernels itself (captured with it); on
+  // the split path rcmdyn_physics_subex runs them between the two phases, or the post phase does
+  // first.  The kernels' increments reach the tendency kernels as the physics sums TPHY + LSC_T ..
+  // (phy_tqc), formed by a pointwise pass at the start of the post phase; the tendency kernels are
+  // the same instances either way.  The switch changes launches and kernel arguments, so the
+  // captured graphs are dropped with it.
+  bool subex = false, sbx_rem = false;
+  SubexPar sbx_par{};
+  double* sbx_chis = nullptr;                  // the chis table (device; lives with the engine)
+  bool sbx_tab_put[5] = {};                    // RH0 .. CACCR: a put covered the interior since the switch-on
+  bool sbx_pre = false, sbx_ran = false;       // the split path: the pre phase ran; the kernels ran after it
+  static constexpr const char* SBX_NAME[RCMDYN_NSUBEX] = {
+      "RH0", "QCK1", "CGUL", "CEVAP", "CACCR", "CU_CLDFRA", "CU_CLDLWC", "RAINNC", "LSMRNC", "FCC", "CLDFRA", "CLDLWC",
+      "RH0ADJ", "LSC_T", "LSC_QV", "LSC_QC", "TRRATE", "REMRAT", "REMBC"};
+  static bool sbx_2d(int f) {
+    return f <= RCMDYN_SUBEX_CACCR || f == RCMDYN_SUBEX_RAINNC || f == RCMDYN_SUBEX_LSMRNC || f == RCMDYN_SUBEX_TRRATE;
+  }
+  static bool sbx_is_rem(int f) { return f == RCMDYN_SUBEX_REMRAT || f == RCMDYN_SUBEX_REMBC; }
+  // the pc_physic tendency of t, qv or qc (q = 0, 1, 2) a tendency kernel reads: the host's, or with
+  // subex on its sum with the rain columns' increment, or that increment alone where none was put
+  double* phy_tqc(const Tile& t, int q) const {
+    if (!subex) return t.phy[q];
+    return t.phy[q] ? t.sbx_sum[q] : t.sbx[RCMDYN_SUBEX_LSC_T + q];
+  }
+  void free_subex() {
+    for (auto& t : tiles) {
+      for (void* p : t.sbx_allocs) (void)hipFree(p);
+      t.sbx_allocs.clear();
+      for (double*& d : t.sbx) d = nullptr;
+      for (double*& d : t.sbx_sum) d = nullptr;
+      t.sbx_dqc = nullptr;
+    }
+  }
+  void set_subex(int on, double rhmax, double rhmin, double tc0, int larcticcorr, int iconvlwp, int rem, int icldfrac,
+                 int icldmstrat, int lsecind) {
+    if (on) {
+      const std::string w = "rcmdyn_set_subex: ";
+      if (cfg.ipptls != 1)
+        throw std::runtime_error(w + "ipptls = " + std::to_string(cfg.ipptls) + ": subex is the scheme of ipptls = 1 alone");
+      if (icldfrac != 0)
+        throw std::runtime_error(w + "icldfrac = " + std::to_string(icldfrac) + " is not built (subex_cldfrac, icldfrac = 0, alone)");
+      if (icldmstrat != 0)
+        throw std::runtime_error(w + "icldmstrat = 1 is not built (the marine stratocumulus term needs th700 and iveg)");
+      if (lsecind != 0)
+        throw std::runtime_error(w + "lsecind is not built (the aerosol second indirect effect needs ccn)");
+      if (!std::isfinite(rhmax) || !std::isfinite(rhmin) || !(rhmin >= 0.0) || !(rhmin < rhmax))
+        throw std::runtime_error(w + "rhmin and rhmax must be finite with 0 <= rhmin < rhmax");
+      if (!std::isfinite(tc0) || !(tc0 > 0.0)) throw std::runtime_error(w + "tc0 must be a finite temperature in K");
+      if ((larcticcorr | 1) != 1) throw std::runtime_error(w + "larcticcorr must be 0 or 1");
+      if ((iconvlwp | 1) != 1) throw std::runtime_error(w + "iconvlwp must be 0 or 1");
+      if ((rem | 1) != 1) throw std::runtime_error(w + "rem must be 0 or 1");
+    }
+    quiesce();                                       // a lazy tend replays its graph first
+    const bool b = on != 0;
+    if (!b && !subex) return;
+    invalidate_graphs();
+    sbx_pre = sbx_ran = false;
+    if (subex) free_subex();                         // a new switch-on starts from zeroed buffers
+    subex = b;
+    if (!b) return;
+    sbx_par = SubexPar{rhmax, rhmin, tc0, larcticcorr, iconvlwp};
+    sbx_rem = rem != 0;
+    for (bool& p : sbx_tab_put) p = false;
+    if (!sbx_chis && !dry) {
+      std::vector<double> chis(sx::NCHI);
+      for (int i = 0; i < sx::NCHI; i++) chis[i] = subex_chis(i);
+      HIPCHK(hipMalloc((void**)&sbx_chis, sizeof(double) * sx::NCHI));
+      HIPCHK(hipMemcpy(sbx_chis, chis.data(), sizeof(double) * sx::NCHI, hipMemcpyHostToDevice));
+    }
+    for (auto& t : tiles) {
+      const size_t P = t.g.plane;
+      for (int f = 0; f < RCMDYN_NSUBEX; f++)
+        if (!sbx_is_rem(f) || sbx_rem) t.sbx[f] = zalloc<double>(t.sbx_allocs, P * (sbx_2d(f) ? 1 : (size_t)cfg.kz));
+      t.sbx_dqc = zalloc<double>(t.sbx_allocs, P * cfg.kz);
+      for (double*& d : t.sbx_sum) d = zalloc<double>(t.sbx_allocs, P * cfg.kz);
+    }
+  }
+  void subex_on(const char* who) const {
+    if (!subex) throw std::runtime_error(std::string(who) + ": subex is off (rcmdyn_set_subex)");
+  }
+  // a run waits for the five tables
+  void subex_ready(const char* who) const {
+    if (!subex) return;
+    for (int f = 0; f < 5; f++)
+      if (!sbx_tab_put[f])
+        throw std::runtime_error(std::string(who) + ": subex is on and no " + SBX_NAME[f] + " was put since that covers the "
+                                 "tiles' interior cross points (rcmdyn_put_subex)");
+  }
+  void put_subex(int f, const double* src, const Box& b) {
+    subex_on("rcmdyn_put_subex");
+    if (f < 0 || f >= RCMDYN_NSUBEX) throw std::runtime_error("rcmdyn_put_subex: unknown field");
+    if (f > RCMDYN_SUBEX_LSMRNC)
+      throw std::runtime_error(std::string("rcmdyn_put_subex: ") + SBX_NAME[f] + " is read-only (the device forms it)");
+    const int nk = sbx_2d(f) ? 1 : cfg.kz;
+    const size_t n = Box{b.j1, b.j2, b.i1, b.i2, b.k1, std::max(b.k1, b.k2)}.cells();
+    for (size_t q = 0; q < n; q++) {
+      if (!std::isfinite(src[q])) throw std::runtime_error(std::string("rcmdyn_put_subex: ") + SBX_NAME[f] + " must be finite");
+      if (f == RCMDYN_SUBEX_CU_CLDFRA && (!(src[q] >= 0.0) || !(src[q] <= 1.0)))
+        throw std::runtime_error("rcmdyn_put_subex: CU_CLDFRA must lie in [0, 1]");
+    }
+    put_window(src, b, nk, [&](Tile& t) { return t.sbx[f]; });
+    if (f <= RCMDYN_SUBEX_CACCR) {
+      const Period p = period();
+      bool all = true;
+      for (const auto& t : tiles) {
+        const Geom& g = t.g;
+        for (int i = g.ici1; all && i <= g.ici2; i++)
+          for (int j = g.jci1; all && j <= g.jci2; j++)
+            if (!b.holds(p.j(j), p.i(i))) all = false;
+      }
+      if (all) sbx_tab_put[f] = true;
+    }
+  }
+  void get_subex(int f, double* dst, const Box& b) {
+    settle();
+    subex_on("rcmdyn_get_subex");
+    if (f < 0 || f >= RCMDYN_NSUBEX) throw std::runtime_error("rcmdyn_get_subex: unknown field");
+    if (f < RCMDYN_SUBEX_RAINNC)
+      throw std::runtime_error(std::string("rcmdyn_get_subex: ") + SBX_NAME[f] + " is the host's own (put only)");
+    if (sbx_is_rem(f) && !sbx_rem)
+      throw std::runtime_error(std::string("rcmdyn_get_subex: ") + SBX_NAME[f] + " needs rem = 1 (rcmdyn_set_subex)");
+    get_window(dst, b, sbx_2d(f) ? 1 : cfg.kz, [&](Tile& t) { return t.sbx[f]; }, Range::Interior);
+  }
+  // the two kernels on the mkslice export of this tend, then rh0adj and the increments one point
+  // wide to the tiles' rings: condtq and the tendency kernels of a decomposed hydrostatic step
+  // compute the ring as its owners do
+  void run_subex() {
+    each([&](Tile& t) {
+      const Geom& g = t.g;
+      SubexArgs a{};
+      a.tb = t.atms[4]; a.qv = t.atms[5]; a.qc = t.atms[6]; a.pb = t.atms[8]; a.pf = t.atms[9]; a.rho = t.atms[13];
+      a.rh = t.atms[21]; a.psb = t.psb_[t.cur];
+      double** s = t.sbx;
+      a.rh0 = s[RCMDYN_SUBEX_RH0]; a.qck1 = s[RCMDYN_SUBEX_QCK1]; a.cgul = s[RCMDYN_SUBEX_CGUL];
+      a.cevap = s[RCMDYN_SUBEX_CEVAP]; a.caccr = s[RCMDYN_SUBEX_CACCR];
+      a.cufra = s[RCMDYN_SUBEX_CU_CLDFRA]; a.culwc = s[RCMDYN_SUBEX_CU_CLDLWC]; a.chis = sbx_chis;
+      a.fcc = s[RCMDYN_SUBEX_FCC]; a.cldfra = s[RCMDYN_SUBEX_CLDFRA]; a.cldlwc = s[RCMDYN_SUBEX_CLDLWC];
+      a.rh0adj = s[RCMDYN_SUBEX_RH0ADJ]; a.dqc = t.sbx_dqc;
+      a.lsc_t = s[RCMDYN_SUBEX_LSC_T]; a.lsc_qv = s[RCMDYN_SUBEX_LSC_QV]; a.lsc_qc = s[RCMDYN_SUBEX_LSC_QC];
+      a.rainnc = s[RCMDYN_SUBEX_RAINNC]; a.lsmrnc = s[RCMDYN_SUBEX_LSMRNC]; a.trrate = s[RCMDYN_SUBEX_TRRATE];
+      a.remrat = s[RCMDYN_SUBEX_REMRAT]; a.rembc = s[RCMDYN_SUBEX_REMBC];
+      a.par = sbx_par; a.dtsec = cfg.dtsec;
+      const int nj = g.jci2 - g.jci1 + 1, ni = g.ici2 - g.ici1 + 1;
+      if (nj <= 0 || ni <= 0) return;
+      KLAUNCH(k_subex_point, grid3(nj, ni, cfg.kz), BLK, 0, stream, g, cfg.kz, a);
+      const size_t lds = sbx_rem ? sizeof(double) * SBX_COLW * (size_t)cfg.kz : 0;
+      KLAUNCH(k_subex_column, dim3((nj + SBX_COLW - 1) / SBX_COLW, ni), dim3(SBX_COLW), lds, stream, g, cfg.kz, ds, a);
+    });
+    xch({{FK::SBX_RH0ADJ, cfg.kz}, {FK::SBX_LSCT, cfg.kz}, {FK::SBX_LSCQV, cfg.kz}, {FK::SBX_LSCQC, cfg.kz}}, 1, 0);
+  }
+  // TPHY + LSC_T, QVPHY + LSC_QV, QCPHY + LSC_QC over the whole frame (the host put the ring too)
+  void subex_sums() {
+    each([&](Tile& t) {
+      if (!t.phy[0]) return;
+      const long n = t.g.plane * (long)cfg.kz;
+      double** s = t.sbx;
+      KLAUNCH(k_subex_sums, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, t.phy[0], t.phy[1], t.phy[2],
+              s[RCMDYN_SUBEX_LSC_T], s[RCMDYN_SUBEX_LSC_QV], s[RCMDYN_SUBEX_LSC_QC], t.sbx_sum[0], t.sbx_sum[1], t.sbx_sum[2]);
+    });
+  }
+  // between the two phases of a tend whose pre phase ran the mkslice export (tend, nh_tend)
+  void subex_mid(int phase) {
+    if (!subex) return;
+    if (phase == TEND_PRE) { sbx_pre = true; sbx_ran = false; return; }
+    if (phase == TEND_ALL || !sbx_ran) run_subex();
+    sbx_pre = sbx_ran = false;
+    subex_sums();
+  }
+  void physics_subex() {
+    subex_on("rcmdyn_physics_subex");
+    subex_ready("rcmdyn_physics_subex");
+    if (!sbx_pre)
+      throw std::runtime_error("rcmdyn_physics_subex: no rcmdyn_tend_pre_physics since the last tend (the mkslice export "
+                               "subex reads is that call's)");
+    if (sbx_ran) return;                             // once per tend
+    run_subex();
+    sbx_ran = true;
   }
 
   // ------------------------------------------------------------------ chemical tracers
@@ -1676,7 +1878,8 @@ struct rcmdyn_engine {
   // rcmdyn_config.  Its buffers are the tiles' (Tile::tra1 ..), the two relaxation tables the
   // engine's; the groups' argument tables are kernel inputs in device memory, so a put writes
   // buffers the captured graphs already point to and only a new count or a new table state (zero
-  // or not) drops the graphs (the slice runs eagerly, from rcmdyn_tend_pre_physics alone).
+  // or not) drops the graphs (the slice runs eagerly, from rcmdyn_tend_pre_physics, or with subex
+  // on inside a whole tend, whose capture allocates the chib3d buffers before it begins).
   int ntr = 0;
   bool tr_bdy_dirty = false;          // chib0 / chibt put since the last tend: their ghost rings are stale
   bool tr_relax = false;              // a cefc / cegc entry is non-zero
@@ -2160,13 +2363,16 @@ struct rcmdyn_engine {
     });
   }
   // mkslice's chib3d (run_slice)
-  void tracer_slice() {
-    if (!ntr) return;
+  void tracer_slice_allocs() {
+    if (!ntr || dry) return;
     for (auto& t : tiles) {
       if (t.trs3d[0]) continue;
       for (int q = 0; q < ntr; q++) t.trs3d[q] = tr_alloc<double>(t, (size_t)t.g.plane * cfg.kz);
       HIPCHK(hipMemcpy(t.trsout, t.trs3d.data(), sizeof(double*) * ntr, hipMemcpyHostToDevice));
     }
+  }
+  void tracer_slice() {
+    if (!ntr) return;
     each([&](Tile& t) {
       const Geom& g = t.g;
       KLAUNCH(k_tr_slice, grid3(g.jce2 - g.jce1 + 1, g.ice2 - g.ice1 + 1, ntr * cfg.kz), BLK, 0, stream, g, cfg.kz, ntr,
@@ -2723,7 +2929,7 @@ struct rcmdyn_engine {
     }
     if (cfg.ibltyp == 2) f.xkcs = t.xkcs;     // the TKE diffusion reads xkcf from it
     if (hc.iqxvadv == 3) f.kpbl = t.kpbl;    // vadv4d ind = 3 of qc
-    f.tphy = t.phy[0]; f.qvphy = t.phy[1]; f.qcphy = t.phy[2]; f.uphy = t.phy[3]; f.vphy = t.phy[4];
+    f.tphy = phy_tqc(t, 0); f.qvphy = phy_tqc(t, 1); f.qcphy = phy_tqc(t, 2); f.uphy = t.phy[3]; f.vphy = t.phy[4];
     f.red = red; f.red_off = t.red_off;
     f.qfuse = qfuse() ? 1 : 0; f.negcnt = t.negcnt; f.neglist = t.neglist;
     for (int n = 0; n < hc.nsp; n++) f.qxa1[n] = t.a1qx[n][c];
@@ -2838,6 +3044,7 @@ struct rcmdyn_engine {
     if (!ovl) xch({{FK::NCR, kz}, {FK::QDOT, kp}, {FK::NXKCR, kz}});
     if (slice) run_slice();
     }
+    subex_mid(phase);
     if (!(phase & TEND_POST)) return;
     each([&](Tile& t) {
       const Geom& g = t.g;
@@ -3054,12 +3261,14 @@ struct rcmdyn_engine {
   // tend, whole or one of its two phases (TEND_PRE, TEND_POST); corr: what the hydrostatic
   // TEND_POST does with the split corrections
   void tend(Corr corr, int phase = TEND_ALL, bool slice = false) {
+    if (subex && (phase & TEND_PRE)) slice = true;     // subex reads the export of this tend
     if (cfg.idynamic == 2) nh_tend(phase, slice);
     else {
       // part 1 of k_momentum / k_scalars beside the prologue exchange only in a whole tend (no
       // host work between) without the semi-Lagrangian pass that precedes them; a split tend
       // never runs it, so nothing is carried from one phase's call to the other's
       const bool post_inner = (phase & TEND_PRE) && tend_pre(slice, phase == TEND_ALL && !slice && cfg.isladvec != 1);
+      subex_mid(phase);
       if (phase & TEND_POST) tend_post(corr, post_inner);
     }
     // the hydrostatic step's snapshot is written by k_split_correct's clock lane
@@ -3500,11 +3709,13 @@ struct rcmdyn_engine {
     else if (sw.nh_tfuse) for (auto& t : tiles) t.tq = 1 - t.tq;
     hs.lcount += 1;
     if (hs.lcount == 2) hs.dt = 2.0 * cfg.dtsec;
+    sbx_pre = sbx_ran = false;         // a whole tend ends the split path's state, as subex_mid does eagerly
   }
   void replayed_bdyval() { hs.xbctime = hs.xbctime + cfg.dtsec; }
 
   void step(int n) {
     condtq_ready("rcmdyn_step");
+    subex_ready("rcmdyn_step");
     prepare();
     settle();
     hipEvent_t e0, e1;
@@ -3543,6 +3754,7 @@ struct rcmdyn_engine {
   // replays its own captured graph and returns without synchronising the stream
   void tend_call() {
     condtq_ready("rcmdyn_tend");
+    subex_ready("rcmdyn_tend");
     begin_tend();
     const int par = gpar();
     const Corr corr = drop_in_corr();
@@ -3573,6 +3785,9 @@ struct rcmdyn_engine {
   void tend_pre_physics() { begin_tend(); tend(Corr::Launch, TEND_PRE, true); }
   void tend_post_physics() {
     condtq_ready("rcmdyn_tend_post_physics");
+    subex_ready("rcmdyn_tend_post_physics");
+    if (subex && !sbx_pre)
+      throw std::runtime_error("rcmdyn_tend_post_physics: subex is on and no rcmdyn_tend_pre_physics ran for this tend");
     begin_tend();
     const Corr corr = drop_in_corr();
     tend(corr, TEND_POST);
@@ -3613,9 +3828,11 @@ struct rcmdyn_engine {
   void capture(Graph kind, int par) {
     const StepState save = hs;
     const Pending saved = pend;
+    const bool saved_pre = sbx_pre, saved_ran = sbx_ran;
     std::vector<int> curs, tqs;
     for (auto& t : tiles) { curs.push_back(t.cur); tqs.push_back(t.tq); }
     hipGraph_t graph;
+    if (subex) slice_allocs();        // a whole tend with subex on holds the mkslice export
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     switch (kind) {
       case Graph::Step: step_once(); break;
@@ -3630,6 +3847,7 @@ struct rcmdyn_engine {
     HIPCHK(hipGraphDestroy(graph));
     hs = save;
     pend = saved;
+    sbx_pre = saved_pre; sbx_ran = saved_ran;
     for (size_t q = 0; q < tiles.size(); q++) { tiles[q].cur = curs[q]; tiles[q].tq = tqs[q]; }
   }
   void ensure(Graph kind, int par) { if (!graphs[(int)kind][par]) capture(kind, par); }
@@ -3658,6 +3876,7 @@ struct rcmdyn_engine {
 
   void kernel_times(int nsteps, int cap, char* names, int32_t* launches, double* avg, int32_t* count) {
     condtq_ready("rcmdyn_kernel_times");
+    subex_ready("rcmdyn_kernel_times");
     prepare();
     quiesce();
     KernelProf kp;
@@ -4014,6 +4233,23 @@ int rcmdyn_get_condtq(rcmdyn_t* h, int32_t term, double* dst, int32_t j1, int32_
                       int32_t k1, int32_t k2) {
   return guard(h, [&] { h->get_condtq(term, dst, Box{j1, j2, i1, i2, k1, k2}); });
 }
+
+int rcmdyn_set_subex(rcmdyn_t* h, int32_t on, double rhmax, double rhmin, double tc0, int32_t larcticcorr, int32_t iconvlwp,
+                     int32_t rem, int32_t icldfrac, int32_t icldmstrat, int32_t lsecind) {
+  return guard(h, [&] { h->set_subex(on, rhmax, rhmin, tc0, larcticcorr, iconvlwp, rem, icldfrac, icldmstrat, lsecind); });
+}
+
+int rcmdyn_put_subex(rcmdyn_t* h, int32_t field, const double* src, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                     int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->put_subex(field, src, Box{j1, j2, i1, i2, k1, k2}); });
+}
+
+int rcmdyn_get_subex(rcmdyn_t* h, int32_t field, double* dst, int32_t j1, int32_t j2, int32_t i1, int32_t i2,
+                     int32_t k1, int32_t k2) {
+  return guard(h, [&] { h->get_subex(field, dst, Box{j1, j2, i1, i2, k1, k2}); });
+}
+
+int rcmdyn_physics_subex(rcmdyn_t* h) { return guard(h, [&] { h->physics_subex(); }); }
 
 int rcmdyn_set_tracers(rcmdyn_t* h, int32_t ntr, int32_t ichebdy) {
   return guard(h, [&] { h->set_tracers(ntr, ichebdy); });

@@ -238,6 +238,11 @@ struct Tile {
   // SUBEX condensation (rcmdyn_set_condtq; allocated at its first switch-on): the host's rh0adj
   // and the last tend's coupled increments of t, qv, qc
   double *rh0adj = nullptr, *cti[3] = {};
+  // SUBEX cldfrac and rain columns (rcmdyn_set_subex; allocated at the switch-on, freed at the
+  // switch-off: sbx_allocs): the fields in rcmdyn_subex_field order, subex's dqc, and the physics
+  // sums TPHY + LSC_T, QVPHY + LSC_QV, QCPHY + LSC_QC the tendency kernels read
+  double *sbx[RCMDYN_NSUBEX] = {}, *sbx_dqc = nullptr, *sbx_sum[3] = {};
+  std::vector<void*> sbx_allocs;
   // boundary slices (Main/mod_bdycod.F90:58-61): [k][frame index]
   double *sl[16];
   // wide frame of the fused split step on a decomposed domain (2-D inputs, ghost depth SPH)

@@ -73,6 +73,34 @@ RCM_HD double rcm_exp(double x) {
 // x**y for x > 0
 RCM_HD double rcm_powpos(double x, double y) { return rcm_exp(y * rcm_log(x)); }
 
+// exp(x + xl) for a tail |xl| <= ulp(x): rcm_exp with xl joined to the low part of the reduced
+// argument, so the tail costs no rounding of its own (|x| < 700)
+RCM_HD double rcm_exp_tail(double x, double xl) {
+  constexpr double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10;
+  constexpr double invln2 = 1.44269504088896338700e+00;
+  const double P1 = RCM_FMC(7, 1.66666666666666019037e-01), P2 = RCM_FMC(8, -2.77777777770155933842e-03);
+  const double P3 = RCM_FMC(9, 6.61375632143793436117e-05), P4 = RCM_FMC(10, -1.65339022054652515390e-06);
+  const double P5 = RCM_FMC(11, 4.13813679705723846039e-08);
+  const double k = std::rint(x * invln2);
+  const double hi = x - k * ln2HI;
+  const double lo = k * ln2LO - xl;
+  const double r = hi - lo;
+  const double t = r * r;
+  const double c = r - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+  const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+  return std::ldexp(y, (int)k);
+}
+
+// 10**x.  rcm_powpos(10.0, x) rounds x * log(10) to a double before the exponential, an error of
+// |x log 10| * 2^-53 in the result (8 ulp at x = -2); here log(10) is a double-double, the product's
+// rounding error comes out of one FMA, and both tails go to rcm_exp_tail: the error is rcm_exp's.
+RCM_HD double rcm_pow10(double x) {
+  constexpr double LN10_HI = 2.302585092994045901e+00, LN10_LO = -2.1707562233822493508e-16;
+  const double p = x * LN10_HI;
+  const double e = __builtin_fma(x, LN10_HI, -p);
+  return rcm_exp_tail(p, e + x * LN10_LO);
+}
+
 // x / y from r = 1.0 / y (an IEEE division formed once for a loop-invariant y): q = RN(x r) is
 // faithful, the remainder x - q y is exact in an FMA, and RN(q + r (x - q y)) is the correctly
 // rounded quotient (Markstein's theorem; finite normal operands), so the result has the bits of

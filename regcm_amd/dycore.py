@@ -34,6 +34,7 @@ EXPORTED = [
     "rcmdyn_set_budget", "rcmdyn_get_budget", "rcmdyn_reset_budget",
     "rcmdyn_set_massck", "rcmdyn_get_massck",
     "rcmdyn_set_condtq", "rcmdyn_put_rh0adj", "rcmdyn_get_condtq",
+    "rcmdyn_set_subex", "rcmdyn_put_subex", "rcmdyn_get_subex", "rcmdyn_physics_subex",
     "rcmdyn_set_tracers", "rcmdyn_put_tracer", "rcmdyn_get_tracer", "rcmdyn_put_tracer_nudge",
     "rcmdyn_set_cumtran", "rcmdyn_put_cumtran", "rcmdyn_get_cumtran",
     "rcmdyn_set_tracer_budget", "rcmdyn_get_tracer_budget", "rcmdyn_reset_tracer_budget",
@@ -48,6 +49,11 @@ IQV = 1    # the reference's index of water vapour (Main/mpplib/mod_runparams.F9
 MASSCK_COLUMNS = ("lcount", "dt", "drymass", "dryadv", "qmass", "qadv")
 # enum rcmdyn_condtq_term, in order: the held rh0adj, the last tend's condensation increments
 CONDTQ_TERMS = ["RH0ADJ", "T", "QV", "QC"]
+# enum rcmdyn_subex_field, in order: the host's 2-D tables, cucloud's output, the accumulators, and
+# what the device forms (REMRAT / REMBC with rem on); SUBEX_2D: the fields of one plane
+SUBEX_FIELDS = ["RH0", "QCK1", "CGUL", "CEVAP", "CACCR", "CU_CLDFRA", "CU_CLDLWC", "RAINNC", "LSMRNC",
+                "FCC", "CLDFRA", "CLDLWC", "RH0ADJ", "LSC_T", "LSC_QV", "LSC_QC", "TRRATE", "REMRAT", "REMBC"]
+SUBEX_2D = ("RH0", "QCK1", "CGUL", "CEVAP", "CACCR", "RAINNC", "LSMRNC", "TRRATE")
 # the host box every put and get ends with: j1, j2, i1, i2, k1, k2
 BOX = [ctypes.c_int32] * 6
 
@@ -110,6 +116,10 @@ def lib():
     L.rcmdyn_set_condtq.argtypes = [P, i32, ctypes.c_double]
     L.rcmdyn_put_rh0adj.argtypes = [P, dp, *BOX]
     L.rcmdyn_get_condtq.argtypes = [P, i32, dp, *BOX]
+    L.rcmdyn_set_subex.argtypes = [P, i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32, i32, i32, i32, i32]
+    L.rcmdyn_put_subex.argtypes = [P, i32, dp, *BOX]
+    L.rcmdyn_get_subex.argtypes = [P, i32, dp, *BOX]
+    L.rcmdyn_physics_subex.argtypes = [P]
     L.rcmdyn_set_tracers.argtypes = [P, i32, i32]
     L.rcmdyn_put_tracer.argtypes = [P, i32, i32, dp, *BOX]
     L.rcmdyn_get_tracer.argtypes = [P, i32, i32, dp, *BOX]
@@ -359,6 +369,36 @@ class DynCore:
         the last tend's coupled condensation increment of t, qv or qc (zero outside the interior
         cross points)."""
         return self._get_box(lib().rcmdyn_get_condtq, self.rc.kz, _number(CONDTQ_TERMS, term))
+
+    def set_subex(self, on: bool = True, rhmax: float = 1.01, rhmin: float = 0.01, tc0: float = 238.0,
+                  larcticcorr: bool = False, iconvlwp: int = 1, rem: bool = False, icldfrac: int = 0,
+                  icldmstrat: int = 0, lsecind: bool = False):
+        """SUBEX on the device (ipptls = 1): cldfrac with subex_cldfrac and the rain columns of subex
+        run where the reference calls physical_parametrizations, in a whole tend / step or from
+        physics_subex on the split path.  rhmax, rhmin, tc0, larcticcorr, iconvlwp: the run's
+        settings; rem: also REMRAT / REMBC.  icldfrac, icldmstrat, lsecind name options that are
+        not built: anything but 0 is refused.  The five 2-D tables must be put before a run."""
+        self._check(lib().rcmdyn_set_subex(self.h, 1 if on else 0, rhmax, rhmin, tc0, int(larcticcorr), int(iconvlwp),
+                                           int(rem), int(icldfrac), int(icldmstrat), int(lsecind)))
+
+    def put_subex(self, name, arr: np.ndarray, j1: int = 1, i1: int = 1, k1: int = 1):
+        """One field (SUBEX_FIELDS name or number) the host owns: the tables RH0, QCK1, CGUL, CEVAP,
+        CACCR and the accumulators RAINNC, LSMRNC as (ni, nj) or (1, ni, nj) arrays, cucloud's
+        CU_CLDFRA (in [0, 1]) and CU_CLDLWC as (kz, ni, nj) arrays, starting at (j1, i1, k1)."""
+        a = np.asarray(arr)
+        self._put_box(lib().rcmdyn_put_subex, a[None] if a.ndim == 2 else a, j1, i1, k1, _number(SUBEX_FIELDS, name))
+
+    def get_subex(self, name) -> np.ndarray:
+        """One field (SUBEX_FIELDS name or number) as a (1, iy, jx) array (SUBEX_2D) or a (kz, iy,
+        jx) array: zero outside the interior cross points."""
+        f = _number(SUBEX_FIELDS, name)
+        nk = 1 if 0 <= f < len(SUBEX_FIELDS) and SUBEX_FIELDS[f] in SUBEX_2D else self.rc.kz
+        return self._get_box(lib().rcmdyn_get_subex, nk, f)
+
+    def physics_subex(self):
+        """The subex kernels of the split path, between tend_pre_physics and tend_post_physics
+        (which runs them first if this was not called); once per tend."""
+        self._check(lib().rcmdyn_physics_subex(self.h))
 
     def set_tracers(self, ntr: int, ichebdy: int = 1):
         """Declares ntr chemical tracers (the reference's ichem = 1 chain of tend and bdyval);

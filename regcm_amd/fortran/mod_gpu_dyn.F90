@@ -58,6 +58,15 @@ module mod_gpu_dyn
   integer(c_int32_t), parameter, public :: &
     condtq_rh0adj = 0, condtq_t = 1, condtq_qv = 2, condtq_qc = 3, rcmdyn_ncondtq = 4
 
+  ! fields of rcmdyn_put_subex / rcmdyn_get_subex (enum rcmdyn_subex_field): the host's 2-D tables,
+  ! cucloud's output, the accumulators, and what the device forms (remrat / rembc with rem = 1)
+  integer(c_int32_t), parameter, public :: &
+    subex_rh0 = 0, subex_qck1 = 1, subex_cgul = 2, subex_cevap = 3, subex_caccr = 4, &
+    subex_cu_cldfra = 5, subex_cu_cldlwc = 6, subex_rainnc = 7, subex_lsmrnc = 8, &
+    subex_fcc = 9, subex_cldfra = 10, subex_cldlwc = 11, subex_rh0adj = 12, &
+    subex_lsc_t = 13, subex_lsc_qv = 14, subex_lsc_qc = 15, subex_trrate = 16, &
+    subex_remrat = 17, subex_rembc = 18, rcmdyn_nsubex = 19
+
   ! fields of one chemical tracer (enum rcmdyn_tracer_field): chia, chib, chiphy (put only), chib0,
   ! chibt, the mkslice export chib3d (get only); the most tracers of one engine (RCMDYN_MAXTR)
   integer(c_int32_t), parameter, public :: &
@@ -327,6 +336,43 @@ module mod_gpu_dyn
       integer(c_int32_t), value :: term, j1, j2, i1, i2, k1, k2
       real(c_double), intent(out) :: dst(*)
     end function
+    ! SUBEX on the device (ipptls = 1): cldfrac with subex_cldfrac and the rain columns of subex in
+    ! physical_parametrizations' place, on (1) or off (0, the default).  rhmax, rhmin, tc0,
+    ! larcticcorr, iconvlwp: the run's settings; rem = 1: also remrat / rembc (ichem = 1).
+    ! icldfrac, icldmstrat, lsecind: the host's settings of options that are not built, anything
+    ! but 0 is refused by name
+    integer(c_int) function rcmdyn_set_subex(h, on, rhmax, rhmin, tc0, larcticcorr, iconvlwp, rem, &
+        icldfrac, icldmstrat, lsecind) bind(c, name='rcmdyn_set_subex')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: on
+      real(c_double), value :: rhmax, rhmin, tc0
+      integer(c_int32_t), value :: larcticcorr, iconvlwp, rem, icldfrac, icldmstrat, lsecind
+    end function
+    ! one field the host owns (subex_rh0 .. subex_lsmrnc) from src(j1:j2,i1:i2,k1:k2); the five
+    ! tables must cover the interior cross points before the first run
+    integer(c_int) function rcmdyn_put_subex(h, field, src, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_put_subex')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: field
+      real(c_double), intent(in) :: src(*)
+      integer(c_int32_t), value :: j1, j2, i1, i2, k1, k2
+    end function
+    ! one field (subex_rainnc .. subex_rembc) into dst(j1:j2,i1:i2,k1:k2), interior cross points
+    integer(c_int) function rcmdyn_get_subex(h, field, dst, j1, j2, i1, i2, k1, k2) &
+        bind(c, name='rcmdyn_get_subex')
+      import :: c_int, c_ptr, c_int32_t, c_double
+      type(c_ptr), value :: h
+      integer(c_int32_t), value :: field, j1, j2, i1, i2, k1, k2
+      real(c_double), intent(out) :: dst(*)
+    end function
+    ! the subex kernels of the split path, between rcmdyn_tend_pre_physics and
+    ! rcmdyn_tend_post_physics (which runs them first if this was not called); once per tend
+    integer(c_int) function rcmdyn_physics_subex(h) bind(c, name='rcmdyn_physics_subex')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function
     ! the chemical tracers (the reference's ichem = 1 chain of tend and bdyval): ntr of them
     ! (0: the family off, its buffers freed); ichebdy must be 1
     integer(c_int) function rcmdyn_set_tracers(h, ntr, ichebdy) bind(c, name='rcmdyn_set_tracers')
@@ -467,6 +513,7 @@ module mod_gpu_dyn
   public :: rcmdyn_kernel_times, rcmdyn_set_budget, rcmdyn_get_budget, rcmdyn_reset_budget
   public :: rcmdyn_set_massck, rcmdyn_get_massck
   public :: rcmdyn_set_condtq, rcmdyn_put_rh0adj, rcmdyn_get_condtq
+  public :: rcmdyn_set_subex, rcmdyn_put_subex, rcmdyn_get_subex, rcmdyn_physics_subex
   public :: rcmdyn_set_tracers, rcmdyn_put_tracer, rcmdyn_get_tracer, rcmdyn_put_tracer_nudge
   public :: rcmdyn_set_cumtran, rcmdyn_put_cumtran, rcmdyn_get_cumtran
   public :: rcmdyn_set_tracer_budget, rcmdyn_get_tracer_budget, rcmdyn_reset_tracer_budget
