@@ -1,6 +1,8 @@
 """A NumPy statement of the reference's horizontal diffusion and lateral-boundary relaxation, and of
-the hydrostatic tendencies they are added to, for one limited-area tile (neither i_band nor i_crm),
-from the state after the initial bdyval.  Written from the Fortran text; nothing here reads the
+the hydrostatic tendencies they are added to, on the whole grid as one tile, from the state after the
+initial bdyval.  The grid is the text's: a limited area, a band (i_band = 1, periodic in j), or the
+cloud-resolving grid (i_crm = 1 over a band, periodic in j and i); `geom` gives the sides that exist and
+the loop ranges, and every mask and range below comes from it.  Written from the Fortran text; nothing here reads the
 oracle or the engine.  Test infrastructure: tests/test_dyn_rows_cpu.py compares the oracle with it,
 tests/test_dyn_rows_gpu.py the engine.
 
@@ -10,6 +12,8 @@ pressure tendency hold no transcendental function but the exp of the iboudy = 5 
 (math.exp, the C library's), so they are comparable bit for bit; the advection, adiabatic and
 pressure-gradient terms hold libm pow / log and are compared at rtol 1e-10.
 
+  the grid          has_bdy*, jde .. jcii, ide .. icii           Main/mod_atm_interface.F90:231-286;
+                                                                Main/mpplib/mod_mppparam.F90:1104-1132, 1338-1360
   setup_boundaries  ba_cr / ba_dt, ibnd and the side           Main/mod_atm_interface.F90:383-542
   setup_bdycon      fnudge, gnudge, fcx.., wgtx.., hefc..      Main/mod_bdycod.F90:203-273
   psc2psd           psdotb, the edge and corner rules          Main/mpplib/mod_mppparam.F90:13811-13862
@@ -28,6 +32,7 @@ pressure-gradient terms hold libm pow / log and are compared at rtol 1e-10.
   nudge2d           p* with the level-kz coefficient           Main/mod_bdycod.F90:4597-4766
   sponge3d/4d/uv/2d wgt * ften + (1 - wgt) * bt                Main/mod_bdycod.F90:2591-3122
   compute_omega     cr, pten, qdot, omega                      Main/mod_tendency.F90:1118-1215
+  compute_omega     the idynamic = 2 qdot (nh_qdot)            Main/mod_tendency.F90:1158-1178
   new_pressure      the p* boundary term                       Main/mod_tendency.F90:1428-1438
   the call order    advection, curvature, adiabatic, boundary, diffusion, the sums, the
                     pressure-gradient force, the u / v sums    Main/mod_tendency.F90:257-294, 398-411
@@ -36,8 +41,10 @@ pressure-gradient terms hold libm pow / log and are compared at rtol 1e-10.
 relaxation, diffusion and then the two pressure-gradient terms.)
 
 Arrays are (k, i, j) with the Fortran point (j, i, k) at [k - 1, i - 1, j - 1]; cross fields hold
-i = 1..iy-1, j = 1..jx-1 (the last row and column are unused).
+i = 1..iy-1, j = 1..jx-1 (the last row and column are unused); in a periodic direction the cross grid
+takes every point and a neighbour past the end is the one at the other end.
 """
+import contextlib
 import math
 
 import numpy as np
@@ -55,12 +62,122 @@ T00PG, P00PG, ALAM = 287.0, 101.325, 6.5e-3   # t00pg, p00pg, alam (:359-361); p
 SOUTH, NORTH, WEST, EAST = 1, 2, 3, 4
 
 
+# ------------------------------------------------------------------------------ the grid
+class Geom:
+    """The sides the whole grid has and the 1-based loop ranges of the text, from i_band, i_crm, jx, iy.
+
+    bandflag makes j periodic and crmflag i (Main/mpplib/mod_mppparam.F90:1104-1132): a periodic
+    direction has no boundary side (has_bdyleft / right under the band, has_bdybottom / top under
+    CRM are false).  The dot grid is 1..jx x 1..iy; the cross grid ends one short of it, but "takes
+    all points" in a periodic direction (:1338-1360).  The interior ranges step in by one (jdi, jci)
+    and by two (jdii, jcii) on the sides that exist only (Main/mod_atm_interface.F90:231-286)."""
+
+    def __init__(self, jx, iy, band=False, crm=False):
+        self.jx, self.iy = jx, iy
+        self.perj, self.peri = bool(band), bool(crm)
+        self.left = self.right = not self.perj                   # has_bdyleft, has_bdyright
+        self.bottom = self.top = not self.peri                   # has_bdybottom, has_bdytop
+        # the dot grid (:231-258)
+        self.jde1 = self.jdi1 = self.jdii1 = 1
+        self.jde2 = self.jdi2 = self.jdii2 = jx
+        self.ide1 = self.idi1 = self.idii1 = 1
+        self.ide2 = self.idi2 = self.idii2 = iy
+        if self.left:
+            self.jdi1, self.jdii1 = self.jde1 + 1, self.jde1 + 2
+        if self.right:
+            self.jdi2, self.jdii2 = self.jde2 - 1, self.jde2 - 2
+        if self.bottom:
+            self.idi1, self.idii1 = self.ide1 + 1, self.ide1 + 2
+        if self.top:
+            self.idi2, self.idii2 = self.ide2 - 1, self.ide2 - 2
+        # the cross grid (:259-286), one short of the dot grid but in a periodic direction
+        self.jce1 = self.jci1 = self.jcii1 = 1
+        self.jce2 = self.jci2 = self.jcii2 = jx if self.perj else jx - 1
+        self.ice1 = self.ici1 = self.icii1 = 1
+        self.ice2 = self.ici2 = self.icii2 = iy if self.peri else iy - 1
+        if self.left:
+            self.jci1, self.jcii1 = self.jce1 + 1, self.jce1 + 2
+        if self.right:
+            self.jci2, self.jcii2 = self.jce2 - 1, self.jce2 - 2
+        if self.bottom:
+            self.ici1, self.icii1 = self.ice1 + 1, self.ice1 + 2
+        if self.top:
+            self.ici2, self.icii2 = self.ice2 - 1, self.ice2 - 2
+
+    def rect(self, j1, j2, i1, i2):
+        """[i, j] of the 1-based j1..j2 x i1..i2."""
+        m = np.zeros((self.iy, self.jx), dtype=bool)
+        m[i1 - 1:i2, j1 - 1:j2] = True
+        return m
+
+    def box(self, which, dot):
+        """The mask of a named range: which = 'e' (jde x ide / jce x ice), 'i' or 'ii'."""
+        if dot:
+            r = {"e": (self.jde1, self.jde2, self.ide1, self.ide2), "i": (self.jdi1, self.jdi2, self.idi1, self.idi2),
+                 "ii": (self.jdii1, self.jdii2, self.idii1, self.idii2)}
+        else:
+            r = {"e": (self.jce1, self.jce2, self.ice1, self.ice2), "i": (self.jci1, self.jci2, self.ici1, self.ici2),
+                 "ii": (self.jcii1, self.jcii2, self.icii1, self.icii2)}
+        return self.rect(*r[which])
+
+    def lines(self, dot):
+        """The masks of the first interior lines on the sides that exist, in the text's order west,
+        east, south, north (j = jdi1 / jci1, jdi2 / jci2, i = idi1 / ici1, idi2 / ici2)."""
+        jj, ii = np.meshgrid(np.arange(1, self.jx + 1), np.arange(1, self.iy + 1))
+        j1, j2, i1, i2 = ((self.jdi1, self.jdi2, self.idi1, self.idi2) if dot else
+                          (self.jci1, self.jci2, self.ici1, self.ici2))
+        cand = ((self.left, jj == j1), (self.right, jj == j2), (self.bottom, ii == i1), (self.top, ii == i2))
+        return [m for has, m in cand if has]
+
+    def pad(self, a, n):
+        """a with n more points on each side of its last two axes: the periodic neighbours in a
+        periodic direction, zeros past a side that exists."""
+        a = np.pad(a, [(0, 0)] * (a.ndim - 1) + [(n, n)], mode="wrap" if self.perj and _WRAP else "constant")
+        return np.pad(a, [(0, 0)] * (a.ndim - 2) + [(n, n), (0, 0)], mode="wrap" if self.peri and _WRAP else "constant")
+
+
+def geom(rc):
+    return Geom(rc.jx, rc.iy, getattr(rc, "i_band", 0) == 1, getattr(rc, "i_crm", 0) == 1)
+
+
+_WRAP = True
+
+
+@contextlib.contextmanager
+def zero_pad_for_the_wrap():
+    """A mutant of the whole module, for the tests' non-vacuity asserts: inside it a neighbour past
+    the end of the grid is zero, the limited-area pad, where a periodic direction has the point at
+    the other end (sh and Geom.pad).  The ranges stay those of the grid."""
+    global _WRAP
+    _WRAP = False
+    try:
+        yield
+    finally:
+        _WRAP = True
+
+
+def twt(rc):
+    """(twt1, twt2), twt(k,1) and twt(k,2) indexed by the 1-based k = 2..kz (Main/mod_params.F90):
+    the weights that take half-level values k and k - 1 to the full level k."""
+    kz, sig = rc.kz, rc.sigma
+    hsig = (sig[1:] + sig[:-1]) * 0.5
+    twt1, twt2 = np.zeros(kz + 1), np.zeros(kz + 1)
+    for k in range(2, kz + 1):
+        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
+        twt2[k] = 1.0 - twt1[k]
+    return twt1, twt2
+
+
 # ------------------------------------------------------------------------------ the band
 def band_sides(rc, dot):
     """{(j, i): (side, ibnd)} of setup_boundaries for ba_dt (dot: icx = icy = 0, nspgd) or ba_cr
-    (nspgx), neither bandflag nor crmflag, on the points the nudge and sponge loops visit
-    (jdi x idi or jci x ici).  The four sides do not overlap (asserted)."""
+    (nspgx), on the points the nudge and sponge loops visit (jdi x idi or jci x ici).  The four sides
+    do not overlap (asserted).  Under crmflag the band is empty (:434); under bandflag (:435-457) it
+    is the south and north rows at every j, with no corner rule.  The band branch's `if ( j < jgbl1
+    .and. j > jgbr2 ) cycle` asks for j < 2 and j > jx - icx - 1 at once, which no j satisfies: it is
+    restated as written and never skips."""
     jx, iy = rc.jx, rc.iy
+    G = geom(rc)
     nsp = rc.nspgd if dot else rc.nspgx
     ic = 0 if dot else 1
     igbb1, igbb2, jgbl1, jgbl2 = 2, nsp - 1, 2, nsp - 1
@@ -71,6 +188,26 @@ def band_sides(rc, dot):
     def put(j, i, side, ib):
         assert (j, i) not in out, (j, i)
         out[(j, i)] = (side, ib)
+
+    def visited(o):
+        m = G.box("i", dot)
+        return {p: v for p, v in o.items() if m[p[1] - 1, p[0] - 1]}
+    if G.peri:
+        return {}
+    if G.perj:
+        for i in range(1, iy + 1):
+            if igbb1 <= i <= igbb2:
+                for j in range(1, jx + 1):
+                    if j < jgbl1 and j > jgbr2:
+                        continue
+                    put(j, i, SOUTH, i - igbb1 + 2)
+        for i in range(1, iy + 1):
+            if igbt1 <= i <= igbt2:
+                for j in range(1, jx + 1):
+                    if j < jgbl1 and j > jgbr2:
+                        continue
+                    put(j, i, NORTH, igbt2 - i + 2)
+        return visited(out)
     for i in range(1, iy + 1):
         if igbb1 <= i <= igbb2:
             for j in range(1, jx + 1):
@@ -109,8 +246,7 @@ def band_sides(rc, dot):
                 if i > igbt1 and (jgbr2 - j) > (igbt2 - i):
                     continue
                 put(j, i, EAST, jgbr2 - j + 2)
-    jhi, ihi = (jx - 1, iy - 1) if dot else (jx - 2, iy - 2)
-    return {p: v for p, v in out.items() if 2 <= p[0] <= jhi and 2 <= p[1] <= ihi}
+    return visited(out)
 
 
 def band(rc, dot=False):
@@ -127,24 +263,20 @@ def band_mask(rc, dot=False):
 
 def domain_mask(rc, dot=False):
     """[i, j] of jdi x idi (dot) or jci x ici."""
-    m = np.zeros((rc.iy, rc.jx), dtype=bool)
-    m[1:(rc.iy - 1 if dot else rc.iy - 2), 1:(rc.jx - 1 if dot else rc.jx - 2)] = True
-    return m
+    return geom(rc).box("i", dot)
 
 
 def ring_masks(rc, dot=False):
-    """(ring, corners): the second-order lines jdi1 / jdi2 / idi1 / idi2 (or the cross ones) and
-    their four corners."""
-    dom = domain_mask(rc, dot)
-    inner = np.zeros_like(dom)
-    inner[2:(rc.iy - 2 if dot else rc.iy - 3), 2:(rc.jx - 2 if dot else rc.jx - 3)] = True
-    ring = dom & ~inner
-    i2, j2 = (rc.iy - 2, rc.jx - 2) if dot else (rc.iy - 3, rc.jx - 3)
-    corners = np.zeros_like(dom)
-    for i in (1, i2):
-        for j in (1, j2):
-            corners[i, j] = True
-    return ring, corners
+    """(ring, corners): the second-order lines jdi1 / jdi2 / idi1 / idi2 (or the cross ones) on the
+    sides that exist, and the corners where two of them meet (none on a band)."""
+    G = geom(rc)
+    dom = G.box("i", dot)
+    ring = dom & ~G.box("ii", dot)
+    count = np.zeros(dom.shape, dtype=int)
+    for line in G.lines(dot):
+        count += (line & dom)
+    assert np.array_equal(count > 0, ring)
+    return ring, count > 1
 
 
 # ------------------------------------------------------------------------------ the coefficient tables
@@ -179,26 +311,42 @@ def tables(rc):
 
 
 # ------------------------------------------------------------------------------ slices
-def psc2psd(pc):
-    """psdot from the cross p* (iy, jx; the last row and column unused) on one global tile."""
+def psc2psd(pc, G=None):
+    """psdot from the cross p* (iy, jx) on the whole grid as one tile; G: the grid (default: a limited
+    area).  The interior form over jdi x idi, whose j - 1 (and i - 1 under CRM) is the periodic
+    neighbour where the direction is periodic; the two-point edge lines (each over jdi or idi) and
+    the corners only on the sides that exist (has_bdytop .., has_bdybottomleft ..)."""
     iy, jx = pc.shape
+    G = G or Geom(jx, iy)
     pd = np.zeros_like(pc)
-    pd[1:iy - 1, 1:jx - 1] = (pc[1:iy - 1, 1:jx - 1] + pc[0:iy - 2, 1:jx - 1] + pc[1:iy - 1, 0:jx - 2] +
-                              pc[0:iy - 2, 0:jx - 2]) * 0.25
-    pd[iy - 1, 1:jx - 1] = (pc[iy - 2, 1:jx - 1] + pc[iy - 2, 0:jx - 2]) * 0.5
-    pd[0, 1:jx - 1] = (pc[0, 1:jx - 1] + pc[0, 0:jx - 2]) * 0.5
-    pd[1:iy - 1, 0] = (pc[1:iy - 1, 0] + pc[0:iy - 2, 0]) * 0.5
-    pd[1:iy - 1, jx - 1] = (pc[1:iy - 1, jx - 2] + pc[0:iy - 2, jx - 2]) * 0.5
-    pd[0, 0], pd[iy - 1, 0] = pc[0, 0], pc[iy - 2, 0]
-    pd[0, jx - 1], pd[iy - 1, jx - 1] = pc[0, jx - 2], pc[iy - 2, jx - 2]
+    inner = G.box("i", True)
+    pd[inner] = ((pc + sh(pc, 0, -1) + sh(pc, -1, 0) + sh(pc, -1, -1)) * 0.25)[inner]
+    js, is_ = slice(G.jdi1 - 1, G.jdi2), slice(G.idi1 - 1, G.idi2)
+    if G.top:
+        pd[G.ide2 - 1, js] = ((pc[G.ice2 - 1] + sh(pc, -1, 0)[G.ice2 - 1]) * 0.5)[js]
+    if G.bottom:
+        pd[G.ide1 - 1, js] = ((pc[G.ice1 - 1] + sh(pc, -1, 0)[G.ice1 - 1]) * 0.5)[js]
+    if G.left:
+        pd[is_, G.jde1 - 1] = ((pc[:, G.jce1 - 1] + sh(pc, 0, -1)[:, G.jce1 - 1]) * 0.5)[is_]
+    if G.right:
+        pd[is_, G.jde2 - 1] = ((pc[:, G.jce2 - 1] + sh(pc, 0, -1)[:, G.jce2 - 1]) * 0.5)[is_]
+    if G.left and G.bottom:
+        pd[G.ide1 - 1, G.jde1 - 1] = pc[G.ice1 - 1, G.jce1 - 1]
+    if G.left and G.top:
+        pd[G.ide2 - 1, G.jde1 - 1] = pc[G.ice2 - 1, G.jce1 - 1]
+    if G.right and G.bottom:
+        pd[G.ide1 - 1, G.jde2 - 1] = pc[G.ice1 - 1, G.jce2 - 1]
+    if G.right and G.top:
+        pd[G.ide2 - 1, G.jde2 - 1] = pc[G.ice2 - 1, G.jce2 - 1]
     return pd
 
 
-def b_slices(st):
+def b_slices(st, G=None):
     """mkslice's b-level exports: (ubd3d, vbd3d, tb3d, qvb3d, qcb3d, psdotb)."""
     psb = st["PSB"][0]
-    pd = psc2psd(psb)
-    rpd = 1.0 / pd
+    pd = psc2psd(psb, G)
+    with np.errstate(divide="ignore"):
+        rpd = 1.0 / pd
     with np.errstate(divide="ignore", invalid="ignore"):       # the unused last row and column hold zeros
         rpsb = 1.0 / psb
         tb = st["ATM2_T"] * rpsb[None]
@@ -213,20 +361,21 @@ def _hgfact(rc, ht, xkhz):
     dx = rc.ds * 1000.0
     hg = np.full((iy, jx), xkhz)
     if rc.diffu_hgtf == 1:
-        c = ht[1:iy - 2, 1:jx - 2]
-        hg1 = np.abs((c - ht[0:iy - 3, 1:jx - 2]) / dx)
-        hg2 = np.abs((c - ht[2:iy - 1, 1:jx - 2]) / dx)
-        hg3 = np.abs((c - ht[1:iy - 2, 0:jx - 3]) / dx)
-        hg4 = np.abs((c - ht[1:iy - 2, 2:jx - 1]) / dx)
+        m = geom(rc).box("i", False)                             # jci x ici (:131-140)
+        hg1 = np.abs((ht - sh(ht, 0, -1)) / dx)
+        hg2 = np.abs((ht - sh(ht, 0, 1)) / dx)
+        hg3 = np.abs((ht - sh(ht, -1, 0)) / dx)
+        hg4 = np.abs((ht - sh(ht, 1, 0)) / dx)
         hgmax = np.maximum(np.maximum(hg1, hg2), np.maximum(hg3, hg4)) * REGRAV * 1.0e3
-        hg[1:iy - 2, 1:jx - 2] = xkhz / (1.0 + hgmax * hgmax)
+        hg[m] = (xkhz / (1.0 + hgmax * hgmax))[m]
     return hg
 
 
 def _deformation(ud, vd):
-    """(dudx - dvdy)^2 + (dvdx + dudy)^2 at the cross points 1..iy-1 x 1..jx-1 (:198-206)."""
+    """(dudx - dvdy)^2 + (dvdx + dudy)^2 at every point (:198-206); the callers keep jce x ice, where
+    j + 1 and i + 1 are dot points of the grid or, past the end of a periodic direction, the first."""
     def q(a):
-        return a[:, :-1, :-1], a[:, :-1, 1:], a[:, 1:, :-1], a[:, 1:, 1:]   # (j,i) (j+1,i) (j,i+1) (j+1,i+1)
+        return a, sh(a, 1, 0), sh(a, 0, 1), sh(a, 1, 1)          # (j,i) (j+1,i) (j,i+1) (j+1,i+1)
     u00, u10, u01, u11 = q(ud)
     v00, v10, v01, v11 = q(vd)
     dudx = u10 + u11 - u00 - u01
@@ -238,16 +387,13 @@ def _deformation(ud, vd):
 
 def _scale_coeff(rc, raw, psb, pd):
     """xkd as the four-point mean of the unscaled xkc (:237-240), then both x rdxsq x p* (:241-249)."""
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    G = geom(rc)
     dx = rc.ds * 1000.0
     rdxsq = 1.0 / (dx * dx)
-    xkd_raw = np.zeros((kz, iy, jx))
-    xkd_raw[:, 1:iy - 1, 1:jx - 1] = 0.25 * (raw[:, 1:iy - 1, 1:jx - 1] + raw[:, 0:iy - 2, 0:jx - 2] +
-                                             raw[:, 1:iy - 1, 0:jx - 2] + raw[:, 0:iy - 2, 1:jx - 1])
-    xkc = np.zeros((kz, iy, jx))
-    xkc[:, 1:iy - 2, 1:jx - 2] = raw[:, 1:iy - 2, 1:jx - 2] * rdxsq * psb[None, 1:iy - 2, 1:jx - 2]
-    xkd = np.zeros((kz, iy, jx))
-    xkd[:, 1:iy - 1, 1:jx - 1] = xkd_raw[:, 1:iy - 1, 1:jx - 1] * rdxsq * pd[None, 1:iy - 1, 1:jx - 1]
+    md, mc = G.box("i", True)[None], G.box("i", False)[None]
+    xkd_raw = np.where(md, 0.25 * (raw + sh(raw, -1, -1) + sh(raw, -1, 0) + sh(raw, 0, -1)), 0.0)
+    xkc = np.where(mc, raw * rdxsq * psb[None], 0.0)
+    xkd = np.where(md, xkd_raw * rdxsq * pd[None], 0.0)
     return dict(xkc_raw=raw, xkd_raw=xkd_raw, xkc=xkc, xkd=xkd)
 
 
@@ -255,13 +401,13 @@ def coeff6(rc, st):
     """calc_coeff at idiffu = 3, either core (:174-183): xkc = diff_6th_coef p*b on jci x ici (every
     level alike; xkcf is the same on kz + 1 levels), xkd = diff_6th_coef p*dotb on jdi x idi, with
     diff_6th_coef = diff_6th_factor * 0.015625 / (2 dtsec) (:154); zero elsewhere.  st: PSB."""
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    G = geom(rc)
     coef = DIFF_6TH_FACTOR * 0.015625 / (2.0 * rc.dt)
     psb = st["PSB"][0]
-    pd = psc2psd(psb)
-    xkc, xkd = np.zeros((kz, iy, jx)), np.zeros((kz, iy, jx))
-    xkc[:, 1:iy - 2, 1:jx - 2] = coef * psb[None, 1:iy - 2, 1:jx - 2]
-    xkd[:, 1:iy - 1, 1:jx - 1] = coef * pd[None, 1:iy - 1, 1:jx - 1]
+    pd = psc2psd(psb, G)
+    one = np.ones((rc.kz, 1, 1))
+    xkc = np.where(G.box("i", False)[None], one * (coef * psb)[None], 0.0)
+    xkd = np.where(G.box("i", True)[None], one * (coef * pd)[None], 0.0)
     return dict(xkc=xkc, xkd=xkd)
 
 
@@ -270,20 +416,20 @@ def hydro_coeff(rc, st):
     xkc (ici x jci) and xkd (idi x jdi); zero elsewhere.  st: ATM2_U, ATM2_V, PSB, HT."""
     if rc.idiffu == 3:
         return coeff6(rc, st)
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
     dx = rc.ds * 1000.0
     dxsq = dx * dx
     xkhmax = dxsq / (64.0 * rc.dt)
     dydc = rc.adyndif * VONKAR * VONKAR * dx * 0.25
     xkhz = rc.ckh * 1.5e-3 * dxsq / rc.dt
     psb = st["PSB"][0]
-    pd = psc2psd(psb)
-    rpd = 1.0 / pd
-    ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
-    hg = _hgfact(rc, st["HT"][0], xkhz)
-    duv = np.sqrt(_deformation(ud, vd))
-    raw = np.zeros((kz, iy, jx))
-    raw[:, :iy - 1, :jx - 1] = np.minimum(hg[None, :iy - 1, :jx - 1] + dydc * duv, xkhmax)
+    G = geom(rc)
+    pd = psc2psd(psb, G)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rpd = 1.0 / pd
+        ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
+        hg = _hgfact(rc, st["HT"][0], xkhz)
+        duv = np.sqrt(_deformation(ud, vd))
+        raw = np.where(G.box("e", False)[None], np.minimum(hg[None] + dydc * duv, xkhmax), 0.0)
     return _scale_coeff(rc, raw, psb, pd)
 
 
@@ -293,23 +439,23 @@ def nh_coeff(rc, st):
     ATM2_V, ATM2_W, PSB (and HT where diffu_hgtf = 1)."""
     if rc.idiffu == 3:
         return coeff6(rc, st)
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    iy, jx = rc.iy, rc.jx
     dx = rc.ds * 1000.0
     dxsq = dx * dx
     xkhmax = 2.0 * (dxsq / (64.0 * rc.dt))
     dydc = rc.adyndif * VONKAR * VONKAR * dx * 0.25
     xkhz = rc.ckh * dx
     psb = st["PSB"][0]
-    pd = psc2psd(psb)
-    rpd = 1.0 / pd
-    ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
+    G = geom(rc)
+    pd = psc2psd(psb, G)
     with np.errstate(divide="ignore", invalid="ignore"):
+        rpd = 1.0 / pd
+        ud, vd = st["ATM2_U"] * rpd[None], st["ATM2_V"] * rpd[None]
         wb = st["ATM2_W"] * (1.0 / psb)[None]
-    hg = _hgfact(rc, st["HT"][0], xkhz) if rc.diffu_hgtf == 1 else np.full((iy, jx), xkhz)
-    dwdz = wb[:-1, :iy - 1, :jx - 1] - wb[1:, :iy - 1, :jx - 1]
-    duv = np.sqrt(np.maximum(_deformation(ud, vd) - dwdz * dwdz, 0.0))
-    raw = np.zeros((kz, iy, jx))
-    raw[:, :iy - 1, :jx - 1] = np.minimum(hg[None, :iy - 1, :jx - 1] + dydc * duv, xkhmax)
+        hg = _hgfact(rc, st["HT"][0], xkhz) if rc.diffu_hgtf == 1 else np.full((iy, jx), xkhz)
+        dwdz = wb[:-1] - wb[1:]
+        duv = np.sqrt(np.maximum(_deformation(ud, vd) - dwdz * dwdz, 0.0))
+        raw = np.where(G.box("e", False)[None], np.minimum(hg[None] + dydc * duv, xkhmax), 0.0)
     return _scale_coeff(rc, raw, psb, pd)
 
 
@@ -327,7 +473,9 @@ def tile_columns(rc, dot, tiles=None):
     sides the tile touches; None is the single tile.  jdi2 = jde2 - 1 on the right side and jde2
     off it, and so on (Main/mod_atm_interface.F90:231-286)."""
     if tiles is None:
-        tiles = [((1, rc.jx, 1, rc.iy, 1, rc.jx - 1, 1, rc.iy - 1), (1, 1, 1, 1))]
+        G = geom(rc)
+        tiles = [((G.jde1, G.jde2, G.ide1, G.ide2, G.jce1, G.jce2, G.ice1, G.ice2),
+                  (G.left, G.right, G.bottom, G.top))]
     out = []
     for ext, (_, right, bottom, top) in tiles:
         j2, i1, i2 = (ext[1], ext[2], ext[3]) if dot else (ext[5], ext[6], ext[7])
@@ -388,31 +536,33 @@ def diffu6(rc, fv, lv, xk, cols, dot, fac=None):
 def _diffu(rc, fm, xk, dot, fac=None):
     """The increments of one diffu_* call, in the order the text adds them: idiffu = 1: the
     fourth-order interior (jdii x idii / jcii x icii), then the second-order lines west, east, south,
-    north (the corners lie on two lines and take two adds); idiffu = 2: the nine-point form on the
-    whole jdi x idi / jci x ici.  fm, xk: (nk, iy, jx); each increment is zero off its support.  fac:
-    diffu_x3df's, which multiplies the coefficient first (fac * xkcf * (...))."""
+    north on the sides that exist (`if ( ma%has_bdyleft )` .., :552-591; the corners lie on two lines
+    and take two adds); idiffu = 2: the nine-point form on the whole jdi x idi / jci x ici.  A
+    neighbour past the end of a periodic direction is the one at the other end; on a band the
+    fourth-order form covers every j and only the south and north lines exist.  fm, xk: (nk, iy, jx);
+    each increment is zero off its support.  fac: diffu_x3df's, which multiplies the coefficient
+    first (fac * xkcf * (...))."""
     iy, jx = rc.iy, rc.jx
+    G = geom(rc)
     if fac is not None:
         xk = fac * xk
-    j2, i2 = (jx - 1, iy - 1) if dot else (jx - 2, iy - 2)
     with np.errstate(invalid="ignore"):
-        P = np.pad(fm, ((0, 0), (2, 2), (2, 2)))
+        P = G.pad(fm, 2)
 
         def F(dj, di):
             return P[:, 2 + di:2 + di + iy, 2 + dj:2 + dj + jx]
-        jj, ii = np.meshgrid(np.arange(1, jx + 1), np.arange(1, iy + 1))
-        dom = (jj >= 2) & (jj <= j2) & (ii >= 2) & (ii <= i2)
+        dom = G.box("i", dot)
         if rc.idiffu == 2:
             inc = xk * (O4[0] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) +
                         O4[1] * (F(1, 1) + F(-1, -1) + F(-1, 1) + F(1, -1)) + O4[2] * fm)
             return [np.where(dom[None], inc, 0.0)]
         assert rc.idiffu == 1
-        inner = (jj >= 3) & (jj <= j2 - 1) & (ii >= 3) & (ii <= i2 - 1)
+        inner = G.box("ii", dot)
         fourth = -(xk * (Z4[0] * (F(2, 0) + F(-2, 0) + F(0, 2) + F(0, -2)) +
                          Z4[1] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) + Z4[2] * fm))
         second = xk * (Z4[0] * (F(1, 0) + F(-1, 0) + F(0, 1) + F(0, -1)) + Z4[1] * fm)
         out = [np.where(inner[None], fourth, 0.0)]
-        for line in (jj == 2, jj == j2, ii == 2, ii == i2):
+        for line in G.lines(dot):
             out.append(np.where((dom & line)[None], second, 0.0))
         return out
 
@@ -448,18 +598,26 @@ def total(incs):
 
 
 # ------------------------------------------------------------------------------ relaxation
-def _lap(fg):
-    """fls1 + fls2 + fls3 + fls4 - 4 fls0 (j-1, j+1, i-1, i+1), zero on the frame edge."""
-    out = np.zeros_like(fg)
-    c = fg[..., 1:-1, 1:-1]
-    out[..., 1:-1, 1:-1] = fg[..., 1:-1, :-2] + fg[..., 1:-1, 2:] + fg[..., :-2, 1:-1] + fg[..., 2:, 1:-1] - 4.0 * c
-    return out
+def _lap(fg, G=None):
+    """fls1 + fls2 + fls3 + fls4 - 4 fls0 (j-1, j+1, i-1, i+1), zero on the frame edge of a side that
+    exists; j +- 1 (i +- 1) is the periodic neighbour in a periodic direction."""
+    G = G or Geom(fg.shape[-1], fg.shape[-2])
+    P = G.pad(fg, 1)
+    out = P[..., 1:-1, :-2] + P[..., 1:-1, 2:] + P[..., :-2, 1:-1] + P[..., 2:, 1:-1] - 4.0 * fg
+    edge = np.zeros(fg.shape[-2:], dtype=bool)
+    if not G.perj:
+        edge[:, 0] = edge[:, -1] = True
+    if not G.peri:
+        edge[0, :] = edge[-1, :] = True
+    return np.where(edge, 0.0, out)
 
 
 def _coef(rc, tab, dot, kind, nk):
     """(xf, xg) as (nk, iy, jx), zero off the band: iboudy 1 the linear fcx / gcx (fcd / gcd for u, v);
     iboudy 5 hefc / hegc(ib, k) for t and qv, (ib, kz) for p*, and for u, v hefc / hegc on the south
-    side, hefd / hegd on the other three (:3720, 3746, 3772, 3798)."""
+    side, hefd / hegd on the other three (:3720, 3746, 3772, 3798); each side's loop names its table,
+    so on a band, which has no west or east side, the south dot points take hefc / hegc and the north
+    ones hefd / hegd."""
     xf, xg = np.zeros((nk, rc.iy, rc.jx)), np.zeros((nk, rc.iy, rc.jx))
     for (j, i), (side, ib) in band_sides(rc, dot).items():
         if rc.iboudy == 1:
@@ -487,9 +645,10 @@ def nudge(rc, f, b0, bt, xt, kind, tab=None):
     else:
         fg = (b0 + xt * bt) - f
     xf, xg = _coef(rc, tab, dot, kind, f.shape[0])
+    G = geom(rc)
     if kind == "qv":
-        return [rfac * (xf * fg - xg * _lap(fg))]
-    return [xf * fg, -(xg * _lap(fg))]
+        return [rfac * (xf * fg - xg * _lap(fg, G))]
+    return [xf * fg, -(xg * _lap(fg, G))]
 
 
 def sponge(rc, ften, bt, dot, tab=None):
@@ -510,8 +669,16 @@ HYDRO_INPUTS = ("ATM1_U", "ATM1_V", "ATM1_T", "ATM1_QV", "ATM1_QC", "ATM2_U", "A
 
 
 def sh(a, dj, di):
-    """sh(a)[k, i, j] = a[k, i + di, j + dj]."""
-    return np.roll(a, shift=(-di, -dj), axis=(-2, -1))
+    """sh(a)[k, i, j] = a[k, i + di, j + dj], around the end of the array (a periodic direction's
+    neighbour; on a side that exists the callers never keep such a point)."""
+    out = np.roll(a, shift=(-di, -dj), axis=(-2, -1))
+    if not _WRAP:                                                # zero_pad_for_the_wrap
+        ni, nj = a.shape[-2:]
+        if di:
+            out[..., (ni - di if di > 0 else 0):(ni if di > 0 else -di), :] = 0.0
+        if dj:
+            out[..., :, (nj - dj if dj > 0 else 0):(nj if dj > 0 else -dj)] = 0.0
+    return out
 
 
 class Sum:
@@ -541,8 +708,10 @@ class Sum:
 
 def compute_omega(rc, g):
     """compute_omega's cr x dummy (a product with the reciprocal), pten and qdot (kz + 1 levels, the
-    first and the last zero) from atm1 u, v, p*a and the map factors: (cr, pten, qdot)."""
+    first and the last zero) from atm1 u, v, p*a and the map factors: (cr, pten, qdot), on jce x ice
+    and zero off it; j + 1 and i + 1 past the end of a periodic direction are the first points."""
     kz = rc.kz
+    me = geom(rc).box("e", False)
     dsig = rc.sigma[1:] - rc.sigma[:-1]
     dx = rc.ds * 1000.0
     pa, msfx, msfd = g["PSA"][0], g["MSFX"][0], g["MSFD"][0]
@@ -558,7 +727,68 @@ def compute_omega(rc, g):
         qdot = np.zeros((kz + 1,) + pa.shape)
         for k in range(2, kz + 1):
             qdot[k - 1] = qdot[k - 2] - (pten + cr[k - 2]) * dsig[k - 2] * rpsa
-    return cr, pten, qdot
+    return np.where(me[None], cr, 0.0), np.where(me, pten, 0.0), np.where(me[None], qdot, 0.0)
+
+
+def decouple_uv(rc, g, psd):
+    """decouple's atmx%ud, vd (Main/mod_tendency.F90:888-994): atm1 u, v times 1 / psdota; after bdyval
+    the boundary slices wue .. nvi hold atm1 on their lines, so the boundary assignments change
+    nothing but under iboudy 3 / 4, where an outflow edge value is the first interior line's (:908-918,
+    933-943, 958-968, 983-993): west, east over idi, then south, north over jde (the corners read the
+    lines just set), each only on a side that exists (`if ( ma%has_bdyleft )` ..)."""
+    G = geom(rc)
+    u1, v1 = g["ATM1_U"], g["ATM1_V"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rpsd = 1.0 / psd
+        ud, vd = u1 * rpsd, v1 * rpsd
+    if rc.iboudy in (3, 4):
+        ri = slice(G.idi1 - 1, G.idi2)
+        for a in (ud, vd):
+            if G.left:
+                a[:, ri, 0] = np.where(u1[:, ri, 0] <= 0.0, a[:, ri, 1], a[:, ri, 0])
+            if G.right:
+                a[:, ri, -1] = np.where(u1[:, ri, -1] >= 0.0, a[:, ri, -2], a[:, ri, -1])
+            if G.bottom:
+                a[:, 0, :] = np.where(v1[:, 0, :] >= 0.0, a[:, 1, :], a[:, 0, :])
+            if G.top:
+                a[:, -1, :] = np.where(v1[:, -1, :] <= 0.0, a[:, -2, :], a[:, -1, :])
+    return ud, vd
+
+
+NH_QDOT_INPUTS = ("ATM1_U", "ATM1_V", "ATM1_W", "PSA", "MSFD", "ATM0_RHOF", "ATM0_PS", "DPSDXM", "DPSDYM")
+
+
+def nh_qdot(rc, g, swap_twt=False):
+    """The idynamic = 2 branch of compute_omega (Main/mod_tendency.F90:1158-1178): qdot on kz + 1
+    levels, the first and the last zero, on jce x ice and zero off it.
+
+      ucc(j,i,k) = umd(j,i,k) + umd(j,i+1,k) + umd(j+1,i,k) + umd(j+1,i+1,k)          (vcc alike)
+      qdot(j,i,k) = -rhof(j,i,k) egrav w(j,i,k) / ps0(j,i)
+                    - sigma(k) (dpsdxm(j,i) (twt(k,1) ucc(k) + twt(k,2) ucc(k-1))
+                                + dpsdym(j,i) (twt(k,1) vcc(k) + twt(k,2) vcc(k-1)))     k = 2..kz
+
+    with atmx%umd = atmx%ud msfd (:1005-1008; ud is decouple_uv's, the inflow / outflow copies
+    included) and atmx%w = atm1%w rpsa (:1051-1053).  No transcendental function.  swap_twt: a mutant
+    for the tests' non-vacuity asserts (twt(k,1) and twt(k,2) exchanged)."""
+    kz = rc.kz
+    G = geom(rc)
+    sig = rc.sigma
+    twt1, twt2 = twt(rc)
+    pa, msfd = g["PSA"][0], g["MSFD"][0]
+    ud, vd = decouple_uv(rc, g, psc2psd(pa, G))
+    qdot = np.zeros((kz + 1,) + pa.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rpsa = 1.0 / pa
+        umd, vmd = ud * msfd, vd * msfd
+        xw = g["ATM1_W"] * rpsa
+        ucc = (umd + sh(umd, 0, 1) + sh(umd, 1, 0) + sh(umd, 1, 1))
+        vcc = (vmd + sh(vmd, 0, 1) + sh(vmd, 1, 0) + sh(vmd, 1, 1))
+        for k in range(2, kz + 1):
+            t1, t2 = (twt2[k], twt1[k]) if swap_twt else (twt1[k], twt2[k])
+            qdot[k - 1] = (-g["ATM0_RHOF"][k - 1] * EGRAV * xw[k - 1] / g["ATM0_PS"][0] -
+                           sig[k - 1] * (g["DPSDXM"][0] * (t1 * ucc[k - 1] + t2 * ucc[k - 2]) +
+                                         g["DPSDYM"][0] * (t1 * vcc[k - 1] + t2 * vcc[k - 2])))
+    return np.where(G.box("e", False)[None], qdot, 0.0)
 
 
 def hydro_tend(rc, g, dt, xbc, relax=True, diffuse=True, revert=None, tiles=None):
@@ -596,27 +826,15 @@ def hydro_tend(rc, g, dt, xbc, relax=True, diffuse=True, revert=None, tiles=None
     u1, v1, t1, q1, qc1 = g["ATM1_U"], g["ATM1_V"], g["ATM1_T"], g["ATM1_QV"], g["ATM1_QC"]
     pa, pb = g["PSA"][0], g["PSB"][0]
     msfx, msfd = g["MSFX"][0], g["MSFD"][0]
-    psd = psc2psd(pa)                                            # psdota, the edge lines included
-    rpsd = 1.0 / psd
+    G = geom(rc)
+    psd = psc2psd(pa, G)                                         # psdota, the edge lines included
     rpsa = np.divide(1.0, pa, out=np.zeros_like(pa), where=pa > 0)
     umc, vmc = u1 * msfd, v1 * msfd
-    ud, vd = u1 * rpsd, v1 * rpsd
-    if rc.iboudy in (3, 4):
-        # decouple's inflow / outflow dependence (Main/mod_tendency.F90:908-918, 933-943, 958-968,
-        # 983-993): an outflow edge value is the first interior line's; west, east over idi, then
-        # south, north over jde (the corners read the lines just set).  After bdyval the boundary
-        # slices wue.. hold atm1 on the edge lines.
-        for a in (ud, vd):
-            a[:, 1:-1, 0] = np.where(u1[:, 1:-1, 0] <= 0.0, a[:, 1:-1, 1], a[:, 1:-1, 0])
-            a[:, 1:-1, -1] = np.where(u1[:, 1:-1, -1] >= 0.0, a[:, 1:-1, -2], a[:, 1:-1, -1])
-            a[:, 0, :] = np.where(v1[:, 0, :] >= 0.0, a[:, 1, :], a[:, 0, :])
-            a[:, -1, :] = np.where(v1[:, -1, :] <= 0.0, a[:, -2, :], a[:, -1, :])
+    ud, vd = decouple_uv(rc, g, psd)
     old_err = np.seterr(divide="ignore", invalid="ignore")      # frame edges: never compared
     cr, pten, qdot = compute_omega(rc, g)
     # new_pressure: the boundary term of p*
-    pten0 = pten.copy()                                          # on jce x ice; the unused line zeroed
-    pten0[-1, :] = 0.0
-    pten0[:, -1] = 0.0
+    pten0 = pten.copy()                                          # on jce x ice, zero off it
     pinc = []
     if sponging:
         ptot = sponge(rc, pten0, g["XPSB_BT"][0], False, tab)
@@ -645,7 +863,7 @@ def hydro_tend(rc, g, dt, xbc, relax=True, diffuse=True, revert=None, tiles=None
         fy2 = (1.0 + f2) * c + (1.0 - f2) * n
         return -xmsf * (u2a * fx2 - u1a * fx1 + v2a * fy2 - v1a * fy1), w, e_, s_, n
 
-    ub, vb, tb, qvb, qcb, pdb = b_slices(g)
+    ub, vb, tb, qvb, qcb, pdb = b_slices(g, G)
     co = hydro_coeff(rc, g)
     if not diffuse:
         co = {k: np.zeros_like(v) for k, v in co.items()}

@@ -1,9 +1,13 @@
-"""A NumPy statement of one step of the UW-PBL turbulent kinetic energy in the hydrostatic core
-(ibltyp = 2) on a limited-area domain: the tend rows and bdyval's TKE lines.  Written from the
-Fortran text; nothing here reads the oracle or the engine.  A sibling of tests/dyn_ref.py, which
-supplies compute_omega's qdot, the diffusion coefficients and the diffusion forms.  Test
-infrastructure: tests/test_tke_rows_cpu.py compares the oracle with it, tests/test_tke_rows_gpu.py the
-engine.
+"""A NumPy statement of one step of the UW-PBL turbulent kinetic energy (ibltyp = 2) in either core,
+on a limited area, a band (i_band = 1) or the cloud-resolving grid (i_crm = 1): the tend rows and
+bdyval's TKE lines.  Written from the Fortran text; nothing here reads the oracle or the engine.  A
+sibling of tests/dyn_ref.py, which supplies the grid (geom), compute_omega's qdot of either core
+(compute_omega, nh_qdot), the diffusion coefficients (hydro_coeff, nh_coeff) and the diffusion forms.
+The TKE rows themselves are the same text in both cores; the cores differ in qdot and in calc_coeff.
+A periodic direction has no boundary line: bdyval acts on the south and north lines of a band, over
+every j, and on nothing under CRM.  Test infrastructure: tests/test_tke_rows_cpu.py and
+tests/test_periodic_rows_cpu.py compare the oracle with it, tests/test_tke_rows_gpu.py and
+tests/test_periodic_rows_gpu.py the engine.
 
 Every expression keeps the operation order of the text (left to right, the parentheses of the
 source), in float64.  The chain holds no transcendental function (calc_coeff's sqrt is correctly
@@ -19,18 +23,29 @@ rounded), so it is comparable bit for bit.
                     and 3 (xkc read on kz + 1 levels)              602-651; called Main/mod_tendency.F90:1545-1548
   the sum, forecast tketen + tkedyn*rpsa + tkephy, max(tkemin,.) Main/mod_tendency.F90:515-542
   filter_ra_3d      timefilter_apply(atm1, atm2, atmc, gnu2)     Main/mod_tendency.F90:543; Main/mod_timefilter.F90:92-110
+  compute_omega     qdot of either core (dyn_ref.compute_omega,   Main/mod_tendency.F90:1118-1178
+                    dyn_ref.nh_qdot)
+  calc_coeff        xkc of either core (dyn_ref.hydro_coeff,      Main/mod_diffusion.F90:193-249
+                    dyn_ref.nh_coeff)
   bdyuv             the wind slices of the inflow / outflow test  Main/mod_bdycod.F90:896-1061
   bdyval            atm2 = atm1 on the lines; tkemin on level 1;  Main/mod_bdycod.F90:1166-1172, 1212-1218,
                     inflow tkemin / outflow interior neighbour     1258-1264, 1301-1307, 2433-2514
 
 Arrays are (k, i, j) with the Fortran point (j, i, k) at [k - 1, i - 1, j - 1], kz + 1 levels; cross
-fields hold i = 1..iy-1, j = 1..jx-1.
+fields hold i = 1..iy-1, j = 1..jx-1, and every point of a periodic direction.
 """
 import numpy as np
 
 from tests import dyn_ref as dr
 
 TKE_INPUTS = ("ATM1_TKE", "ATM2_TKE", "TKEPHY")
+BDY_WINDS = ("XUB_B0", "XUB_BT", "XVB_B0", "XVB_BT")
+NH_INPUTS = tuple(dict.fromkeys(dr.NH_QDOT_INPUTS + ("ATM2_U", "ATM2_V", "ATM2_W", "PSB", "MSFX", "HT") + BDY_WINDS))
+
+
+def input_names(rc):
+    """The fields tke_tend and tke_bdyval read, by core."""
+    return (dr.HYDRO_INPUTS if rc.idynamic == 1 else NH_INPUTS) + TKE_INPUTS
 
 
 def sigma_weights(rc):
@@ -38,12 +53,8 @@ def sigma_weights(rc):
     indexed by the 1-based k = 1..kz+1 with dds(1) = dds(kzp1) = 0 (Main/mod_advection.F90:100-105)."""
     kz = rc.kz
     sig = rc.sigma
-    hsig = (sig[1:] + sig[:-1]) * 0.5
     dsig = sig[1:] - sig[:-1]
-    twt1, twt2 = np.zeros(kz + 1), np.zeros(kz + 1)
-    for k in range(2, kz + 1):
-        twt1[k] = (sig[k - 1] - hsig[k - 2]) / (hsig[k - 1] - hsig[k - 2])
-        twt2[k] = 1.0 - twt1[k]
+    twt1, twt2 = dr.twt(rc)
     dds = np.zeros(kz + 2)
     for k in range(2, kz + 1):
         dds[k] = 1.0 / (dsig[k - 1] + dsig[k - 2])
@@ -55,9 +66,13 @@ def interior(rc):
     return dr.domain_mask(rc)
 
 
-def tke_tend(rc, g, tke1, tke2, tkephy, dt, tiles=None):
-    """The TKE rows of one hydrostatic tend.  g: dyn_ref.HYDRO_INPUTS after bdyval; tke1, tke2: atm1 /
+def tke_tend(rc, g, tke1, tke2, tkephy, dt, tiles=None, hydro_qdot=False, swap_twt=False):
+    """The TKE rows of one tend of either core.  g: input_names(rc) after bdyval; tke1, tke2: atm1 /
     atm2 tke (decoupled); tkephy: the UW scheme's tendency; dt: the step's dt (rcmdyn get_time).
+    qdot is compute_omega's of the core (rc.idynamic) and the coefficient calc_coeff's.  The last two
+    arguments are mutants for the tests' non-vacuity asserts: hydro_qdot takes the hydrostatic qdot in
+    the non-hydrostatic core; swap_twt exchanges nh_qdot's weights (dyn_ref.zero_pad_for_the_wrap is a
+    third, of every neighbour read).
     Returns atm1 / atm2 tke after the time filter (`a1`, `a2`) and the stages: `had` (tkedyn after
     hadv3d), `adv` (after vadv3d), `dif` (the diffusion increments), `dyn` (tkedyn), `ten` (tketen), `raw`
     (atm2 + dt tketen), `fc` (atmc), `qdot`.  tiles: the decomposition, for idiffu = 3 alone."""
@@ -70,7 +85,10 @@ def tke_tend(rc, g, tke1, tke2, tkephy, dt, tiles=None):
     sh = dr.sh
     m = interior(rc)
     old_err = np.seterr(divide="ignore", invalid="ignore")      # frame edges: masked off below
-    _, _, qdot = dr.compute_omega(rc, g)
+    if rc.idynamic == 1 or hydro_qdot:
+        _, _, qdot = dr.compute_omega(rc, g)
+    else:
+        qdot = dr.nh_qdot(rc, g, swap_twt=swap_twt)
     umc, vmc = g["ATM1_U"] * msfd, g["ATM1_V"] * msfd
     uavg1 = sh(umc, 0, 1) + umc                                  # ua(j,i+1,k) + ua(j,i,k)
     uavg2 = sh(umc, 1, 1) + sh(umc, 1, 0)                        # ua(j+1,i+1,k) + ua(j+1,i,k)
@@ -116,7 +134,7 @@ def tke_tend(rc, g, tke1, tke2, tkephy, dt, tiles=None):
     # ---- diffu_x3df(tkedyn, atm2%tke, nuk): xkcf(1) = xkc(1), xkcf(k+1) = xkc(k), scaled like xkc
     # (:232-245).  At idiffu = 3 the text reads xkc(j,i,k) up to k = kzp1, one level past xkc's kz; the
     # coefficient is diff_6th_coef * p*b on every level (what xkcf holds), which is what is taken here.
-    co = dr.hydro_coeff(rc, g)
+    co = dr.hydro_coeff(rc, g) if rc.idynamic == 1 else dr.nh_coeff(rc, g)
     xkcf = np.concatenate([co["xkc"][:1], co["xkc"]], axis=0)
     if rc.idiffu == 3:
         dif = dr.diffu6(rc, tke2, tke2 / msfd[None], xkcf, dr.tile_columns(rc, False, tiles), dot=False, fac=rc.nuk)
@@ -137,28 +155,47 @@ def tke_tend(rc, g, tke1, tke2, tkephy, dt, tiles=None):
 
 
 def bdyuv_slices(rc, u1, v1, b, xt):
-    """bdyuv on one limited-area tile, iboudy /= 0: the u slices west / east and the v slices south /
-    north, exterior (the boundary value b0 + xt bt on jde1 / jde2 / ide1 / ide2) and interior (atm1 on
-    jdi1 / jdi2 / idi1 / idi2), (kz, iy + 2) or (kz, jx + 2) indexed by the 1-based i or j, zero where
-    never written, with the corner fills of the interior slices (:1030-1061)."""
+    """bdyuv on the whole grid as one tile, iboudy /= 0: the u slices west / east and the v slices
+    south / north, exterior (the boundary value b0 + xt bt on jde1 / jde2 / ide1 / ide2) and interior
+    (atm1 on jdi1 / jdi2 / idi1 / idi2), (kz, iy + 2) or (kz, jx + 2) indexed by the 1-based i or j, zero
+    where never written.  Each only on a side that exists (`if ( ma%has_bdyleft )` .., :909-1025).  The
+    corner fills of the interior slices (:1030-1061) stand under has_bdytopleft .. alone, which need
+    two sides: a band has none, and its south / north interior slices are whole already, since
+    jdi1..jdi2 is every j; the j + 1 past jx that bdyval reads is the slice at j = 1
+    (exchange_bdy_lr, :1063-1076)."""
     kz, iy, jx = rc.kz, rc.iy, rc.jx
+    G = dr.geom(rc)
+    if not (G.left or G.right or G.bottom or G.top):
+        return {}
     ub = b["XUB_B0"] + xt * b["XUB_BT"]
     vb = b["XVB_B0"] + xt * b["XVB_BT"]
-    ri = np.arange(2, iy)                                        # idi1..idi2
-    rj = np.arange(2, jx)                                        # jdi1..jdi2
-    re = np.arange(1, jx + 1)                                    # jde1..jde2
+    ri = np.arange(G.idi1, G.idi2 + 1)
+    rj = np.arange(G.jdi1, G.jdi2 + 1)
+    re = np.arange(G.jde1, G.jde2 + 1)
     sl = {n: np.zeros((kz, iy + 2)) for n in ("wue", "wui", "eue", "eui")}
     sl.update({n: np.zeros((kz, jx + 2)) for n in ("sve", "svi", "nve", "nvi", "sue", "nue")})
-    sl["wui"][:, ri], sl["eui"][:, ri] = u1[:, ri - 1, 1], u1[:, ri - 1, jx - 2]
-    sl["wue"][:, ri], sl["eue"][:, ri] = ub[:, ri - 1, 0], ub[:, ri - 1, jx - 1]
-    sl["svi"][:, rj], sl["nvi"][:, rj] = v1[:, 1, rj - 1], v1[:, iy - 2, rj - 1]
-    sl["sve"][:, re], sl["nve"][:, re] = vb[:, 0, re - 1], vb[:, iy - 1, re - 1]
-    sl["sue"][:, re], sl["nue"][:, re] = ub[:, 0, re - 1], ub[:, iy - 1, re - 1]
+    if G.left:
+        sl["wui"][:, ri], sl["wue"][:, ri] = u1[:, ri - 1, G.jdi1 - 1], ub[:, ri - 1, G.jde1 - 1]
+    if G.right:
+        sl["eui"][:, ri], sl["eue"][:, ri] = u1[:, ri - 1, G.jdi2 - 1], ub[:, ri - 1, G.jde2 - 1]
+    if G.bottom:
+        sl["svi"][:, rj] = v1[:, G.idi1 - 1, rj - 1]
+        sl["sve"][:, re], sl["sue"][:, re] = vb[:, G.ide1 - 1, re - 1], ub[:, G.ide1 - 1, re - 1]
+    if G.top:
+        sl["nvi"][:, rj] = v1[:, G.idi2 - 1, rj - 1]
+        sl["nve"][:, re], sl["nue"][:, re] = vb[:, G.ide2 - 1, re - 1], ub[:, G.ide2 - 1, re - 1]
     we = {"wve": vb[:, :, 0], "eve": vb[:, :, jx - 1]}           # wve / eve at idi1 and idi2
-    sl["wui"][:, iy], sl["wui"][:, 1] = sl["nue"][:, 2], sl["sue"][:, 2]
-    sl["eui"][:, iy], sl["eui"][:, 1] = sl["nue"][:, jx - 1], sl["sue"][:, jx - 1]
-    sl["nvi"][:, 1], sl["svi"][:, 1] = we["wve"][:, iy - 2], we["wve"][:, 1]
-    sl["nvi"][:, jx], sl["svi"][:, jx] = we["eve"][:, iy - 2], we["eve"][:, 1]
+    if G.top and G.left:
+        sl["wui"][:, iy], sl["nvi"][:, 1] = sl["nue"][:, 2], we["wve"][:, iy - 2]
+    if G.bottom and G.left:
+        sl["wui"][:, 1], sl["svi"][:, 1] = sl["sue"][:, 2], we["wve"][:, 1]
+    if G.top and G.right:
+        sl["eui"][:, iy], sl["nvi"][:, jx] = sl["nue"][:, jx - 1], we["eve"][:, iy - 2]
+    if G.bottom and G.right:
+        sl["eui"][:, 1], sl["svi"][:, jx] = sl["sue"][:, jx - 1], we["eve"][:, 1]
+    if G.perj:
+        for n in ("sve", "svi", "nve", "nvi", "sue", "nue"):
+            sl[n][:, jx + 1], sl[n][:, 0] = sl[n][:, 1], sl[n][:, jx]
     return sl
 
 
@@ -167,29 +204,40 @@ def tke_bdyval(rc, a1, a2, u1, v1, b, xt):
     after tend; u1, v1: atm1 u, v after tend, of which only the lines jdi1, jdi2, idi1, idi2 are read (the
     interior slices of the inflow / outflow test); b: the boundary fields XUB / XVB _B0 / _BT; xt =
     xbctime + dt at the call.  Returns (atm1, atm2, inflow) with inflow {side: bool (kz - 1, n)} the
-    choice at the levels k + 1 = 3..kz+1 of each line.
+    choice at the levels k + 1 = 3..kz+1 of each line that exists.
 
-    In the text's order: atm2 = atm1 on the four lines (west / east over ici1..ici2, south / north over
+    In the text's order: atm2 = atm1 on the lines (west / east over ici1..ici2, south / north over
     jce1..jce2), from atm1 before it takes its new boundary values; then, west, east, south, north:
     level 1 of both time levels is tkemin along the whole line; for k = 2..kz the level k + 1 of atm1 is
     tkemin where the eight-wind sum of levels k and k - 1 blows in and the first interior point's
     value (read when its turn comes) where it does not.  Level 2 of the lines is never written.  West
-    and east run over ice1..ice2 (the corners theirs), south and north over jci1..jci2."""
-    kz, iy, jx = rc.kz, rc.iy, rc.jx
+    and east run over ice1..ice2 (the corners theirs), south and north over jci1..jci2.  Every block
+    stands under its side's has_bdy flag: a band has the south and north lines alone, over every j
+    (jce = jci = 1..jx), and the CRM grid has none, so that bdyval changes no TKE value there."""
+    kz = rc.kz
+    G = dr.geom(rc)
     a1, a2 = a1.copy(), a2.copy()
-    ci = np.arange(2, iy - 1)                                    # ici1..ici2
-    a2[:, ci - 1, 0] = a1[:, ci - 1, 0]
-    a2[:, ci - 1, jx - 2] = a1[:, ci - 1, jx - 2]
-    a2[:, 0, :jx - 1] = a1[:, 0, :jx - 1]
-    a2[:, iy - 2, :jx - 1] = a1[:, iy - 2, :jx - 1]
+    ci = np.arange(G.ici1, G.ici2 + 1)
+    je = slice(G.jce1 - 1, G.jce2)
+    if G.left:
+        a2[:, ci - 1, G.jce1 - 1] = a1[:, ci - 1, G.jce1 - 1]
+    if G.right:
+        a2[:, ci - 1, G.jce2 - 1] = a1[:, ci - 1, G.jce2 - 1]
+    if G.bottom:
+        a2[:, G.ice1 - 1, je] = a1[:, G.ice1 - 1, je]
+    if G.top:
+        a2[:, G.ice2 - 1, je] = a1[:, G.ice2 - 1, je]
     sl = bdyuv_slices(rc, u1, v1, b, xt)
     tkemin = rc.tkemin
     inflow = {}
-    ie = np.arange(1, iy)                                        # ice1..ice2
-    jc = np.arange(2, jx - 1)                                    # jci1..jci2
-    for side, ext, itr, col, cin, sign in (("west", "wue", "wui", 0, 1, 1.0), ("east", "eue", "eui", jx - 2, jx - 3, -1.0)):
-        a1[0, :iy - 1, col] = tkemin
-        a2[0, :iy - 1, col] = tkemin
+    ie = np.arange(G.ice1, G.ice2 + 1)
+    jc = np.arange(G.jci1, G.jci2 + 1)
+    for has, side, ext, itr, col, cin, sign in ((G.left, "west", "wue", "wui", G.jce1 - 1, G.jci1 - 1, 1.0),
+                                                (G.right, "east", "eue", "eui", G.jce2 - 1, G.jci2 - 1, -1.0)):
+        if not has:
+            continue
+        a1[0, ie - 1, col] = tkemin
+        a2[0, ie - 1, col] = tkemin
         flow = np.zeros((kz - 1, ie.size), dtype=bool)
         for k in range(2, kz + 1):
             e, n = sl[ext], sl[itr]
@@ -198,10 +246,12 @@ def tke_bdyval(rc, a1, a2, u1, v1, b, xt):
             flow[k - 2] = sign * windavg > 0.0
             a1[k, ie - 1, col] = np.where(flow[k - 2], tkemin, a1[k, ie - 1, cin])
         inflow[side] = flow
-    for side, ext, itr, row, rin, sign in (("south", "sve", "svi", 0, 1, 1.0),
-                                           ("north", "nve", "nvi", iy - 2, iy - 3, -1.0)):
-        a1[0, row, :jx - 1] = tkemin
-        a2[0, row, :jx - 1] = tkemin
+    for has, side, ext, itr, row, rin, sign in ((G.bottom, "south", "sve", "svi", G.ice1 - 1, G.ici1 - 1, 1.0),
+                                                (G.top, "north", "nve", "nvi", G.ice2 - 1, G.ici2 - 1, -1.0)):
+        if not has:
+            continue
+        a1[0, row, je] = tkemin
+        a2[0, row, je] = tkemin
         flow = np.zeros((kz - 1, jc.size), dtype=bool)
         for k in range(2, kz + 1):
             e, n = sl[ext], sl[itr]
